@@ -17,7 +17,7 @@ with HIP events on the launch stream inside the timed region (libtrh's timing ho
 `cpu_baseline` times oracle/cpu_ref.cpp (the C++ restatement of halo2_proofs' rayon
 best_multiexp; kind "port") on a bounded sample on this box's host cores.
 
-Outside the timed headline region the same process also reports
+With --full, outside the timed headline region the same process also reports
   sweep            (N = 1) MSM at 2^20 / 2^22 / 2^26 and NTT at 2^20 / 2^24, each checked (closed form / inverse round trip) with
                    its own roofline fraction -- north_star's 2^20 .. 2^26 size range;
   strong           (N > 1) BASELINE config 5: ONE 2^26 Pallas MSM range-sharded over the N ranks (2^26 / N pairs each), same
@@ -32,6 +32,12 @@ Outside the timed headline region the same process also reports
   collective       which backend carried the partials, over how many ranks and which devices, proven by an all-reduce.
 `python bench.py --gpus N` WITHOUT a torch.distributed.run environment spawns its N ranks itself (fresh child processes, started
 before this process makes any GPU call; the parent only waits and relays rank 0's line).
+A plain run does only what the headline needs: set up, warm up, time the --steps steps, write --dump-outputs, print the line.  The result
+checks (`check`, `collective.all_gather_points`), `secondary` (the NTT), `cpu_baseline`, `with_base_conversion` and the extras below run only
+with --full (each still switched off by its own --no-* flag); a --full run is what a plain run was before --full existed.
+`--dump-outputs DIR` writes what the timed path returned in its last step: DIR/msm_point.npy, the 12 u64 limbs of the point (X, Y, Z,
+Montgomery, normalised to Z = 1) as float64 16-bit digits, shape (3, 4, 4) = (coordinate, limb, digit, least significant first).  The
+inputs are fixed by the arguments (seeded scalars, bases (s0 + i d) G), so two builds can be compared output for output.
 `--global-log-n L` makes the HEADLINE run strong-scaling instead (2^L pairs in total, split over the ranks); the JSON line
 says which mode produced `value`.  A failed result check prints the line with "check": "MISMATCH" and exits with status 1.
 """
@@ -194,6 +200,14 @@ def msm_roofline(n, acc_ms, tm, traffic):
 MADD_MIX = {"v_mad_i64_i32": 1179, "v_and_b32": 156, "v_lshl_add_u64": 147, "v_ashrrev_i64": 144, "v_mov_b32": 23, "other_32bit_alu": 84}
 # marginal SIMD cycles next to multiply-adds at 3 waves per SIMD (profiles/issue_probe_r04.txt, `norm` column; other_32bit_alu priced as v_add_u32)
 ISSUE_CYCLES = {"v_mad_i64_i32": 4.0, "v_and_b32": 2.80, "v_lshl_add_u64": 3.58, "v_ashrrev_i64": 3.11, "v_mov_b32": 1.50, "other_32bit_alu": 2.80}
+
+
+def dump_outputs(out_dir: str, point) -> None:
+    """the 12 u64 limbs of the headline step's point as exact float64 16-bit digits, shape (3, 4, 4): (X / Y / Z, limb, digit)"""
+    limbs = np.asarray(point, dtype=np.uint64).reshape(3, 4)
+    digits = np.stack([(limbs >> np.uint64(16 * k)) & np.uint64(0xFFFF) for k in range(4)], axis=-1)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "msm_point.npy"), digits.astype(np.float64))
 
 
 def spawn_ranks(args) -> int:
@@ -451,7 +465,14 @@ def main():
     ap.add_argument("--global-log-n", type=int, default=0, help="strong scaling: 2^L pairs in TOTAL, range-sharded over the ranks (default: weak, 2^log-n per GPU)")
     ap.add_argument("--no-sweep", action="store_true", help="skip the size sweep / strong-scaling / single-process extras (profiling runs)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the k = 18 create_proof replays (N = 1 only; implied by --no-sweep)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: result checks, NTT secondary, CPU baseline, base-conversion rate, "
+                                                         "size sweep / strong-scaling / single-process / e2e legs (default: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the point the last timed step returned to DIR/msm_point.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: set-up, warm-up and the timed steps of the headline, nothing else
+        args.no_check = args.no_cpu_baseline = args.no_sweep = args.no_e2e = True
     if args.single_process_child is not None:
         sys.exit(single_process_child([int(v) for v in args.single_process_child.split(",")], args.steps))
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -641,7 +662,9 @@ def main():
     wl = Workload(lo, n)
     result, elapsed, acc, phase, tm = time_msm(wl, args.steps, args.warmup)
     check = None if args.no_check else check_msm(wl, result)
-    if world == 1 and launched:  # sharded_msm short-cuts a world of one: the gather of the 96-byte partial still goes through the backend once
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, result)
+    if args.full and world == 1 and launched:  # sharded_msm short-cuts a world of one: the gather of the 96-byte partial still goes through the backend once
         got = sharded.all_gather_points(np.asarray(result, dtype=np.uint64).reshape(12), device=coll_dev)
         collective["all_gather_points"] = "ok" if got.shape == (1, 12) and bool((got[0] == np.asarray(result, dtype=np.uint64).reshape(12)).all()) else "MISMATCH"
         if collective["all_gather_points"] != "ok":
@@ -710,9 +733,10 @@ def main():
                              "traffic_gbs": (traffic / (ms * 1e-3) / 1e9) if traffic else None}}
 
     ln = args.ntt_log_n
-    ms, chk = time_ntt(ln, max(args.steps, 5) * 4, max(args.warmup, 2), not args.no_check, keep_forward=world == 1 and not args.no_cpu_baseline)
     ntt = None
-    if rank == 0:
+    if args.full:
+        ms, chk = time_ntt(ln, max(args.steps, 5) * 4, max(args.warmup, 2), not args.no_check, keep_forward=world == 1 and not args.no_cpu_baseline)
+    if args.full and rank == 0:
         ntt = ntt_entry(ln, ms, chk)
         ntt["mode"] = "one transform per GPU at a time (independent columns, no collective)" if world > 1 else "single GPU"
         if world == 1 and not args.no_cpu_baseline:

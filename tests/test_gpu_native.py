@@ -44,7 +44,7 @@ def test_bench_two_ranks_on_one_device():
     import sys
     env = dict(os.environ, TRH_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29533",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--log-n", "20", "--ntt-log-n", "16"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--log-n", "20", "--ntt-log-n", "16", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:] + r.stdout[-2000:]
     out = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
@@ -80,7 +80,7 @@ def test_bench_spawns_its_own_ranks():
     import sys
     env = dict(os.environ, TRH_BENCH_BACKEND="gloo", TRH_BENCH_SINGLE_PROCESS="0")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--log-n", "18", "--ntt-log-n", "14", "--no-sweep"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--log-n", "18", "--ntt-log-n", "14", "--full", "--no-sweep"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:] + r.stdout[-2000:]
     out = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
@@ -120,10 +120,35 @@ def test_bench_one_rank_rccl_first_contact():
         port = sk.getsockname()[1]
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), TRH_BENCH_BACKEND="nccl",
                HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--log-n", "16", "--no-sweep", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--log-n", "16", "--full", "--no-sweep", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:] + r.stdout[-2000:]
     out = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
     c = out["collective"]
     assert c["backend"] == "nccl" and c["ok"] is True and c["world"] == 1 and c["all_reduce_of_ones"] == 1, c
     assert c["all_gather_points"] == "ok" and out["check"] == "closed-form ok", (c, out["check"])
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_its_last_step(tmp_path):
+    """a plain run times exactly --steps steps of the headline, runs none of the --full legs and writes the point its last step returned;
+    the same arguments with --full close the closed-form check on the same point"""
+    import sys
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--log-n", "16"]
+    outs = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-sweep", "--no-cpu-baseline", "--ntt-log-n", "14"])):
+        r = subprocess.run(cmd + extra + ["--dump-outputs", str(tmp_path / mode)], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:] + r.stdout[-2000:]
+        outs[mode] = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
+    plain, full = outs["plain"], outs["full"]
+    assert plain["steps"] == 3 and plain["warmup"] == 1 and plain["ms_per_step"] > 0 and plain["unit"] == "pairs/s" and plain["higher_is_better"] is True
+    assert abs(plain["value"] * plain["ms_per_step"] * 1e-3 - (1 << 16)) < 1e-6 * (1 << 16)
+    assert plain["check"] is None and plain["secondary"] is None
+    assert not {"sweep", "e2e", "cpu_baseline", "with_base_conversion", "e2e_summary"} & set(plain)
+    assert full["check"] == "closed-form ok" and full["secondary"]["check"] == "inverse round trip ok"
+    pts = {m: np.load(tmp_path / m / "msm_point.npy") for m in outs}
+    assert pts["plain"].dtype == np.float64 and pts["plain"].shape == (3, 4, 4) and (pts["plain"] == pts["full"]).all()
+    assert (pts["plain"] == np.floor(pts["plain"])).all() and pts["plain"].min() >= 0 and pts["plain"].max() < 1 << 16

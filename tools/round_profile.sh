@@ -13,7 +13,9 @@ REPO=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$REPO"
 if [ "$MODE" = collect ]; then
     bash tools/profile.sh "$TAG" > gpurun_out/profile_$TAG.log 2>&1
-    python3 bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err
+    # the whole bench line (--full: checks, CPU baseline, NTT, sweep, e2e), written beside the prof_<tag>/ folder tools/profile.sh just filled
+    OUT=$(dirname "$(ls -d "$REPO"/*/prof_"$TAG" | head -1)")
+    python3 bench.py --full > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err"
     python3 -m tiny_ram_halo2_amd.replay --word-bits 32 2>/dev/null | tail -1 > gpurun_out/replay_$TAG.json
     python3 -m tiny_ram_halo2_amd.replay --word-bits 32 --columns witness --overlap 2>/dev/null | tail -1 > gpurun_out/replay_witness_$TAG.json
     LD_LIBRARY_PATH=tiny-ram-halo2_amd ./examples/replay --word-bits 32 --columns witness 2>/dev/null | tail -1 > gpurun_out/native_replay_witness_$TAG.json

@@ -54,7 +54,7 @@ def main():
                       "from kernels group by name order by sum(duration) desc").fetchall()
     total = sum(r[2] for r in rows) or 1
     lines = [f"# rocprofv3 --kernel-trace --stats summary ({tag})", "",
-             "Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 8 --warmup 2 --no-cpu-baseline --no-check --no-sweep`",
+             "Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 8 --warmup 2 --full --no-cpu-baseline --no-check --no-sweep`",
              "(2 warm-up + 8 timed 2^%d Pallas MSMs, then the 2^%d Fp NTT loop).  Durations in microseconds." % (msm_log_n, ntt_log_n), "",
              "`VGPR (ISA)` is the kernel's .vgpr_count from the code object (tools/isa_regs.py -> profiles/isa_registers.json); `VGPR (rocprofv3)` is the",
              "trace's own column, an allocation-granule count on gfx950 (half the ISA figure for the kernels here).", "",
