@@ -1316,6 +1316,16 @@ int trh_stat(const char* name, uint64_t* value) {
     TRH_ENTER(0);
     if (strcmp(name, "msm_lean_retries") == 0) { *value = ctx().msm.lean_retries; return TRH_OK; }
     if (strcmp(name, "msm_small_launches") == 0) { *value = ctx().msm.small_launches; return TRH_OK; }
+    if (strcmp(name, "msm_bin_sorted_windows") == 0) {  // synchronises the device: tests only
+        const MsmScratch& m = ctx().msm;
+        *value = 0;
+        if (!m.sort_flags) return TRH_OK;
+        std::vector<u32> flags(m.sort_flag_count);
+        TRH_HIP_TRY(hipDeviceSynchronize());
+        TRH_HIP_TRY(hipMemcpy(flags.data(), m.sort_flags, flags.size() * 4, hipMemcpyDeviceToHost));
+        for (u32 k = 0; k < m.sort_flag_count; ++k) *value += flags[k] == 0u;
+        return TRH_OK;
+    }
     if (strcmp(name, "ipa_generator_collapses") == 0) { *value = ctx().ipa_collapses; return TRH_OK; }
     set_error("trh_stat: unknown counter '%s'", name);
     return TRH_EINVAL;

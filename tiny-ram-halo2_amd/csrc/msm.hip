@@ -364,6 +364,10 @@ constexpr u32 BIN_CAP_MAX = BIN_THREADS * BIN_PER_MAX; // 36864 entries
 // scatters -- 72 entries per thread spill and the sort went from 1.61 to 2.29 ms at 2^24.  Round 2: a workgroup taking 8 consecutive
 // bins with the NEXT bin's 36 entries per thread in flight in a second register array while the current bin is sorted in the LDS:
 // 128 VGPRs + 132 B of scratch, sort 1.66 -> 1.73 ms -- the register arrays, not the unoverlapped loads, are what it costs.)
+// PER = entries per thread: the launch's bin_cap / BIN_THREADS rounded up to 8, 18 or BIN_PER_MAX.  With all of a thread's loads in
+// flight the kernel holds PER registers of entries plus their addresses (PER = 36: 116 VGPRs, 4 waves per SIMD), so the smaller
+// shapes (2^20 / 2^22 pairs: stages of 20 / 72 KB) get a form small enough for the occupancy their LDS allows.
+template <int PER>
 __global__ void __launch_bounds__(BIN_THREADS) msm_bin_sort_kernel(const u32* __restrict__ parted, const u32* __restrict__ bin_starts, const u32* __restrict__ bin_ends,
                                                                    u32* __restrict__ sorted, u32* __restrict__ starts, u32* __restrict__ ends, size_t n, int k2, u32 nbins,
                                                                    int idx_bits, u32 nbk, const u32* __restrict__ oversize) {
@@ -382,16 +386,19 @@ __global__ void __launch_bounds__(BIN_THREADS) msm_bin_sort_kernel(const u32* __
     const u32 lane = threadIdx.x & 63u;
     if (threadIdx.x < 128) cnt[threadIdx.x] = 0;
     __syncthreads();
-    u32 mine[BIN_PER_MAX];
+    // every load is issued before the first histogram atomic: a load and its atomic in one guarded step compiled to load, wait for
+    // HBM, atomic -- 36 round trips one after the other, 16 x 256 B in flight per CU (0.92 ms at 2^24, 2.3 TB/s).  Rows of the
+    // register array that lie wholly past the bin's end are skipped (uniform over the workgroup); in the last row lanes past the end
+    // read the bin's first entry (count > q * BIN_THREADS >= 0, so it exists) and drop it.
+    u32 mine[PER];
 #pragma unroll
-    for (int q = 0; q < BIN_PER_MAX; ++q) {
+    for (int q = 0; q < PER; ++q) {
         const u32 i = threadIdx.x + (u32)q * BIN_THREADS;
-        mine[q] = 0u;
-        if (i < count) {
-            mine[q] = src[i];
-            atomicAdd(&cnt[(mine[q] >> idx_bits) & low_mask], 1u);
-        }
+        mine[q] = (u32)q * BIN_THREADS < count ? src[i < count ? i : 0u] : 0u;
     }
+#pragma unroll
+    for (int q = 0; q < PER; ++q)
+        if (threadIdx.x + (u32)q * BIN_THREADS < count) atomicAdd(&cnt[(mine[q] >> idx_bits) & low_mask], 1u);
     __syncthreads();
     u32 v = 0, x = 0;
     if (threadIdx.x < 128) {  // exclusive scan of the sub-bucket counts inside the two waves that hold them
@@ -418,7 +425,7 @@ __global__ void __launch_bounds__(BIN_THREADS) msm_bin_sort_kernel(const u32* __
     }
     __syncthreads();
 #pragma unroll
-    for (int q = 0; q < BIN_PER_MAX; ++q) {
+    for (int q = 0; q < PER; ++q) {
         if (threadIdx.x + (u32)q * BIN_THREADS < count) {
             const u32 e = mine[q];
             const u32 sub = (e >> idx_bits) & low_mask;
@@ -427,7 +434,17 @@ __global__ void __launch_bounds__(BIN_THREADS) msm_bin_sort_kernel(const u32* __
         }
     }
     __syncthreads();
-    for (u32 i = threadIdx.x; i < count; i += BIN_THREADS) dst[i] = bstage[i];
+    // copy-out through the (now free) registers: all LDS reads in flight before the first store
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const u32 i = threadIdx.x + (u32)q * BIN_THREADS;
+        if (i < count) mine[q] = bstage[i];
+    }
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const u32 i = threadIdx.x + (u32)q * BIN_THREADS;
+        if (i < count) dst[i] = mine[q];
+    }
 }
 
 // per window: exclusive scan of the bucket counts -> starts / ends, cursor (in place of the counts).  Two launches over
@@ -1490,6 +1507,7 @@ int msm_enqueue_t(const void* bases_dev, const void* bases_z, const void* scalar
     MsmLane& L = m.lane;
     if (fb && (n == 0 || !msm_fixed_base_fits(n, fb->c))) fb = nullptr;
     if (!m.in_tile) m.tile_sum_valid = false;
+    m.sort_flags = nullptr; m.sort_flag_count = 0;
     if (!fb && batch == 1 && n > MSM_TILE && !m.in_tile && c.window_override == 0) {
         const size_t tiles = (n + MSM_TILE - 1) / MSM_TILE, len = (n + tiles - 1) / tiles;
         u64 acc[24];
@@ -1653,7 +1671,9 @@ int msm_enqueue_t(const void* bases_dev, const void* bases_z, const void* scalar
         m.host_sums_cap = hs + 4096;
     }
     if (!(c.attr_done & ATTR_MSM)) {  // per device
-        TRH_HIP_TRY(hipFuncSetAttribute((const void*)msm_bin_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BIN_CAP_MAX * 4));
+        TRH_HIP_TRY(hipFuncSetAttribute((const void*)msm_bin_sort_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * BIN_THREADS * 4));
+        TRH_HIP_TRY(hipFuncSetAttribute((const void*)msm_bin_sort_kernel<18>, hipFuncAttributeMaxDynamicSharedMemorySize, 18 * BIN_THREADS * 4));
+        TRH_HIP_TRY(hipFuncSetAttribute((const void*)msm_bin_sort_kernel<BIN_PER_MAX>, hipFuncAttributeMaxDynamicSharedMemorySize, BIN_CAP_MAX * 4));
         TRH_HIP_TRY(hipFuncSetAttribute((const void*)msm_partition_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PART_TILE * 4 + 2048 * 12));
         c.attr_done |= ATTR_MSM;
     }
@@ -1716,6 +1736,7 @@ int msm_enqueue_t(const void* bases_dev, const void* bases_z, const void* scalar
         }
         if (timing) TRH_HIP_TRY(hipEventRecord(m.ev[1], s));
         const bool bin_sort = use_bin && !compact;  // compact lists: ~2^11 entries per bin, and a flag column has them all in one: the chunked passes
+        m.sort_flags = bin_sort ? oversize : nullptr; m.sort_flag_count = bin_sort ? nb * (u32)Ws : 0u;
         if (bin_sort && !zero_fused) TRH_HIP_TRY(hipMemsetAsync(oversize, 0, (size_t)chunk * Ws * 4, s));
         hipLaunchKernelGGL(msm_offsets_kernel, dim3(Ws, 1, nb), dim3(1024), 0, s, L.counts.as<u32>(), L.bin_starts.as<u32>(), nbins, bin_sort ? oversize : nullptr, bin_cap,
                            (adaptive && mode == PIPE_PLAIN) ? totals : nullptr);
@@ -1763,9 +1784,16 @@ int msm_enqueue_t(const void* bases_dev, const void* bases_z, const void* scalar
         {
             const dim3 cgrid((unsigned)((nse + BS_CHUNK - 1) / BS_CHUNK), Ws, nb);
             const u32* gate = bin_sort ? oversize : nullptr;  // the chunked passes return at once when the bin sort did the work
-            if (bin_sort)
-                hipLaunchKernelGGL(msm_bin_sort_kernel, dim3(nbins, Ws, nb), dim3(BIN_THREADS), (size_t)bin_cap * 4, s, L.parted.as<u32>(), L.bin_starts.as<u32>(), L.counts.as<u32>(),
-                                   L.sorted.as<u32>(), L.starts.as<u32>(), L.ends.as<u32>(), nse, k2, nbins, idx_bits, nbk, oversize);
+            if (bin_sort) {
+#define TRH_LAUNCH_BIN_SORT(P)                                                                                                                      \
+    hipLaunchKernelGGL((msm_bin_sort_kernel<P>), dim3(nbins, Ws, nb), dim3(BIN_THREADS), (size_t)bin_cap * 4, s, L.parted.as<u32>(), L.bin_starts.as<u32>(), \
+                       L.counts.as<u32>(), L.sorted.as<u32>(), L.starts.as<u32>(), L.ends.as<u32>(), nse, k2, nbins, idx_bits, nbk, oversize)
+                // (entries per thread: the smallest form that holds bin_cap)
+                if (bin_cap <= 8u * BIN_THREADS) TRH_LAUNCH_BIN_SORT(8);
+                else if (bin_cap <= 18u * BIN_THREADS) TRH_LAUNCH_BIN_SORT(18);
+                else TRH_LAUNCH_BIN_SORT(BIN_PER_MAX);
+#undef TRH_LAUNCH_BIN_SORT
+            }
             if (!(lean_sort && bin_sort)) {
             if (!zero_fused) TRH_HIP_TRY(hipMemsetAsync(L.bucket_cnt.p, 0, (size_t)nb * Ws * nb1 * 4, s));
             hipLaunchKernelGGL((msm_bucket_pass_kernel<false>), cgrid, dim3(BS_THREADS), 0, s, L.parted.as<u32>(), L.bin_starts.as<u32>(), L.counts.as<u32>(),
