@@ -299,6 +299,38 @@ int trh_ipa_create_proof(trh_bases_t g_w, const uint64_t u_xy[8], uint32_t k, co
                          trh_rng_scalar_fn rng, void* rng_ctx, void* stream,
                          uint64_t out_c[4], uint64_t out_f[4]);
 
+/* ---- IPA verifier accumulator: poly::commitment::msm::MSM and verifier::Guard::use_challenges (halo2_proofs 0.2.0
+ *      poly/commitment/{msm.rs, verifier.rs}; reached from plonk::verify_proof / BatchVerifier::finalize after the proofs are made,
+ *      reference call site /root/reference/src/test_utils.rs:52-68) ----------------------------------------------------------
+ * The transcript, the challenges, compute_b and the multiopen verifier stay on the host; these entries hold MSM's arithmetic.
+ * g_w_u: the opening's resident set, g || w (2^k + 1 points) or g || w || u (2^k + 2; the last point must equal u_xy) -- with
+ * fixed-base tables attached, eval's MSM uses them.  The g scalars live on the device (2^k Montgomery words, fully reduced) and
+ * are absent, as halo2's `g_scalars: Option<Vec<_>>`, until add_constant_term / add_to_g_scalars_dev / use_challenges first sets them;
+ * w, u and the appended terms stay on the host.  Scalars are Montgomery words, points 8-word affine (all-zero = identity).
+ * Every call on an accumulator must come from the context that created it (trh_ctx_set_current); the stream arguments order the
+ * device work as elsewhere (add_constant_term enqueues on the stream of the accumulator's previous call).                      */
+typedef struct trh_ipa_msm* trh_ipa_msm_t;
+int trh_ipa_msm_create(trh_bases_t g_w_u, uint32_t k, const uint64_t u_xy[8], trh_ipa_msm_t* out);   /* Params::empty_msm (k >= 1) */
+void trh_ipa_msm_destroy(trh_ipa_msm_t m);
+int trh_ipa_msm_append_term(trh_ipa_msm_t m, const uint64_t scalar[4], const uint64_t point_xy[8]);   /* MSM::append_term */
+int trh_ipa_msm_add_constant_term(trh_ipa_msm_t m, const uint64_t c[4]);                              /* MSM::add_constant_term: g[0] += c */
+int trh_ipa_msm_add_to_w_scalar(trh_ipa_msm_t m, const uint64_t s[4]);
+int trh_ipa_msm_add_to_u_scalar(trh_ipa_msm_t m, const uint64_t s[4]);
+int trh_ipa_msm_add_to_g_scalars_dev(trh_ipa_msm_t m, const void* scalars_dev, void* stream);          /* MSM::add_to_g_scalars, 2^k device scalars */
+/* Guard::use_challenges for `count` (>= 1) guards in one pass over the 2^k g scalars:
+ *     g[i] = alpha g[i] + sum_p weights[p] neg_c[p] prod_{j : bit (k - 1 - j) of i set} u[p][j]
+ * u: count x k challenges (round order), neg_c: count scalars (-c), weights: count scalars or NULL (all one), alpha: NULL = one.
+ * count = 1 without weights / alpha is Guard::use_challenges (compute_s(u, neg_c) added to g); weights_p = prod_{q > p} r_q with
+ * alpha = prod_q r_q is BatchVerifier::finalize's chain of scale(r_q) / add_msm over the guards' MSMs, for their g parts.         */
+int trh_ipa_msm_use_challenges(trh_ipa_msm_t m, size_t count, const uint64_t* u, const uint64_t* neg_c, const uint64_t* weights,
+                               const uint64_t alpha[4], void* stream);
+int trh_ipa_msm_scale(trh_ipa_msm_t m, const uint64_t factor[4], void* stream);   /* MSM::scale: g, w, u and every appended scalar */
+int trh_ipa_msm_add_msm(trh_ipa_msm_t dst, trh_ipa_msm_t src, void* stream);       /* MSM::add_msm; same curve, context and base set */
+/* MSM::eval: one full-range MSM over g_w_u (trh_msm_dev) when the g part exists, the appended terms (and w / u where that MSM does not
+ * carry them) through the small MSM, the points added on the host.  is_identity: what eval returns; out_xyz: the point itself. */
+int trh_ipa_msm_eval(trh_ipa_msm_t m, void* stream, int* is_identity, uint64_t out_xyz[12]);
+const void* trh_ipa_msm_g_scalars_dev(trh_ipa_msm_t m);   /* the 2^k g scalars in device memory, NULL while there are none (tests, shims) */
+
 /* ---- grand-product building blocks of the permutation / lookup arguments ----------------------
  * (plonk/permutation/prover.rs, plonk/lookup/prover.rs: batch_invert of the denominators, then the
  * running product z[0] = 1, z[i] = z[i-1] * numerator[i-1] / denominator[i-1])                    */

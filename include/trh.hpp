@@ -10,6 +10,7 @@
 //                                                                      extended_to_coeff, divide_by_vanishing_poly }
 //   trh::Expression + compile_gates         plonk::Expression<F> and the y-folded evaluation of the gate polynomials
 //   trh::ipa_create_proof                   poly::commitment::create_proof (IPA opening)
+//   trh::IpaMsm                             poly::commitment::msm::MSM + Guard::use_challenges (the verifier's accumulator)
 //
 // Reference call sites of all of these: /root/reference/src/test_utils.rs:21-49, 89-104 (through keygen_* and
 // create_proof of the halo2_proofs crate pinned at /root/reference/Cargo.lock:619-621).
@@ -454,6 +455,51 @@ inline std::pair<Limbs, Limbs> ipa_create_proof(const Params& params, const Devi
                                rng_ctx, stream, c.data(), f.data()), "ipa create_proof");
     return {c, f};
 }
+
+// ---- poly::commitment::msm::MSM (the verifier's accumulator) over the opening's base set -------------------------------------
+// g scalars resident (absent until first set, as halo2's Option), w / u / appended terms on the host; eval() is MSM::eval
+class IpaMsm {
+public:
+    explicit IpaMsm(const Params& params, void* stream = nullptr) : k_(params.k), stream_(stream) {
+        check(trh_ipa_msm_create(params.ipa_bases().handle(), params.k, (const uint64_t*)&params.u, &m_), "Params::empty_msm");
+    }
+    IpaMsm(const IpaMsm&) = delete;
+    IpaMsm& operator=(const IpaMsm&) = delete;
+    IpaMsm(IpaMsm&& o) noexcept : m_(o.m_), k_(o.k_), stream_(o.stream_) { o.m_ = nullptr; }
+    IpaMsm& operator=(IpaMsm&& o) noexcept { std::swap(m_, o.m_); std::swap(k_, o.k_); std::swap(stream_, o.stream_); return *this; }
+    ~IpaMsm() { if (m_) trh_ipa_msm_destroy(m_); }
+    trh_ipa_msm_t handle() const { return m_; }
+    void append_term(const Limbs& scalar, const Affine& point) { check(trh_ipa_msm_append_term(m_, scalar.data(), (const uint64_t*)&point), "MSM::append_term"); }
+    void add_constant_term(const Limbs& c) { check(trh_ipa_msm_add_constant_term(m_, c.data()), "MSM::add_constant_term"); }
+    void add_to_w_scalar(const Limbs& s) { check(trh_ipa_msm_add_to_w_scalar(m_, s.data()), "MSM::add_to_w_scalar"); }
+    void add_to_u_scalar(const Limbs& s) { check(trh_ipa_msm_add_to_u_scalar(m_, s.data()), "MSM::add_to_u_scalar"); }
+    void add_to_g_scalars(const DeviceBuffer& scalars) {
+        require(scalars.size() >= ((size_t)32 << k_), "scalars.len() == params.n");
+        check(trh_ipa_msm_add_to_g_scalars_dev(m_, scalars.data(), stream_), "MSM::add_to_g_scalars");
+    }
+    // Guard::use_challenges for every guard at once: challenges[p] holds guard p's k round challenges; empty weights = all one
+    void use_challenges(const std::vector<std::vector<Limbs>>& challenges, const std::vector<Limbs>& neg_c, const std::vector<Limbs>& weights = {},
+                        const Limbs* alpha = nullptr) {
+        require(challenges.size() == neg_c.size() && (weights.empty() || weights.size() == neg_c.size()), "one neg_c (and weight) per guard");
+        std::vector<Limbs> u;
+        for (const auto& row : challenges) { require(row.size() == k_, "u.len() == k"); u.insert(u.end(), row.begin(), row.end()); }
+        check(trh_ipa_msm_use_challenges(m_, neg_c.size(), (const uint64_t*)u.data(), (const uint64_t*)neg_c.data(),
+                                         weights.empty() ? nullptr : (const uint64_t*)weights.data(), alpha ? alpha->data() : nullptr, stream_), "Guard::use_challenges");
+    }
+    void scale(const Limbs& factor) { check(trh_ipa_msm_scale(m_, factor.data(), stream_), "MSM::scale"); }
+    void add_msm(const IpaMsm& other) { check(trh_ipa_msm_add_msm(m_, other.m_, stream_), "MSM::add_msm"); }
+    bool eval(Point* point = nullptr) const {
+        int ident = 0;
+        Point p;
+        check(trh_ipa_msm_eval(m_, stream_, &ident, (uint64_t*)&p), "MSM::eval");
+        if (point) *point = p;
+        return ident != 0;
+    }
+private:
+    trh_ipa_msm_t m_ = nullptr;
+    uint32_t k_;
+    void* stream_;
+};
 
 // ---- the remaining polynomial steps of create_proof on resident data -------------------------------------------------
 // arithmetic::eval_polynomial for `batch` coefficient forms (n each, back to back) at one point

@@ -124,6 +124,18 @@ _SIGNATURES = {
     "trh_domain_extended_to_coeff": ([_vp, _vp, ctypes.c_size_t, _vp], ctypes.c_int),
     "trh_domain_divide_by_vanishing_poly": ([_vp, _vp, ctypes.c_size_t, _vp], ctypes.c_int),
     "trh_ipa_create_proof": ([_vp, _u64p, ctypes.c_uint32, _vp, _u64p, _u64p, _vp, _u64p, ctypes.POINTER(Transcript), RNG_FN, _vp, _vp, _u64p, _u64p], ctypes.c_int),
+    "trh_ipa_msm_create": ([_vp, ctypes.c_uint32, _u64p, ctypes.POINTER(_vp)], ctypes.c_int),
+    "trh_ipa_msm_destroy": ([_vp], None),
+    "trh_ipa_msm_append_term": ([_vp, _u64p, _u64p], ctypes.c_int),
+    "trh_ipa_msm_add_constant_term": ([_vp, _u64p], ctypes.c_int),
+    "trh_ipa_msm_add_to_w_scalar": ([_vp, _u64p], ctypes.c_int),
+    "trh_ipa_msm_add_to_u_scalar": ([_vp, _u64p], ctypes.c_int),
+    "trh_ipa_msm_add_to_g_scalars_dev": ([_vp, _vp, _vp], ctypes.c_int),
+    "trh_ipa_msm_use_challenges": ([_vp, ctypes.c_size_t, _u64p, _u64p, _u64p, _u64p, _vp], ctypes.c_int),
+    "trh_ipa_msm_scale": ([_vp, _u64p, _vp], ctypes.c_int),
+    "trh_ipa_msm_add_msm": ([_vp, _vp, _vp], ctypes.c_int),
+    "trh_ipa_msm_eval": ([_vp, _vp, ctypes.POINTER(ctypes.c_int), _u64p], ctypes.c_int),
+    "trh_ipa_msm_g_scalars_dev": ([_vp], _vp),
     "trh_poly_eval_batch_dev": ([ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, _u64p, _vp, _u64p], ctypes.c_int),
     "trh_field_batch_invert_dev": ([ctypes.c_int, _vp, ctypes.c_size_t, _vp], ctypes.c_int),
     "trh_field_batch_invert_mul_dev": ([ctypes.c_int, _vp, _vp, ctypes.c_size_t, _vp], ctypes.c_int),

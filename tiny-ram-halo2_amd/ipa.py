@@ -7,6 +7,9 @@ The transcript (BLAKE2b, on the Rust host) and the prover's randomness are injec
     transcript.write_point(jacobian12), .write_scalar(limbs4), .squeeze_challenge_scalar() -> int (canonical)
     rng() -> int (canonical scalar)
 so the flow can be replayed bit-for-bit against the oracle restatement.
+
+The verifier's side (`poly::commitment::{MSM, Guard}`, verify_proof's arithmetic, BatchVerifier::finalize's fold) follows
+create_proof below: MSM, verify_proof, batch_verify.
 """
 from __future__ import annotations
 
@@ -127,3 +130,154 @@ def create_proof(params, rng, transcript, p_poly, p_blind: int, x3: int, s_poly=
     transcript.write_scalar(_mont(sf, c))
     transcript.write_scalar(_mont(sf, f))
     return c, f
+
+
+# ---------------------------------------------------------------------------------------
+# The verifier's arithmetic: halo2_proofs 0.2.0 poly/commitment/{msm.rs, verifier.rs} (reference call site
+# /root/reference/src/test_utils.rs:52-68).  Transcript reading and challenge squeezing stay with the caller: the functions below
+# take the already-parsed proof.  Scalars are canonical ints, points 8-limb affine PODs (all-zero = identity).
+# ---------------------------------------------------------------------------------------
+class MSM:
+    """poly::commitment::msm::MSM over the opening's resident base set (params.ipa_bases(): g || w, or g || w || u with its
+    fixed-base tables -- no second copy of g goes to the device).  The g scalars stay in device memory (csrc/ipaverify.hip)."""
+
+    def __init__(self, params, stream=None):
+        import ctypes
+        self.params, self.curve, self.k, self.n = params, params.curve, params.k, params.n
+        self.sf = api.SCALAR_FIELD[self.curve]
+        self.stream = stream
+        self.handle = api._vp()
+        u = np.ascontiguousarray(params.u, dtype=np.uint64).reshape(8)
+        api._check(api.lib().trh_ipa_msm_create(params.ipa_bases().handle, params.k, api._p(u), ctypes.byref(self.handle)))
+
+    def _m(self, v):
+        return _mont(self.sf, v)
+
+    def append_term(self, scalar: int, point_xy):
+        api._check(api.lib().trh_ipa_msm_append_term(self.handle, api._p(self._m(scalar)), api._p(api._c(point_xy).reshape(8))))
+
+    def add_constant_term(self, c: int):
+        api._check(api.lib().trh_ipa_msm_add_constant_term(self.handle, api._p(self._m(c))))
+
+    def add_to_w_scalar(self, s: int):
+        api._check(api.lib().trh_ipa_msm_add_to_w_scalar(self.handle, api._p(self._m(s))))
+
+    def add_to_u_scalar(self, s: int):
+        api._check(api.lib().trh_ipa_msm_add_to_u_scalar(self.handle, api._p(self._m(s))))
+
+    def add_to_g_scalars_dev(self, scalars_dev):
+        """scalars_dev: 2^k Montgomery scalars in device memory (torch tensor, DeviceBuffer or pointer)"""
+        api._check(api.lib().trh_ipa_msm_add_to_g_scalars_dev(self.handle, api._devptr(scalars_dev), self.stream))
+
+    def use_challenges(self, challenges, neg_cs, weights=None, alpha=None):
+        """g <- alpha g + sum_p weights[p] neg_cs[p] s(challenges[p]) in one pass (Guard::use_challenges for one guard and no
+        weights / alpha; challenges[p]: the k round challenges of guard p)"""
+        u = np.stack([self._m(v) for row in challenges for v in row])
+        nc = np.stack([self._m(v) for v in neg_cs])
+        assert u.shape[0] == len(neg_cs) * self.k
+        wt = None if weights is None else np.stack([self._m(v) for v in weights])
+        al = None if alpha is None else self._m(alpha)
+        api._check(api.lib().trh_ipa_msm_use_challenges(self.handle, len(neg_cs), api._p(u), api._p(nc), None if wt is None else api._p(wt),
+                                                        None if al is None else api._p(al), self.stream))
+
+    def scale(self, factor: int):
+        api._check(api.lib().trh_ipa_msm_scale(self.handle, api._p(self._m(factor)), self.stream))
+
+    def add_msm(self, other: "MSM"):
+        api._check(api.lib().trh_ipa_msm_add_msm(self.handle, other.handle, self.stream))
+
+    def eval(self):
+        """MSM::eval -> (is_identity, the point as normalised Jacobian (12,) limbs)"""
+        import ctypes
+        flag = ctypes.c_int(0)
+        out = np.zeros(12, dtype=np.uint64)
+        api._check(api.lib().trh_ipa_msm_eval(self.handle, self.stream, ctypes.byref(flag), api._p(out)))
+        return bool(flag.value), out
+
+    def g_scalars(self):
+        """the 2^k g scalars (Montgomery limbs, (n, 4)) or None while the accumulator has no g part"""
+        ptr = api.lib().trh_ipa_msm_g_scalars_dev(self.handle)
+        if not ptr:
+            return None
+        api._check(api.lib().trh_stream_synchronize(self.stream))
+        out = np.empty((self.n, 4), dtype=np.uint64)
+        api._check(api.lib().trh_memcpy_d2h(out.ctypes.data_as(api._vp), api._vp(ptr), out.nbytes))
+        return out
+
+    def destroy(self):
+        if self.handle:
+            api.lib().trh_ipa_msm_destroy(self.handle)
+            self.handle = api._vp()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def compute_b(sf: str, x: int, u) -> int:
+    """poly/commitment/verifier.rs compute_b: prod_j (1 + u_{k-1-j} x^(2^j)), O(k) on the host"""
+    m = _MODULUS[sf]
+    tmp, cur = 1, x % m
+    for u_j in reversed(u):
+        tmp = tmp * (1 + u_j * cur) % m
+        cur = cur * cur % m
+    return tmp
+
+
+class Guard:
+    """poly::commitment::verifier::Guard: the MSM's host-side terms with neg_c and the challenges; use_challenges() makes the MSM"""
+
+    def __init__(self, params, terms, constant: int, w_scalar: int, u_scalar: int, neg_c: int, u):
+        self.params, self.terms, self.constant = params, terms, constant
+        self.w_scalar, self.u_scalar, self.neg_c, self.u = w_scalar, u_scalar, neg_c, list(u)
+
+    def _fill(self, msm: MSM, weight: int = 1):
+        m = _MODULUS[msm.sf]
+        for s, pt in self.terms:
+            msm.append_term(s * weight % m, pt)
+        msm.add_to_w_scalar(self.w_scalar * weight % m)
+        msm.add_to_u_scalar(self.u_scalar * weight % m)
+
+    def use_challenges(self, stream=None) -> MSM:
+        msm = MSM(self.params, stream)
+        self._fill(msm)
+        msm.add_constant_term(self.constant)
+        msm.use_challenges([self.u], [self.neg_c])
+        return msm
+
+
+def verify_proof(params, p_terms, v: int, x3: int, s_commitment, xi: int, z: int, rounds, c: int, f: int) -> Guard:
+    """the arithmetic of poly/commitment/verifier.rs verify_proof on the parsed proof: p_terms = [(scalar, point)] of P (the multiopen
+    verifier's commitments; [(1, P)] for one), v = P(x3), S, xi, z, rounds = [(L_j, R_j, u_j)], c, f.  Returns the guard."""
+    m = _MODULUS[api.SCALAR_FIELD[params.curve]]
+    terms = [(s % m, pt) for s, pt in p_terms] + [(xi % m, s_commitment)]
+    for l_j, r_j, u_j in rounds:
+        terms += [(pow(u_j, -1, m), l_j), (u_j % m, r_j)]
+    u = [u_j for _, _, u_j in rounds]
+    neg_c = -c % m
+    b = compute_b(api.SCALAR_FIELD[params.curve], x3, u)
+    return Guard(params, terms, -v % m, -f % m, neg_c * b % m * z % m, neg_c, u)
+
+
+def batch_msm(params, guards, weights, stream=None) -> MSM:
+    """sum_p weights[p] guards[p].use_challenges() as ONE accumulator: the guards' g parts in one pass over the 2^k vector.
+    BatchVerifier::finalize folds acc = r_p acc + msm_p, i.e. weights[p] = prod_{q > p} r_q."""
+    m = _MODULUS[api.SCALAR_FIELD[params.curve]]
+    acc = MSM(params, stream)
+    const = 0
+    for g, w in zip(guards, weights):
+        g._fill(acc, w)
+        const = (const + g.constant * w) % m
+    acc.add_constant_term(const)
+    acc.use_challenges([g.u for g in guards], [g.neg_c for g in guards], weights=list(weights))
+    return acc
+
+
+def batch_verify(params, guards, weights, stream=None) -> bool:
+    """the arithmetic of BatchVerifier::finalize: the weighted sum of the guards' MSMs is the identity"""
+    acc = batch_msm(params, guards, weights, stream)
+    ok, _ = acc.eval()
+    acc.destroy()
+    return ok
