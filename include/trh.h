@@ -156,7 +156,8 @@ void trh_bases_destroy(trh_bases_t b);
 int trh_bases_precompute(trh_bases_t b, int window_bits);   /* must not run while an MSM over `b` is in flight on another context; the same holds for trh_bases_destroy */
 int trh_bases_precomputed_window_bits(trh_bases_t b); /* 0 when no table is attached */
 /* sizes the calling context's MSM scratch for batches of `batch` MSMs (commitments) over the first n bases of the set, without running one:
- * setup-time, so that the first commitment batch of a process allocates nothing (see trh_domain_reserve) */
+ * setup-time, so that the first commitment batch of a process allocates nothing (see trh_domain_reserve).  A lone MSM beyond 2^25 pairs runs as
+ * range tiles: the scratch of one tile is reserved */
 int trh_bases_reserve(trh_bases_t b, size_t n, size_t batch);
 
 /* MSM over bases[offset .. offset+n) with host scalars (Params::commit / commit_lagrange) */
@@ -458,7 +459,12 @@ int trh_stream_synchronize(void* stream);
  * "msm_bin_sorted_windows": of the last MSM's last chunk of items, the (item, window) bucket sets whose level-1 bins all fit the LDS
  * bin sort (0 when that MSM did not use it; synchronises the device, for tests);
  * "msm_small_launches": MSMs that ran as ONE launch (up to 8448 pairs, batches of up to four); "ipa_generator_collapses": openings that
- * collapsed their generators from the fixed-base table (option ipa_fold). */
+ * collapsed their generators from the fixed-base table (option ipa_fold);
+ * "msm_host_ranges": the ranges the last MSM with host scalars (trh_best_multiexp_*, trh_msm) on this context was cut into -- host bases: one up
+ * to 2^21 pairs, equal ranges of about 2^20 above; resident bases: one up to 3 * 2^21 pairs, then 2^21, 2^22 and the rest;
+ * "msm_range_tiles": the tiles of the last MSM enqueue on this context that ran as range tiles of at most 2^25 pairs (0 when it did not);
+ * "ntt_tableless_passes": of the last transform, the passes after the first that had no inter-pass twiddle table and computed their twiddles
+ * per element (1 from 2^26 elements, where the last pass's table would exceed 1.125 GiB; 0 below). */
 int trh_stat(const char* name, uint64_t* value);
 /* GPU-side timing without HIP headers: events recorded on a stream between the steps (a hipEvent_t each), read afterwards.
  * trh_event_elapsed_ms waits for `end` and returns the device time between the two records. */

@@ -80,31 +80,81 @@ def test_dropin_replay_k10_matches_oracle(level):
         assert res["mode"] == "dropin-batched-blocks"
 
 
-@pytest.mark.parametrize("curve", ["pallas", "vesta"])
-def test_host_msm_tiles_vs_oracle(curve, monkeypatch):
-    """trh_best_multiexp_* (host scalars AND host bases) and trh_msm (resident bases, host scalars) cut into ranges -- forced small
-    here so that several tiles, a ragged last one and the double-buffered uploads are exercised -- against cpu_ref.best_multiexp
-    with unstructured bases"""
-    n = (1 << 16) + 13
-    sc = synth.field_elements(0x51, n)
-    bases = cpu_ref.gen_bases_hashed(curve, 11, n)
-    want = cpu_ref.to_affine(curve, cpu_ref.best_multiexp(curve, sc, bases, threads=8))
+# the sizes at which msm_host_tiled (csrc/capi.hip; boundaries in csrc/hostplan.h) changes the number of ranges
+HOST_SPLIT = 1 << 21          # host bases: one range up to here, equal ranges of about 2^20 pairs above
+RES_SPLIT = 3 << 21           # resident bases: one range up to here; above: 2^21, 2^22, the rest
+RES_OFFSET = 1000
+ORACLE_THREADS = min(cpu_ref.hardware_threads(), 16)
+
+
+@pytest.fixture(scope="module", params=["pallas", "vesta"])
+def split_set(request):
+    """one unstructured base set per curve, long enough for every case below (3 * 2^21 + 5 pairs at offset 1000), and its scalars"""
+    curve = request.param
+    total = RES_SPLIT + 5 + RES_OFFSET
+    bases = cpu_ref.gen_bases_hashed(curve, 0x2B5E + len(curve), total, ORACLE_THREADS)
+    sc = synth.field_elements(0x5C51 + len(curve), total)
+    return curve, sc, bases
+
+
+def test_host_msm_tiles_vs_oracle(split_set):
+    """trh_best_multiexp_* (host scalars AND host bases) and trh_msm (resident bases, host scalars) are cut into ranges whose uploads run
+    under the range before them, the range points added on the host.  Sizes on both sides of the true thresholds, each against
+    cpu_ref.best_multiexp with unstructured bases, and each with the number of ranges the call must have used (trh_stat
+    "msm_host_ranges"; the boundaries themselves are checked without a GPU by tests/native/hostplan_test.cpp):
+      host bases      2^21 -> 1 range, 2^21 + 1 -> 3, 2^21 + 2^20 + 13 -> 4 (three of 786436 pairs and a ragged 786433)
+      resident bases  3 * 2^21 -> 1 range, 3 * 2^21 + 5 -> 3 (2^21, 2^22 and FIVE pairs: a one-launch msm_small_kernel MSM queued behind a
+                      4-million-pair one on the other upload slot), the same at offset 1000 into the set.
+    Option bases_cache: off by default; were it switched on through the environment, the counts would still hold -- a (pointer, length,
+    content) triple only becomes a resident set at its SECOND sighting, and no triple is passed twice here -- so the host-bases calls
+    below are msm_host_tiled calls either way.
+    A fixed-base table cannot reach the split: tables need W * n <= 2^24 (about 2^20 pairs), so trh_bases_precompute refuses this set
+    and the MSM after the refused call is the untabled one, range for range."""
+    curve, sc, bases = split_set
+
+    def oracle(lo, n):
+        return cpu_ref.to_affine(curve, cpu_ref.best_multiexp(curve, sc[:n], bases[lo:lo + n], threads=ORACLE_THREADS))
+
+    # host scalars and host bases
+    for n, ranges in ((HOST_SPLIT, 1), (HOST_SPLIT + 1, 3), (HOST_SPLIT + (1 << 20) + 13, 4)):
+        got = api.best_multiexp(curve, sc[:n], bases[:n])
+        assert api.stat("msm_host_ranges") == ranges, ("best_multiexp", n)
+        assert (got[:8] == oracle(0, n)).all(), ("best_multiexp", n)
+    # resident bases, host scalars
     res = api.Bases.from_host(curve, bases)
-    for tile_log in (None, 14, 12):
-        if tile_log is None:
-            monkeypatch.delenv("TRH_HOST_TILE_LOG", raising=False)
-        else:
-            monkeypatch.setenv("TRH_HOST_TILE_LOG", str(tile_log))
-        assert (api.best_multiexp(curve, sc, bases)[:8] == want).all(), ("best_multiexp", tile_log)
-        assert (res.msm(sc)[:8] == want).all(), ("msm", tile_log)
-        off, ln = 1000, (1 << 15) + 7  # a sub-range of the resident set, tiled
-        w2 = cpu_ref.to_affine(curve, cpu_ref.best_multiexp(curve, sc[:ln], bases[off:off + ln], threads=8))
-        assert (res.msm(sc[:ln], offset=off)[:8] == w2).all(), ("msm offset", tile_log)
-    monkeypatch.delenv("TRH_HOST_TILE_LOG", raising=False)
+    small = api.stat("msm_small_launches")
+    got = res.msm(sc[:RES_SPLIT])
+    assert api.stat("msm_host_ranges") == 1 and api.stat("msm_small_launches") == small
+    assert (got[:8] == oracle(0, RES_SPLIT)).all(), "msm 3 * 2^21"
+    n = RES_SPLIT + 5
+    want = oracle(0, n)
+    got = res.msm(sc[:n])
+    assert api.stat("msm_host_ranges") == 3 and api.stat("msm_small_launches") == small + 1   # the 5-pair range ran as one launch
+    assert (got[:8] == want).all(), "msm 3 * 2^21 + 5"
+    got = res.msm(sc[:n], offset=RES_OFFSET)
+    assert api.stat("msm_host_ranges") == 3 and api.stat("msm_small_launches") == small + 2
+    assert (got[:8] == oracle(RES_OFFSET, n)).all(), "msm 3 * 2^21 + 5, offset"
+    # Bases.precompute(0) over a set of this length is refused (the table would hold W * n > 2^24 entries); what follows is the untabled MSM
+    with pytest.raises(api.TrhError, match="fixed-base range"):
+        res.precompute(0)
+    big = api.Bases.from_host(curve, bases[:n])   # offset 0 and the whole set: the shape that would take a table if there were one
+    with pytest.raises(api.TrhError, match="fixed-base range"):
+        big.precompute(0)
+    got = big.msm(sc[:n])
+    assert api.stat("msm_host_ranges") == 3
+    assert (got[:8] == want).all(), "msm 3 * 2^21 + 5 after precompute"
+    big.destroy()
+    # a sub-range of the resident set below the threshold: one range
+    off, ln = RES_OFFSET, (1 << 15) + 7
+    got = res.msm(sc[:ln], offset=off)
+    assert api.stat("msm_host_ranges") == 1
+    assert (got[:8] == oracle(off, ln)).all(), "msm offset"
+    res.destroy()
     # degenerate sizes through the same path
     ident = np.zeros(8, dtype=np.uint64)
     assert (api.best_multiexp(curve, sc[:0], bases[:0])[:8] == ident).all()
     assert (api.best_multiexp(curve, sc[:1], bases[:1])[:8] == cpu_ref.to_affine(curve, cpu_ref.best_multiexp(curve, sc[:1], bases[:1], threads=1))).all()
+    assert api.stat("msm_host_ranges") == 1
 
 
 @pytest.mark.parametrize("field,log_n,count", [("fp", 12, 37), ("fq", 16, 9), ("fp", 20, 5)])
@@ -204,7 +254,6 @@ def test_busy_context_is_reported_and_recovers():
         b.msm(sc)
     got = b.msm_dev_finish()
     assert (b.msm(sc) == got).all()
-    os.environ.pop("TRH_HOST_TILE_LOG", None)
 
 
 def test_device_block_pool_reuses_and_isolates():

@@ -293,14 +293,137 @@ def test_ntt_golden(field):
 
 
 @pytest.mark.parametrize("field", FIELDS)
-@pytest.mark.parametrize("log_n", [1, 2, 5, 9, 11, 12, 13, 16, 18, 19, 20])
+@pytest.mark.parametrize("log_n", [1, 2, 5, 9, 11, 12, 13, 16, 18, 19, 20, 21, 23, 24, 25, 26])
 def test_ntt_vs_cpu_ref(field, log_n):
     f = o.FIELDS[field]
     a = synth.field_elements(0x4E5454 + log_n, 1 << log_n)
     w = np.array(f.limbs(f.omega(log_n)), np.uint64)
     got = api.best_fft(field, a, w, log_n)
+    assert api.stat("ntt_tableless_passes") == (1 if log_n >= 26 else 0)
     want = cpu_ref.best_fft(field, a, w, log_n, threads=8)
     assert (got == want).all()
+
+
+# ---- the sizes whose pass plans are shapes of their own (csrc/hostplan.h ntt_plan_passes, checked by tests/native/hostplan_test.cpp):
+#      25 = 9 + 8 + 8, 26 = 9 + 9 + 8, 27 = 9 + 9 + 9 -- three passes with nine-stage ones among them; from 2^26 the last pass's
+#      inter-pass table (36 B << log_n) is above the 1.125 GiB cap and the pass computes its twiddles per element; at 2^27 the tile
+#      count no longer fits the batch-major grid.  trh_stat "ntt_tableless_passes" says which branch a transform took.
+ORACLE_THREADS = min(cpu_ref.hardware_threads(), 16)
+
+
+def _lim(f, v):
+    return np.array(f.limbs(v % f.m), np.uint64)
+
+
+@pytest.mark.parametrize("field,log_n", [("fp", 26), ("fq", 26), ("fp", 27)])
+def test_ntt_large_device_and_host_entries_vs_cpu_ref(field, log_n):
+    """2^26 (the largest size the project quotes) and 2^27 (the largest it accepts): the forward transform on a device buffer against
+    the oracle's best_fft, the inverse transform and n^-1 back to the input, and the host-pointer entry to the same words"""
+    f = o.FIELDS[field]
+    n = 1 << log_n
+    w = f.omega(log_n)
+    a = synth.field_elements(0x4E54A0 + 2 * log_n + (field == "fq"), n)
+    small = synth.field_elements(0x4E54A1, 1 << 12)
+    d = api.DeviceBuffer.from_host(small)
+    api.ntt_dev(field, d, 12, _lim(f, f.omega(12)))
+    assert api.stat("ntt_tableless_passes") == 0
+    d.free()
+    d = api.DeviceBuffer.from_host(a)
+    api.ntt_dev(field, d, log_n, _lim(f, w))
+    assert api.stat("ntt_tableless_passes") == 1
+    fwd = d.to_host(shape=(-1, 4))
+    want = cpu_ref.best_fft(field, a, _lim(f, w), log_n, threads=ORACLE_THREADS)
+    assert (fwd == want).all()
+    del want
+    api.ntt_dev(field, d, log_n, _lim(f, f.inv(w)))
+    assert api.stat("ntt_tableless_passes") == 1
+    api.field_scale_dev(field, d, n, _lim(f, f.inv(n)))
+    api.lib().trh_stream_synchronize(None)
+    back = d.to_host(shape=(-1, 4))
+    d.free()
+    assert (back == a).all()
+    del back
+    api.best_fft_inplace(field, a, _lim(f, w), log_n)
+    assert api.stat("ntt_tableless_passes") == 1
+    assert (a == fwd).all()
+
+
+@pytest.mark.parametrize("field,log_n", [("fp", 18), ("fq", 25), ("fp", 26), ("fq", 27)])
+def test_ntt_closed_form_inputs(field, log_n):
+    """inputs whose transform is known without best_fft, through the nine-stage passes (18 = 9 + 9 and the three-pass plans):
+      * a = delta_j (j = 1 and one odd j above n / 2): output i is omega^(i j).  The powers omega^i are built with the oracle's field
+        multiplication by doubling spans; row i of the j-th table is entry (i j mod n) of that one.
+      * every element p - 1: n (p - 1) at index 0, zero elsewhere;  p - 1 at the even indices and 0 at the odd ones: (n / 2)(p - 1) at
+        index 0 and at index n / 2, zero elsewhere;  0 at the even indices and p - 1 at the odd ones: (n / 2)(p - 1) at index 0, its
+        negative at n / 2.  These are the inputs of maximal magnitude for the unreduced nine-limb butterflies: the bound argued in ntt.hip
+        ("Limb growth and where the butterflies normalise") is for operands as large as they can be, and random inputs never are."""
+    f = o.FIELDS[field]
+    n = 1 << log_n
+    w = f.omega(log_n)
+    wl = _lim(f, w)
+    tableless = 1 if log_n >= 26 else 0
+
+    def transform(a):
+        d = api.DeviceBuffer.from_host(a)
+        api.ntt_dev(field, d, log_n, wl)
+        assert api.stat("ntt_tableless_passes") == tableless
+        out = d.to_host(shape=(-1, 4))
+        d.free()
+        return out
+
+    def expect_sparse(got, entries):
+        idx = np.flatnonzero(got.any(axis=1))
+        want_idx = sorted(i for i, v in entries.items() if v % f.m)
+        assert idx.tolist() == want_idx
+        for i in want_idx:
+            assert (got[i] == _lim(f, entries[i])).all(), i
+
+    top = f.m - 1
+    a = np.tile(_lim(f, top), (n, 1))
+    expect_sparse(transform(a), {0: n * top})
+    a[1::2] = 0
+    expect_sparse(transform(a), {0: (n // 2) * top, n // 2: (n // 2) * top})
+    a[1::2] = _lim(f, top)
+    a[0::2] = 0
+    expect_sparse(transform(a), {0: (n // 2) * top, n // 2: -(n // 2) * top})
+    # powers of omega by doubling spans: pw[i + span] = pw[i] * omega^span
+    pw = np.empty((n, 4), np.uint64)
+    pw[0] = _lim(f, 1)
+    span, cur = 1, w
+    while span < n:
+        pw[span:2 * span] = cpu_ref.field_op(field, "mul", pw[:span], np.tile(_lim(f, cur), (span, 1)))
+        cur, span = cur * cur % f.m, span * 2
+    assert (pw[n - 1] == _lim(f, f.inv(w))).all() and (pw[n // 2] == _lim(f, top)).all()
+    a[:] = 0
+    a[1] = _lim(f, 1)
+    assert (transform(a) == pw).all()
+    j = n // 2 + 0x2B5 * 2 + 1
+    a[1] = 0
+    a[j] = _lim(f, 1)
+    got = transform(a)
+    del a
+    step = 1 << 22   # the gather pw[(i j) mod n] in slices, so that no second table is held
+    for i0 in range(0, n, step):
+        i = np.arange(i0, min(i0 + step, n), dtype=np.uint64)
+        assert (got[i0:i0 + i.shape[0]] == pw[(i * np.uint64(j)) & np.uint64(n - 1)]).all(), i0
+
+
+@pytest.mark.parametrize("field,log_n,batch,chunk", [("fp", 22, 9, 7), ("fq", 24, 3, 1)])
+def test_ntt_batch_in_several_chunks(field, log_n, batch, chunk):
+    """a batch beyond the 2 GiB raw scratch runs in chunks of 2 GiB / (72 B x 2^log_n) transforms: 9 at 2^22 as 7 + 2 (a second chunk at a
+    non-zero offset, ragged), 3 at 2^24 one by one.  Distinct random columns, every one against the oracle"""
+    f = o.FIELDS[field]
+    n = 1 << log_n
+    assert (2 << 30) // (n * 72) == chunk and batch > chunk
+    w = _lim(f, f.omega(log_n))
+    a = synth.field_elements(0xBA7C6 + log_n, n * batch).reshape(batch, n, 4)
+    d = api.DeviceBuffer.from_host(a)
+    api.ntt_dev(field, d, log_n, w, batch=batch)
+    assert api.stat("ntt_tableless_passes") == 0
+    got = d.to_host(shape=(batch, n, 4))
+    d.free()
+    for k in range(batch):
+        assert (got[k] == cpu_ref.best_fft(field, a[k], w, log_n, threads=ORACLE_THREADS)).all(), k
 
 
 def test_ntt_2_22_roundtrip_and_spot_values():

@@ -262,6 +262,66 @@ def test_msm_2_24_unstructured_bases_vs_best_multiexp():
     assert (api.best_multiexp(curve, sc, bases)[:8] == want).all()
 
 
+def test_msm_2_25_plus_3_range_tiles_host_ranges_and_reserve():
+    """pair sets beyond every size threshold of the MSM drivers: Pallas, random 254-bit scalars, unstructured bases, limb-for-limb against
+    the oracle's best_multiexp, each entry with the branch it must have taken (trh_stat):
+      * trh_bases_reserve(n, 1) on a FRESH handle, before any MSM over it: an untabled lone MSM above 2^25 pairs runs as range tiles
+        (msm.hip MSM_TILE) and the reservation sizes the scratch of one tile.  (Before this test existed the tile loop finished a
+        reserve-only enqueue that had queued nothing and the call answered TRH_EINVAL, "msm_finish: no matching MSM enqueued on this
+        context and stream".)
+      * device scalars, 2^25 + 3 pairs: two range tiles of 16777218 + 16777217 pairs;
+      * host scalars over the resident set, 3 * 2^21 + 2^25 + 3 pairs: three host ranges 2^21, 2^22 and 2^25 + 3 pairs -- the third is
+        itself above 2^25 and is split into the same two tiles INSIDE the host pipeline (the tile loop's blocking finishes between
+        msm_host_tiled's enqueue and finish, that range's upload on the other slot).  With 2^25 + 3 host scalars the third range has
+        27262979 pairs, BELOW the tile size: three host ranges, no tiles -- asserted too, so that the two sizes cannot be confused;
+    then reservations of a small shape (4098 pairs, batch 2: the one-launch kernel's buffers) and a mid one (2^20, batch 1) on fresh
+    handles, each followed by the MSMs it was made for"""
+    curve, n1 = "pallas", (1 << 25) + 3
+    n2 = (3 << 21) + n1
+    threads = min(cpu_ref.hardware_threads(), 16)
+    sc = synth.field_elements(0x5CA125, n2)
+    bases = cpu_ref.gen_bases_hashed(curve, 0xBA5E25, n2, threads)
+    jac1 = cpu_ref.best_multiexp(curve, sc[:n1], bases[:n1], threads=threads)
+    want1 = cpu_ref.to_affine(curve, jac1)
+    # (the oracle's sum over all n2 pairs: its sum over the first n1 plus its sum over the rest, added with its own group law)
+    want2 = cpu_ref.to_affine(curve, cpu_ref.point_op(curve, "add", jac1, cpu_ref.best_multiexp(curve, sc[n1:], bases[n1:], threads=threads)))
+    assert want1.any() and want2.any() and (want1 != want2).any()
+    b = api.Bases.from_host(curve, bases)
+    b.reserve(n2, 1)
+    got = b.msm_dev(to_dev(sc[:n1]), n1)
+    assert api.stat("msm_range_tiles") == 2
+    assert (got[:8] == want1).all(), "msm_dev"
+    got = b.msm(sc)
+    assert api.stat("msm_host_ranges") == 3 and api.stat("msm_range_tiles") == 2
+    assert (got[:8] == want2).all(), "msm (host scalars), tiles inside the third range"
+    got = b.msm(sc[:n1])
+    assert api.stat("msm_host_ranges") == 3 and api.stat("msm_range_tiles") == 0
+    assert (got[:8] == want1).all(), "msm (host scalars)"
+    # a later MSM below the tile size leaves the tile branch alone
+    m = 1 << 20
+    w20 = cpu_ref.to_affine(curve, cpu_ref.best_multiexp(curve, sc[:m], bases[:m], threads=threads))
+    assert (b.msm_dev(to_dev(sc[:m]), m)[:8] == w20).all() and api.stat("msm_range_tiles") == 0
+    b.destroy()
+    # mid shape: reserve, then the MSM it sized
+    b = api.Bases.from_host(curve, bases[:m])
+    b.reserve(m, 1)
+    assert (b.msm_dev(to_dev(sc[:m]), m)[:8] == w20).all() and api.stat("msm_range_tiles") == 0
+    assert (b.msm(sc[:m])[:8] == w20).all() and api.stat("msm_host_ranges") == 1
+    b.destroy()
+    # small shape, batch 2 (one msm_small_kernel launch for both rows)
+    k = 4098
+    b = api.Bases.from_host(curve, bases[:k])
+    b.reserve(k, 2)
+    small = api.stat("msm_small_launches")
+    rows = np.ascontiguousarray(np.stack([sc[:k], sc[k:2 * k]]))
+    got2 = b.msm_batch_dev(to_dev(rows), k, 2)
+    assert api.stat("msm_small_launches") == small + 1
+    for i in range(2):
+        assert (got2[i][:8] == cpu_ref.to_affine(curve, cpu_ref.best_multiexp(curve, rows[i], bases[:k], threads=threads))).all(), i
+    assert (b.msm(rows[0])[:8] == got2[0][:8]).all()
+    b.destroy()
+
+
 def test_msm_2_26_as_8_logical_shards():
     """BASELINE config 5's decomposition on the one GPU of the test box: a device group of 8 contexts on device 0, the 2^26 bases
     range-sharded 8 x 2^23 by trh_bases_generate, device-resident scalars handed to the shards, 8 local Pippengers, the 8 partial

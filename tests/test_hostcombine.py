@@ -79,6 +79,19 @@ def test_device_block_pool_index():
         assert r.returncode == 0 and "devpool: ok" in r.stdout, r.stdout + r.stderr
 
 
+def test_host_range_cuts_and_ntt_pass_plan():
+    """csrc/hostplan.h, the host-side shape decisions of the two headline operations: the range boundaries of an MSM with host scalars
+    (both modes, sizes on and around the 2^21 and 3 * 2^21 thresholds, a ragged last range, 2^31 - 1) and the NTT's pass plan for
+    log_n = 1 .. 27; built with address + undefined sanitizers.  The GPU tests assert the same range counts through trh_stat"""
+    src = os.path.join(ROOT, "tests", "native", "hostplan_test.cpp")
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "hostplan_test")
+        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", exe])
+        r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0 and "hostplan: ok" in r.stdout, r.stdout + r.stderr
+        assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr
+
+
 def test_copy_pool_under_thread_sanitizer():
     """the host threads of the host-pointer staging path (csrc/copypool.h: spin-then-sleep workers handed slices through a generation
     counter): two callers sharing one pool and a third on another, byte-exact copies, no report from -fsanitize=thread; then the same

@@ -572,6 +572,10 @@ class Bases:
         _check(lib().trh_bases_precompute(self.handle, window_bits))
         return int(lib().trh_bases_precomputed_window_bits(self.handle))
 
+    def reserve(self, n: int, batch: int = 1) -> None:
+        """trh_bases_reserve: sizes the calling context's MSM scratch for batches of `batch` MSMs over the first n bases, without running one"""
+        _check(lib().trh_bases_reserve(self.handle, n, batch))
+
     def download(self, offset: int = 0, n: int | None = None) -> np.ndarray:
         n = len(self) - offset if n is None else n
         out = np.empty((n, 8), dtype=np.uint64)

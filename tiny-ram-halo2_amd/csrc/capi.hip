@@ -12,6 +12,7 @@
 #include <thread>
 
 #include "ctx.h"
+#include "hostplan.h"
 #include "hosthelper.h"
 #include "curve_q4.h"
 #include "devpool.h"
@@ -414,19 +415,9 @@ int msm_host_tiled(int curve, const uint64_t* coeffs, const uint64_t* bases_host
     TRH_TRY(stage_begin(c));
     StageScope scope(c);
     Stage& st = c.stage;
-    // range boundaries
-    std::vector<size_t> cut(1, 0);
-    if (bases_host && n > ((size_t)1 << 21)) {  // equal ranges
-        const size_t want = (size_t)1 << 20, nt = (n + want - 1) / want, len = (n + nt - 1) / nt;
-        for (size_t o = len; o < n; o += len) cut.push_back(o);
-    } else if (!bases_host && n > ((size_t)3 << 21)) {
-        // growing ranges: 2^21, 2^22, then the rest -- the first upload is short, every later one hides under the range before it
-        // (32 B per pair cross the link ~2x faster than they are multiplied), and most pairs run as one large MSM at the full rate
-        cut.push_back((size_t)1 << 21);
-        cut.push_back((size_t)3 << 21);
-    }
-    cut.push_back(n);
+    const std::vector<size_t> cut = hostplan::msm_host_cuts(bases_host != nullptr, n);  // range boundaries (hostplan.h)
     const size_t ntiles = cut.size() - 1;
+    c.msm.host_ranges = ntiles;
     uint64_t acc[24];
     memset(acc, 0, sizeof(acc));
     // option trace, bit 0: where the call's time goes (microseconds since here, stderr)
@@ -458,8 +449,8 @@ int msm_host_tiled(int curve, const uint64_t* coeffs, const uint64_t* bases_host
         TRH_HIP_TRY(hipStreamWaitEvent(st.cs, st.ev_up[slot], 0));
         const void* bdev = bases_host ? st.ring_out[slot].p : (const void*)((const char*)res->d_xy + (offset + off) * 64);
         const void* bz = bases_host ? nullptr : lazy_bases(res, offset + off, st.cs);
-        // the fixed-base table covers whole sets of at most 2^24 / W pairs, which never split on their own (the growing ranges start above
-        // 3 * 2^21 pairs); only a forced range length (TRH_HOST_TILE_LOG, a test switch) sends a tabled set down the per-window path
+        // the fixed-base table covers whole sets of at most 2^24 / W pairs (W >= 15: about 2^20), which never split: the growing ranges start
+        // above 3 * 2^21 pairs.  A call that does split therefore never finds a table, and every range takes the per-window path
         const MsmFixedBase* fb = (!bases_host && ntiles == 1) ? fixed_base(res, offset, n) : nullptr;
         TRH_TRY(msm_enqueue(curve, bdev, bz, st.ring_in[slot].p, cur, 1, cur, mont, st.cs, fb));
         tr_mark("MSM enqueued");
@@ -1316,6 +1307,9 @@ int trh_stat(const char* name, uint64_t* value) {
     TRH_ENTER(0);
     if (strcmp(name, "msm_lean_retries") == 0) { *value = ctx().msm.lean_retries; return TRH_OK; }
     if (strcmp(name, "msm_small_launches") == 0) { *value = ctx().msm.small_launches; return TRH_OK; }
+    if (strcmp(name, "msm_host_ranges") == 0) { *value = ctx().msm.host_ranges; return TRH_OK; }
+    if (strcmp(name, "msm_range_tiles") == 0) { *value = ctx().msm.range_tiles; return TRH_OK; }
+    if (strcmp(name, "ntt_tableless_passes") == 0) { *value = ctx().ntt_tableless_passes; return TRH_OK; }
     if (strcmp(name, "msm_bin_sorted_windows") == 0) {  // synchronises the device: tests only
         const MsmScratch& m = ctx().msm;
         *value = 0;

@@ -152,6 +152,8 @@ struct MsmScratch {
     // an MSM beyond MSM_TILE pairs runs as range tiles: the sum of the finished tiles (normalised Jacobian), added by msm_finish
     bool tile_sum_valid = false, in_tile = false;
     u64 tile_sum[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    u64 range_tiles = 0;  // tiles of the last MSM enqueue that ran as range tiles, 0 if it did not (tests: the branch was taken)
+    u64 host_ranges = 0;  // ranges of the last MSM with host scalars (msm_host_tiled in capi.hip; tests)
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool ev_valid = false;
 };
@@ -191,6 +193,7 @@ struct Ctx {
     trh_timing_t last{};
     MsmScratch msm;
     DevBuf ntt_tmp;
+    u64 ntt_tableless_passes = 0;  // of the last transform: lazy passes p >= 1 that had no inter-pass table and computed their twiddles per element (tests)
     DevBuf io;  // staging for host-pointer NTT entry points
     Stage stage;
     DevBuf pfft;  // curve-point FFT work array + twiddle scalars

@@ -1507,9 +1507,17 @@ int msm_enqueue_t(const void* bases_dev, const void* bases_z, const void* scalar
     MsmLane& L = m.lane;
     if (fb && (n == 0 || !msm_fixed_base_fits(n, fb->c))) fb = nullptr;
     if (!m.in_tile) m.tile_sum_valid = false;
+    if (!m.in_tile && !m.reserve_only) m.range_tiles = 0;
     m.sort_flags = nullptr; m.sort_flag_count = 0;
     if (!fb && batch == 1 && n > MSM_TILE && !m.in_tile && c.window_override == 0) {
         const size_t tiles = (n + MSM_TILE - 1) / MSM_TILE, len = (n + tiles - 1) / tiles;
+        if (m.reserve_only) {  // trh_bases_reserve: the scratch of the longest tile (the first) is what every tile of this MSM needs; nothing to finish
+            m.in_tile = true;
+            const int rc = msm_enqueue_t<SF, BF>(bases_dev, bases_z, scalars_dev, len, 1, len, mont, s, nullptr, nullptr);
+            m.in_tile = false;
+            return rc;
+        }
+        m.range_tiles = tiles;
         u64 acc[24];
         memset(acc, 0, sizeof(acc));
         m.in_tile = true;

@@ -20,15 +20,16 @@
 #include <string.h>
 
 #include "ctx.h"
+#include "hostplan.h"
 
 namespace trh {
 
 namespace {
 
-constexpr int TILE_LOG = 11;
+constexpr int TILE_LOG = hostplan::NTT_TILE_LOG;
 constexpr int TILE = 1 << TILE_LOG;
 constexpr int NTT_THREADS = TILE / 4;
-constexpr int MAX_PASS_LOG = 9;
+constexpr int MAX_PASS_LOG = hostplan::NTT_MAX_PASS_LOG;
 
 struct alignas(16) Half {  // 16 bytes of a field element
     u32 w[4];
@@ -620,21 +621,8 @@ TwiddleEntry* find_tables(int field, int log_n, const u64 omega[4], const u64* s
     return nullptr;
 }
 
-// pass plan: log_n split into passes of <= MAX_PASS_LOG stages on 2^tlog-element tiles
-void plan_passes(int log_n, int* sizes, int* n_passes, int* tile_log) {
-    // (a 4096-element tile -- two passes for 2^19..2^22, all 160 KiB of LDS, one workgroup per CU -- measured equal: removed.  Round 6: 2^22 as
-    //  two 11-stage passes on the 2048-element tile, pass 0 reading 64-KiB-strided columns: 0.83 ms against 0.47 for 8 + 7 + 7, the fabric
-    //  fetches 4.8 x the bytes -- profiles/r06_ntt_11_11_ab.txt.)
-    int P = 0, tlog = TILE_LOG;
-    if (log_n <= TILE_LOG) { sizes[P++] = log_n; }
-    else {
-        P = (log_n + MAX_PASS_LOG - 1) / MAX_PASS_LOG;
-        if (P < 2) P = 2;
-        int rem = log_n;
-        for (int p = 0; p < P; ++p) { sizes[p] = (rem + (P - p) - 1) / (P - p); rem -= sizes[p]; }
-    }
-    *n_passes = P; *tile_log = tlog;
-}
+// pass plan: log_n split into passes of <= MAX_PASS_LOG stages on 2^tlog-element tiles (hostplan.h)
+void plan_passes(int log_n, int* sizes, int* n_passes, int* tile_log) { hostplan::ntt_plan_passes(log_n, sizes, n_passes, tile_log); }
 template <class F>
 int build_tables(int log_n, const u64 omega[4], const u64* scale, hipStream_t s, TwiddleEntry** out) {
     Ctx& c = ctx();
@@ -709,6 +697,7 @@ template <class F>
 int ntt_device_t(void* a_dev, uint32_t log_n, const u64 omega[4], size_t batch, hipStream_t s, const NttFusion* fu, const u64* scale) {
     if (log_n == 0 || batch == 0) return TRH_OK;
     Ctx& c = ctx();
+    c.ntt_tableless_passes = 0;
     TwiddleEntry* t = find_tables(F::ID, (int)log_n, omega, scale);
     if (!t) TRH_TRY(build_tables<F>((int)log_n, omega, scale, s, &t));
 
@@ -728,6 +717,7 @@ int ntt_device_t(void* a_dev, uint32_t log_n, const u64 omega[4], size_t batch, 
         if (chunk > batch) chunk = batch;
         TRH_TRY(c.ntt_tmp.ensure(2 * chunk * N * 36));
         char* raw[2] = {(char*)c.ntt_tmp.p, (char*)c.ntt_tmp.p + chunk * N * 36};
+        for (int p = 1; p < P; ++p) c.ntt_tableless_passes += t->direct[p].p == nullptr;
         for (size_t b0 = 0; b0 < batch; b0 += chunk) {
             const size_t nb = (b0 + chunk <= batch) ? chunk : batch - b0;
             uint4* base = a + b0 * N * 2;
