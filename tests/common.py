@@ -226,6 +226,57 @@ def expr_to_tuple(e):
     return ("scaled", expr_to_tuple(e.e), e.value)
 
 
+# ---- stored words that random data never produces: synth.field_elements masks every row below 2^254 and both moduli are 2^254 + t
+#      (t < 2^126), so the stored forms in [2^254, m) and the values next to 0, m and R appear in a bulk input only when put there ------
+def stored_ints(a) -> list:
+    """(n, 4) uint64 stored forms -> n Python ints (the stored 256-bit words themselves, no Montgomery conversion)"""
+    buf = np.ascontiguousarray(a, dtype="<u8").tobytes()
+    return [int.from_bytes(buf[i:i + 32], "little") for i in range(0, len(buf), 32)]
+
+
+def edge_residue_ints(field: str) -> list:
+    import pasta as o
+    f = o.FIELDS[field]
+    m, top = f.m, 1 << 254
+    # the device keeps an element as nine 30-bit limbs (limb 8 = bits 240 and up).  m - 1 has limb 8 = 2^14, limbs 5..7 = 0 and limbs
+    # 0..4 = those of t - 1.  Lowering limb 8 by one and filling every limb below gives 2^254 - 1, which is listed on its own.  Going down
+    # from there, limbs 7, 6, 5 are zero and cannot be lowered; limb 4 is the next that can: lower it by one and set limbs 0..3 to 2^30 - 1.
+    # That is the largest value below m, with the top limb of m, in which every limb that is free to be full is full.
+    k = max(i for i in range(8) if ((m - 1) >> (30 * i)) & 0x3FFFFFFF)
+    full = (((m - 1) >> (30 * k)) - 1 << (30 * k)) | ((1 << (30 * k)) - 1)
+    assert top <= full < m and k == 4 and full & ((1 << 120) - 1) == (1 << 120) - 1
+    vals = [0, 1, 2, m - 1, m - 2, top, top + 1, top - 1, full, f.R, m - f.R, (m - 1) // 2, (m + 1) // 2]
+    assert len(set(vals)) == len(vals) and all(0 <= v < m for v in vals)
+    return vals
+
+
+def edge_residues(field: str) -> np.ndarray:
+    """(13, 4) uint64 stored-form rows: 0, 1, 2, m-1, m-2, 2^254, 2^254+1, 2^254-1, the fullest-limbed value below m (see
+    edge_residue_ints), R mod m (the stored form of one), m - R mod m (of minus one), (m-1)/2 and (m+1)/2"""
+    from tiny_ram_halo2_amd import synth
+    return synth.ints_to_limbs(edge_residue_ints(field))
+
+
+def with_edges(a, seed: int, field: str, zeros=False, zero_at=()):
+    """a copy of the (n, 4) array `a` (synth.field_elements) in which a fixed pseudo-random 1/64 of the rows, chosen by `seed`, hold edge
+    residues.  The zero residue is used only with zeros=True; otherwise the only zero rows are the indices in `zero_at` (a zero early in
+    a product column makes everything after it zero and the test blind)."""
+    from tiny_ram_halo2_amd import synth
+    a = np.array(a, dtype=np.uint64).reshape(-1, 4)
+    n = a.shape[0]
+    edges = edge_residues(field)
+    if not zeros:
+        edges = edges[1:]
+    pick = synth.splitmix64_stream(0xED6E0000 ^ seed, 0, n)
+    sel = (pick & np.uint64(63)) == 0
+    a[sel] = edges[((pick[sel] >> np.uint64(6)) % np.uint64(len(edges))).astype(np.int64)]
+    for i in zero_at:
+        a[i] = 0
+    if not zeros:
+        assert int((~a.any(axis=1)).sum()) == len(set(int(i) % n for i in zero_at))
+    return a
+
+
 # ---- library options are fixed while a context exists (trh_set_option / TRH_<NAME> read once): a test that needs another setting runs the
 #      computation in a fresh process and compares what it prints with this process's result -----------------------------------------------
 def run_with_options(script: str, env: dict, timeout: int = 600) -> str:

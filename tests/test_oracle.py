@@ -126,6 +126,47 @@ def test_ntt_roundtrip_and_horner_2_16(field):
     assert (cpu_ref.field_op(field, "mul", inv, ninv) == a).all()
 
 
+@pytest.mark.parametrize("field", FIELDS)
+def test_field_ops_on_edge_residues_cpu_ref(field):
+    """the C++ oracle on the stored words random data never gives it (0, 1, m - 1, [2^254, m), R, ...; common.edge_residues): add, sub,
+    mul, sqr and neg on every ordered pair against big-int arithmetic on the stored forms.  The size tests of the scan, reduction and
+    powers kernels take this oracle as their reference on inputs that hold these words."""
+    from common import edge_residue_ints, edge_residues, stored_ints
+    f = o.FIELDS[field]
+    m, rinv = f.m, pow(f.R, -1, f.m)
+    vals, rows = edge_residue_ints(field), edge_residues(field)
+    assert stored_ints(rows) == vals and len(vals) == 13
+    assert (rows[9] == np.array(f.limbs(1), np.uint64)).all() and (rows[10] == np.array(f.limbs(m - 1), np.uint64)).all()
+    ia, ib = np.divmod(np.arange(len(vals) ** 2), len(vals))
+    a, b = rows[ia], rows[ib]
+    want = {
+        "add": [(x + y) % m for x in vals for y in vals],
+        "sub": [(x - y) % m for x in vals for y in vals],
+        "mul": [x * y * rinv % m for x in vals for y in vals],  # Montgomery product of the stored forms
+        "sqr": [x * x * rinv % m for x in vals for _ in vals],
+        "neg": [-x % m for x in vals for _ in vals],
+    }
+    for op in ("add", "sub", "mul"):
+        assert stored_ints(cpu_ref.field_op(field, op, a, b)) == want[op], op
+    for op in ("sqr", "neg"):
+        assert stored_ints(cpu_ref.field_op(field, op, a)) == want[op], op
+
+
+@pytest.mark.parametrize("field", FIELDS)
+def test_with_edges_places_every_residue_and_only_the_allowed_zeros(field):
+    """common.with_edges: 1/64 of the rows, the same ones for the same seed, every edge residue used, zeros only where asked for"""
+    from common import edge_residue_ints, stored_ints, with_edges
+    from tiny_ram_halo2_amd import synth
+    vals = edge_residue_ints(field)
+    base = synth.field_elements(0xED6E, 1 << 14)
+    e = with_edges(base, 7, field, zero_at=(5,))
+    changed = (e != base).any(axis=1)
+    assert 150 < int(changed.sum()) < 370 and (e == with_edges(base, 7, field, zero_at=(5,))).all()
+    assert [i for i in range(len(e)) if not e[i].any()] == [5]
+    assert set(stored_ints(e[changed])) == set(vals)  # every residue is used (the zero is the one at index 5)
+    assert int((~with_edges(base, 7, field, zeros=True).any(axis=1)).sum()) > 5
+
+
 def test_ipa_prover_restatement_satisfies_the_verifier_equation():
     """the two oracle restatements (commitment::create_proof and commitment::verify_proof) agree: what the reference's own
     tests pin for this path is exactly `verifier accepts` (src/test_utils.rs:52-68)"""
