@@ -1,7 +1,9 @@
 // csrc/hostplan.h without a device: the range boundaries msm_host_tiled (capi.hip) cuts an MSM with host scalars at, in both modes
 // (host bases: equal ranges of ceil(n / ceil(n / 2^20)) pairs above 2^21; resident bases: 2^21, 2^22, the rest above 3 * 2^21), and the
 // pass plan of the NTT for every accepted size.  The range counts asserted here are the ones the GPU tests expect from trh_stat
-// "msm_host_ranges" (tests/test_gpu_dropin.py, tests/test_gpu_realsize.py).  Plain C++, run by tests/test_hostcombine.py.
+// "msm_host_ranges" (tests/test_gpu_dropin.py, tests/test_gpu_realsize.py).  Then the launch plan of an MSM on the device (msm_route, msm_plan):
+// the invariants the kernels of msm.hip rely on over a sweep of shapes, the routes at their edges and the geometry of named shapes.
+// Plain C++, run by tests/test_hostcombine.py.
 #include <cstdio>
 
 #include "../../tiny-ram-halo2_amd/csrc/hostplan.h"
@@ -82,6 +84,76 @@ int main() {
         ntt_plan_passes(25, s, &P, &tlog); expect(P == 3 && s[0] == 9 && s[1] == 8 && s[2] == 8, "2^25 is 9 + 8 + 8", 25, P);
         ntt_plan_passes(26, s, &P, &tlog); expect(P == 3 && s[0] == 9 && s[1] == 9 && s[2] == 8, "2^26 is 9 + 9 + 8", 26, P);
         ntt_plan_passes(27, s, &P, &tlog); expect(P == 3 && s[0] == 9 && s[1] == 9 && s[2] == 9, "2^27 is 9 + 9 + 9", 27, P);
+    }
+
+    // MSM launch plan: invariants over the sweep
+    {
+        std::vector<size_t> ns = {1, 2, 255, 256, 8448, 8449};
+        for (int k = 9; k <= 31; ++k) { ns.push_back(((size_t)1 << k) - 1); ns.push_back((size_t)1 << k); ns.push_back(((size_t)1 << k) + 1); }
+        const size_t batches[] = {1, 2, 4, 5, 7, 8, 64, 65, 200};
+        const int tables[] = {0, 4, 14, 15, 18}, overrides[] = {0, 2, 13, 18};
+        const unsigned gbs[] = {1, 4};
+        for (size_t n : ns) for (size_t batch : batches) for (int fc : tables) for (int ov : overrides) for (unsigned gb : gbs) {
+            if (fc && !msm_fixed_base_fits(n, fc)) continue;
+            const MsmPlan p = msm_plan(MsmShape{n, batch, fc, ov, gb});
+            expect(p.k1 + p.k2 == p.c - 1, "k1 + k2 == c - 1", n, batch);
+            expect(p.idx_bits + p.k2 <= 31, "index and low bucket bits fit the entry", n, batch);
+            expect(p.nbins <= 2048 && p.nbins == 1u << p.k1, "at most 2048 level-1 bins (LDS of the partition)", n, p.nbins);
+            expect((size_t)p.slice * p.tpw == p.nbk, "slice * tpw == nbk", n, batch);
+            expect(p.chunk >= 1 && p.chunk <= 64, "1 <= chunk <= 64", n, p.chunk);
+            expect(p.tpw <= 256 || (size_t)p.Ws * p.tpw * p.chunk <= ((size_t)1 << 16) || p.tpw == p.nbk, "reduction within 2^16 threads", n, p.tpw);
+            expect(p.seg_len0 == 16 || p.seg_len0 == 32 || p.seg_len0 == 64 || p.seg_len0 == 128, "segment length", n, p.seg_len0);
+            expect((size_t)p.nseg0 * p.seg_len0 >= p.ns, "the segments cover the slots", n, p.nseg0);
+            if (p.use_bin_shape) expect(p.bin_cap % 1024 == 0 && p.bin_cap <= BIN_CAP_MAX && p.avg_bin >= 4096, "LDS bin sort: capacity and bin size", n, p.bin_cap);
+            // counts: [bin counts][tile flags][oversize flags][entry totals], 16 bytes of slack
+            expect(p.tile_flags_off() == p.bins_bytes(p.chunk) && p.oversize_off() == p.tile_flags_off() + p.flag_bytes && p.totals_off() == p.oversize_off() + p.chunk * p.Ws * 4 &&
+                   p.counts_bytes() == p.totals_off() + p.chunk * p.Ws * 4 + 16, "counts: four disjoint regions, then 16 bytes", n, batch);
+            expect(p.tile_flags_off() % 4 == 0 && p.oversize_off() % 4 == 0 && p.totals_off() % 4 == 0, "counts: regions 4-byte aligned", n, batch);
+            expect((fc != 0) == (p.flag_bytes != 0) && p.flag_bytes >= (fc ? p.chunk * p.part_tiles : 0), "tile flags: one byte per (item, partition tile) of a tabled set", n, p.flag_bytes);
+            expect((p.recode_use_lds != 0) == ((size_t)p.Ws * p.nbins * 4 <= 65536), "recode histogram in LDS up to 64 KiB", n, p.recode_lds);
+        }
+    }
+    // routes at their edges (no table, no override)
+    {
+        const size_t T = (size_t)1 << 25;
+        auto route = [](size_t n, size_t batch, int ov, bool in_tile, size_t* tiles, size_t* len) { return msm_route(MsmShape{n, batch, 0, ov, 4}, in_tile, false, tiles, len); };
+        size_t tiles = 0, len = 0;
+        expect(route(8448, 4, 0, false, &tiles, &len) == MSM_ROUTE_SMALL, "(8448, 4) is one launch", 8448, 4);
+        expect(route(8449, 4, 0, false, &tiles, &len) == MSM_ROUTE_PIPELINE, "(8449, 4) is the pipeline", 8449, 4);
+        expect(route(8448, 5, 0, false, &tiles, &len) == MSM_ROUTE_PIPELINE, "(8448, 5) is the pipeline", 8448, 5);
+        expect(route(T, 1, 0, false, &tiles, &len) == MSM_ROUTE_PIPELINE, "(2^25, 1) is the pipeline", T, 1);
+        expect(route(T + 1, 1, 0, false, &tiles, &len) == MSM_ROUTE_TILED && tiles == 2 && len == T / 2 + 1, "(2^25 + 1, 1): 2 tiles of 2^24 + 1", tiles, len);
+        // the count tests/test_gpu_realsize.py expects from trh_stat "msm_range_tiles"
+        expect(route(T + 3, 1, 0, false, &tiles, &len) == MSM_ROUTE_TILED && tiles == 2, "(2^25 + 3, 1): 2 tiles", tiles, len);
+        expect(route(T + 1, 2, 0, false, &tiles, &len) == MSM_ROUTE_PIPELINE, "(2^25 + 1, 2) is the pipeline", T + 1, 2);
+        expect(route(T + 1, 1, 16, false, &tiles, &len) == MSM_ROUTE_PIPELINE, "(2^25 + 1, 1) with a window override is the pipeline", T + 1, 16);
+        expect(route(T + 1, 1, 0, true, &tiles, &len) == MSM_ROUTE_PIPELINE, "(2^25 + 1, 1) in a tile is the pipeline", T + 1, 1);
+    }
+    // named shapes.  The 256 bins and BIN_CAP = 5120 that tests/test_gpu_msm_sort.py hard-codes are the (2^20, 1) row.
+    {
+        const struct { size_t n, batch; int fc, c, W, Ws, k2; unsigned nbins; size_t chunk; unsigned tpw, slice, seg_len0, nseg0, bin_cap; bool use_bin; } rows[] = {
+            {8449u, 1, 0, 8, 32, 32, 7, 1, 1, 128, 1, 16, 529, 10240, true},
+            {65536u, 64, 0, 10, 26, 26, 7, 4, 64, 256, 2, 128, 512, 18432, true},
+            {262144u, 1, 0, 15, 18, 18, 7, 128, 1, 2048, 8, 16, 16384, 3072, false},
+            {1048576u, 1, 0, 16, 16, 16, 7, 256, 1, 4096, 8, 64, 16384, 5120, true},
+            {1048576u, 4, 0, 16, 16, 16, 7, 256, 4, 1024, 32, 128, 8192, 5120, true},
+            {16777216u, 1, 0, 17, 16, 16, 7, 512, 1, 4096, 16, 128, 131072, 35840, true},
+            {33554432u, 1, 0, 17, 16, 16, 6, 1024, 1, 4096, 16, 128, 262144, 35840, true},
+            {268435456u, 1, 0, 15, 18, 18, 3, 2048, 1, 2048, 8, 128, 2097152, 0 /* beyond BIN_CAP_MAX */, false},
+            {2147483648u, 1, 0, 12, 22, 22, 0, 2048, 1, 2048, 1, 128, 16777216, 0 /* beyond BIN_CAP_MAX */, false},
+            {4194304u, 200, 0, 16, 16, 16, 7, 256, 5, 512, 64, 128, 32768, 18432, true},
+            {65538u, 2, 14, 14, 19, 1, 7, 64, 2, 8192, 1, 16, 77827, 21504, true},
+            {262146u, 2, 15, 15, 18, 1, 7, 128, 2, 16384, 1, 32, 147458, 39936, false},
+            {262145u, 100, 15, 15, 18, 1, 7, 128, 64, 1024, 16, 128, 36865, 39936, false},
+        };
+        for (const auto& r : rows) {
+            const MsmPlan p = msm_plan(MsmShape{r.n, r.batch, r.fc, 0, 4});
+            expect(p.c == r.c && p.W == r.W && p.Ws == r.Ws && p.k2 == r.k2 && p.nbins == r.nbins, "named shape: window bits, windows, bucket sets, k2, bins", r.n, r.batch);
+            expect(p.chunk == r.chunk && p.tpw == r.tpw && p.slice == r.slice, "named shape: chunk, reduce geometry", r.n, r.batch);
+            expect(p.seg_len0 == r.seg_len0 && p.nseg0 == r.nseg0, "named shape: segments", r.n, r.batch);
+            expect(r.bin_cap ? p.bin_cap == r.bin_cap : p.bin_cap > BIN_CAP_MAX, "named shape: bin capacity", r.n, p.bin_cap);
+            expect(p.use_bin_shape == r.use_bin, "named shape: LDS bin sort", r.n, r.batch);
+        }
     }
     std::printf(bad ? "hostplan: FAILED (%d)\n" : "hostplan: ok\n", bad);
     return bad ? 1 : 0;

@@ -665,11 +665,10 @@ int msm_sharded(trh_bases* B, size_t offset, const void* scalars, bool scalars_o
             // no sparse vote on a shard: the sampler ends in a host synchronisation behind this shard's upload / hand-over, which
             // would hold back the enqueues of the later shards; a range-sharded MSM is a full-size one
             // (its own flag: dense_hint also selects the quad-lane combine, which is for callers that vouch for full-size scalars -- ADVICE r05)
-            const bool keep = sc->msm.no_sparse_vote;
-            sc->msm.no_sparse_vote = true;
+            MsmFlags no_vote;
+            no_vote.no_sparse_vote = true;
             rc = msm_enqueue(B->curve, (const char*)sh->d_xy + rg[g].local * 64, lazy_bases(sh, rg[g].local, sc->own_stream), sc->msm.scalars.p, rg[g].cnt, 1, rg[g].cnt, mont, sc->own_stream,
-                             fixed_base(sh, rg[g].local, rg[g].cnt));
-            sc->msm.no_sparse_vote = keep;
+                             fixed_base(sh, rg[g].local, rg[g].cnt), nullptr, no_vote);
         }
         if (rc != TRH_OK) { join_all(); return rc; }
     }
@@ -938,6 +937,18 @@ int single_device(trh_bases_t bases, const char* what) {
     return TRH_OK;
 }
 }  // namespace
+// trh_msm_dev; the flags are the self-test's way to the pipeline and the quad combine at a size the small kernel would take
+int msm_dev_flagged(trh_bases_t bases, size_t offset, const void* scalars_dev, size_t n, int mont, void* stream, uint64_t out[12], MsmFlags flags) {
+    TRH_TRY(msm_args(bases, offset, scalars_dev, n, 1, out));
+    if (!bases->shards.empty()) return msm_sharded(bases, offset, scalars_dev, false, n, mont, (hipStream_t)stream, out);
+    TRH_ENTER(stream);
+    Range range("trh_msm_dev");
+    TRH_TRY(single_device(bases, "msm_dev"));
+    if (ctx().msm.pending_curve >= 0) { set_error("msm_dev: this context has an enqueued MSM that was not finished"); return TRH_EBUSY; }
+    TRH_TRY(msm_enqueue(bases->curve, (const char*)bases->d_xy + offset * 64, lazy_bases(bases, offset, (hipStream_t)stream), scalars_dev, n, 1, n, mont, (hipStream_t)stream, fixed_base(bases, offset, n),
+                        nullptr, flags));
+    return msm_finish(bases->curve, (hipStream_t)stream, out, 1);
+}
 }  // namespace trh
 
 extern "C" {
@@ -981,10 +992,9 @@ int trh_bases_reserve(trh_bases_t b, size_t n, size_t batch) {
     Ctx& c = ctx();
     if (c.msm.pending_curve >= 0) { set_error("bases_reserve: this context has an enqueued MSM that was not finished"); return TRH_EBUSY; }
     TRH_TRY(c.msm.tails.ensure(batch * 32));
-    c.msm.reserve_only = true;
-    const int rc = msm_enqueue(b->curve, b->d_xy, lazy_bases(b, 0, nullptr), b->d_xy /* never read */, n, batch, n, 1, nullptr, fixed_base(b, 0, n), batch > 1 ? c.msm.tails.p : nullptr);
-    c.msm.reserve_only = false;
-    TRH_TRY(rc);
+    MsmFlags reserve;
+    reserve.reserve_only = true;
+    TRH_TRY(msm_enqueue(b->curve, b->d_xy, lazy_bases(b, 0, nullptr), b->d_xy /* never read */, n, batch, n, 1, nullptr, fixed_base(b, 0, n), batch > 1 ? c.msm.tails.p : nullptr, reserve));
     // the shape of an IPA opening's round MSMs -- two rows over the whole of a tabled set of 2^k + 2 points (g || w || u): the opening's own buffers too
     if (batch == 2 && n == b->n && b->d_table && n > 2 && ((n - 2) & (n - 3)) == 0) {
         uint32_t k = 0;
@@ -1062,14 +1072,7 @@ int trh_msm_dev_finish(trh_bases_t bases, void* stream, uint64_t out[12]) {
     return msm_finish(bases->curve, (hipStream_t)stream, out, 1);
 }
 int trh_msm_dev(trh_bases_t bases, size_t offset, const void* scalars_dev, size_t n, int mont, void* stream, uint64_t out[12]) {
-    TRH_TRY(msm_args(bases, offset, scalars_dev, n, 1, out));
-    if (!bases->shards.empty()) return msm_sharded(bases, offset, scalars_dev, false, n, mont, (hipStream_t)stream, out);
-    TRH_ENTER(stream);
-    Range range("trh_msm_dev");
-    TRH_TRY(single_device(bases, "msm_dev"));
-    if (ctx().msm.pending_curve >= 0) { set_error("msm_dev: this context has an enqueued MSM that was not finished"); return TRH_EBUSY; }
-    TRH_TRY(msm_enqueue(bases->curve, (const char*)bases->d_xy + offset * 64, lazy_bases(bases, offset, (hipStream_t)stream), scalars_dev, n, 1, n, mont, (hipStream_t)stream, fixed_base(bases, offset, n)));
-    return msm_finish(bases->curve, (hipStream_t)stream, out, 1);
+    return msm_dev_flagged(bases, offset, scalars_dev, n, mont, stream, out, MsmFlags{});
 }
 int trh_msm_batch_dev(trh_bases_t bases, size_t offset, const void* scalars_dev, size_t n, size_t batch, int mont, void* stream, uint64_t* out) {
     TRH_TRY(msm_args(bases, offset, scalars_dev, n, batch, out));

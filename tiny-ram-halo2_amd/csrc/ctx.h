@@ -124,23 +124,29 @@ struct MsmLane {         // scratch of one chunk of MSMs (leading dimension: bat
     DevBuf sparse;       // sparse-column path: per item SP_LISTS list counters (one 128-byte line each), then one dense flag per item
 };
 
+// what a caller of msm_enqueue says about ONE call (an argument, not context state)
+struct MsmFlags {
+    bool dense_hint = false;      // the caller knows its scalars are full-size (the IPA's round MSMs): the sparse classifier is skipped, the combine takes the quad form
+    bool no_sparse_vote = false;  // the sparse classifier is skipped and nothing else changes (the shards of a range-sharded MSM: its host synchronisation would hold back the other shards)
+    bool force_fallback = false;  // neither the one-launch small kernel nor the lean sort (msm_finish's retry, the self-test)
+    bool reserve_only = false;    // msm_enqueue sizes the scratch of the described launch and returns before the first kernel (trh_bases_reserve)
+    bool in_tile = false;         // the call is one range tile of a larger MSM (msm.hip's own recursion)
+};
+
 struct MsmScratch {
     DevBuf scalars;      // host-scalar entry points stage here
     DevBuf tails;        // blinds of a commit batch (scalar n of every item)
     DevBuf bases_z;      // n affine bases converted to the lazy domain
     DevBuf window_sums;  // batch x W XYZZ
     MsmLane lane;
-    bool dense_hint = false;    // the caller knows its scalars are full-size (the IPA's round MSMs): the sparse classifier is skipped, the combine takes the quad form
     // lean sort (msm.hip): the enqueued MSM skipped the chunked fallback passes; msm_finish checks the flags and repeats it with them if needed
-    bool force_fallback = false, lean_pending = false;
-    struct { const void *bases_dev, *bases_z, *scalars_dev, *tails_dev; size_t n, batch, stride; int mont; bool has_fb; MsmFixedBase fb; } retry{};
+    bool lean_pending = false;
+    struct { const void *bases_dev, *bases_z, *scalars_dev, *tails_dev; size_t n, batch, stride; int mont; bool has_fb; MsmFixedBase fb; MsmFlags flags; } retry{};
     unsigned lean_retries = 0;  // how often that happened on this context (tests)
     u64 small_launches = 0;     // MSMs that ran as one msm_small_kernel launch (tests: the path was taken, not fallen back from)
     const u32* sort_flags = nullptr;  // the last MSM's last chunk: its per-window "a bin did not fit the LDS" flags (null: no bin sort), for trh_stat
     u32 sort_flag_count = 0;
     size_t lean_off_n = 0; int lean_off_c = 0;  // the shape (pairs, window bits) whose lean sort last overflowed: the fallback launches are queued for it again
-    bool reserve_only = false;  // msm_enqueue sizes the scratch of the described launch and returns before the first kernel (trh_bases_reserve)
-    bool no_sparse_vote = false;  // the sparse classifier is skipped and nothing else changes (the shards of a range-sharded MSM: its host synchronisation would hold back the other shards)
     void* sp_host = nullptr;    // pinned: the sparse path's list counters as read back, then the dense flags it sends down
     void* host_sums = nullptr;  // pinned mirror of window_sums
     size_t host_sums_cap = 0;
@@ -149,8 +155,9 @@ struct MsmScratch {
     size_t pending_batch = 0;
     hipStream_t pending_stream = nullptr;  // the finish must name the stream (and, through the C ABI, the base set) of its enqueue
     const void* pending_owner = nullptr;
+    bool pending_in_tile = false;  // the pending MSM is an inner range tile: its finish does not add the running tile sum
     // an MSM beyond MSM_TILE pairs runs as range tiles: the sum of the finished tiles (normalised Jacobian), added by msm_finish
-    bool tile_sum_valid = false, in_tile = false;
+    bool tile_sum_valid = false;
     u64 tile_sum[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     u64 range_tiles = 0;  // tiles of the last MSM enqueue that ran as range tiles, 0 if it did not (tests: the branch was taken)
     u64 host_ranges = 0;  // ranges of the last MSM with host scalars (msm_host_tiled in capi.hip; tests)
@@ -336,7 +343,9 @@ int ipa_reserve(int curve, const trh_bases* gw, uint32_t k);  // ipa.hip: the op
 int ipa_fold_generators(int curve, const MsmFixedBase& fb, size_t row, uint32_t k, uint32_t r, const u64* u_mont, void* out_xy, void* out_z, hipStream_t s);
 // msm.hip
 int msm_enqueue(int curve, const void* bases_dev, const void* bases_z_or_null, const void* scalars_dev, size_t n, size_t batch,
-                size_t scalar_stride_elems, int mont, hipStream_t s, const MsmFixedBase* fb = nullptr, const void* tails_dev = nullptr);
+                size_t scalar_stride_elems, int mont, hipStream_t s, const MsmFixedBase* fb = nullptr, const void* tails_dev = nullptr, MsmFlags flags = {});
+// trh_msm_dev with the flags of its one msm_enqueue (capi.hip; the self-test runs the pipeline and the quad combine through it)
+int msm_dev_flagged(::trh_bases* bases, size_t offset, const void* scalars_dev, size_t n, int mont, void* stream, uint64_t out[12], MsmFlags flags);
 size_t msm_small_max_pairs();  // the largest MSM msm_small_kernel takes (batches of up to four, no window override)
 int msm_fixed_base_windows(int c);
 bool msm_fixed_base_fits(size_t n, int c);

@@ -1,8 +1,10 @@
 // Host-side shape decisions of the two headline operations, free of HIP types so that a plain C++ test can check them
-// (tests/native/hostplan_test.cpp): where msm_host_tiled (capi.hip) cuts an MSM with host scalars into ranges, and how
-// ntt.hip splits a transform into passes.
+// (tests/native/hostplan_test.cpp): where msm_host_tiled (capi.hip) cuts an MSM with host scalars into ranges, how
+// ntt.hip splits a transform into passes, and the launch plan of an MSM on the device (msm.hip: route, Pippenger geometry,
+// scratch layout) as a pure function of its shape.
 #pragma once
 #include <cstddef>
+#include <cstdint>
 #include <vector>
 
 namespace trh {
@@ -46,6 +48,230 @@ inline void ntt_plan_passes(int log_n, int* sizes, int* n_passes, int* tile_log)
         for (int p = 0; p < P; ++p) { sizes[p] = (rem + (P - p) - 1) / (P - p); rem -= sizes[p]; }
     }
     *n_passes = P; *tile_log = NTT_TILE_LOG;
+}
+
+// ---------------------------------------------------------------------------------------
+// The launch plan of one MSM on the device (msm.hip): which route msm_enqueue takes, the Pippenger geometry of the pipeline and the
+// layout of its scratch, all integer functions of the shape.  No HIP types, no context, no options, no heap: it runs on every MSM.
+// The constants are the ones the kernels of msm.hip are built with (each is described where its kernel is).
+// ---------------------------------------------------------------------------------------
+constexpr int MAX_C = 18;
+constexpr int MAX_C_FIXED = 18;  // fixed-base tables: one bucket set per MSM, so wider windows pay
+// Above 2^25 pairs the entry index squeezes the second sort level (31 bits = index + low bucket bits) and the rate drops
+// (2^25: 815 M pairs/s, 2^26: 740, 2^27: 490, 2^28: 410): larger MSMs run as equal range tiles of at most 2^25 pairs, each
+// at the full rate; the tiles' points are added on the host (the same sum the range-sharded multi-GPU path forms).
+constexpr size_t MSM_TILE = (size_t)1 << 25;
+constexpr int SMALL_C = 5;                  // msm_small_kernel
+constexpr uint32_t SMALL_MAX_N = 8448;      // LDS: one byte + one u16 per scalar
+constexpr int PART_TILE = 16384;            // msm_partition_kernel: digits per workgroup tile
+constexpr int BIN_THREADS = 1024;           // msm_bin_sort_kernel
+constexpr int BIN_PER_MAX = 36;                             // entries per thread, kept in registers from the load to the last pass
+constexpr uint32_t BIN_CAP_MAX = BIN_THREADS * BIN_PER_MAX; // 36864 entries
+constexpr int RANGE_BLOCK = 1024;           // msm_bucket_block_sums_kernel / msm_bucket_ranges_kernel
+constexpr uint32_t HEAVY_PIECES = 64;       // msm_combine_heavy_kernel
+constexpr int SP_LISTS = 16;              // compact lists per column (one counter each: a single counter per column would serialise its 1025 workgroups)
+constexpr int SP_CNT = 2 * SP_LISTS;      // counters per column: the SP_LISTS digit lists, then the SP_LISTS unit lists
+constexpr uint32_t SP_PAD = 32;           // u32 words between two list counters (one 128-byte line each)
+constexpr int SP_PARTS = SP_LISTS + 1;    // partial sums per column: one per unit list, one for the digit entries of a tiny column
+constexpr size_t SP_MAX_CHUNK = 256;      // items per launch set the pinned read-back area is sized for
+constexpr size_t XYZZ_BYTES = 128;        // a window sum (XYZZMem)
+constexpr size_t RAW_POINT_BYTES = 144;   // a raw lazy point of the accumulate -> combine -> reduce scratch (XYZZzMem)
+
+inline int ilog2_floor(size_t n) {
+    int l = 0;
+    while ((n >> (l + 1)) != 0) ++l;
+    return l;
+}
+
+inline int choose_window_bits(size_t n, int window_override) {
+    const int o = window_override;
+    if (o >= 2 && o <= MAX_C) return o;
+    // measured on MI355X (tools/window_sweep.py): below 2^15 pairs an MSM is latency-bound and the width
+    // hardly matters; from 2^16 the wide windows win (fewer mixed adds, more level-1 sort bins)
+    const int l = ilog2_floor(n ? n : 1);
+    // 2^24 / 2^25: c = 17 (15 full windows + an almost always empty carry window) beats 16 by 3 %; from 2^26 the index
+    // takes 26 of the 31 entry bits, which leaves 5 low bucket bits for the second sort level, and 16 wins again
+    return l < 9 ? 4 : l < 15 ? 8 : l == 15 ? 11 : l == 16 ? 10 : l == 17 ? 12 : l < 20 ? 15 : l < 24 ? 16 : l < 26 ? 17 : 16;
+}
+inline int num_windows(int c) { return 255 / c + 1; }
+// the partitioned entries pack 7 low bucket bits above the flat table index
+inline bool msm_fixed_base_fits(size_t n, int c) {
+    if (c < 2 || c > MAX_C_FIXED) return false;
+    return (size_t)num_windows(c) * n <= ((size_t)1 << 24);
+}
+
+struct MsmShape {
+    size_t n, batch;       // pairs per item, items
+    int fb_c;              // window bits of the fixed-base table the MSM runs over, 0: no table
+    int window_override;   // the context's override, 0: none
+    unsigned chunk_gb;     // option msm_chunk_gb
+};
+
+enum MsmRoute { MSM_ROUTE_TILED, MSM_ROUTE_SMALL, MSM_ROUTE_PIPELINE };
+// TILED: range tiles of `len` pairs (the last one shorter), each through msm_route again with in_tile; SMALL: one launch (msm_small_kernel)
+inline MsmRoute msm_route(const MsmShape& sh, bool in_tile, bool force_fallback, size_t* tiles = nullptr, size_t* len = nullptr) {
+    if (!sh.fb_c && sh.batch == 1 && sh.n > MSM_TILE && !in_tile && sh.window_override == 0) {
+        const size_t t = (sh.n + MSM_TILE - 1) / MSM_TILE;
+        if (tiles) *tiles = t;
+        if (len) *len = (sh.n + t - 1) / t;
+        return MSM_ROUTE_TILED;
+    }
+    if (!sh.fb_c && sh.n != 0 && sh.n <= SMALL_MAX_N && sh.batch <= 4 && sh.window_override == 0 && !in_tile && !force_fallback) return MSM_ROUTE_SMALL;
+    return MSM_ROUTE_PIPELINE;
+}
+
+// segments of the sorted lists (one thread of msm_accumulate_seg_kernel each) and the heavy-bucket list that goes with them
+struct MsmSegments { uint32_t seg_len, nseg, heavy_stride; unsigned heavy_blocks; };
+// a heavy bucket spans > HEAVY_PIECES segments, so there are fewer than W * nseg / HEAVY_PIECES of them
+inline size_t msm_max_heavy(int Ws, uint32_t nseg) { return (size_t)Ws * nseg / HEAVY_PIECES + 1; }
+inline MsmSegments msm_segments(int Ws, uint32_t seg_len, uint32_t nseg) {
+    const size_t mh = msm_max_heavy(Ws, nseg);
+    return MsmSegments{seg_len, nseg, (uint32_t)(mh + 1), (unsigned)(mh < 256 ? mh : 256)};
+}
+
+struct MsmPlan {
+    size_t n, batch;
+    bool fb;                 // fixed-base mode (a table): one bucket set per item
+    int c, W, Ws;            // window bits, windows of the recoding, bucket sets per item
+    size_t ns;               // slots per item and bucket set
+    uint32_t nbk, nb1;       // buckets per set, + 1
+    int idx_bits, k1, k2;    // sort geometry (see msm_plan)
+    uint32_t nbins;
+    size_t recode_lds; int recode_use_lds;
+    size_t chunk;            // items per launch set
+    uint32_t tpw, slice, rblocks;  // reduce geometry: threads per window, buckets per thread, workgroups
+    uint32_t seg_len0, nseg0;  // the segments every launch starts from (run_chunk resizes them for dense and counted chunks)
+    size_t max_heavy; uint32_t heavy_stride0; unsigned heavy_blocks0;
+    uint32_t part_tiles; size_t flag_bytes;
+    unsigned range_blocks;
+    size_t avg_bin; uint32_t bin_cap;
+    bool use_bin_shape;      // the shape half of "LDS bin sort" (option bin_sort is the other)
+    bool adaptive;
+    uint32_t sp_subcap, sp_cap;
+    bool sparse_shape_ok;    // the shape half of "ask the sparse sampler" (option, table and the call's flags are the other)
+
+    MsmSegments seg0() const { return MsmSegments{seg_len0, nseg0, heavy_stride0, heavy_blocks0}; }
+    // ---- scratch layout: every size msm.hip reserves, zeroes or offsets by, once
+    size_t entries_bytes() const { return chunk * W * n * 4 + 16; }                     // digits, parted, sorted
+    // counts: [bin counts][fixed-base mode: one byte per (item, partition tile)][oversize-bin flags of the LDS bin sort][entry totals per item and window]
+    size_t bins_bytes(size_t items) const { return items * Ws * nbins * 4; }            // (also bin_starts, for `chunk` items)
+    size_t tile_flags_off() const { return bins_bytes(chunk); }
+    size_t oversize_off() const { return tile_flags_off() + flag_bytes; }
+    size_t set_words_bytes() const { return chunk * Ws * 4; }                           // one u32 per (item, bucket set)
+    size_t totals_off() const { return oversize_off() + set_words_bytes(); }
+    size_t counts_used() const { return totals_off() + set_words_bytes(); }
+    size_t counts_bytes() const { return counts_used() + 16; }
+    size_t ranges_bytes(size_t items) const { return items * Ws * nb1 * 4; }            // starts, ends, bucket_cnt (+ 16)
+    size_t seg_bucket_bytes() const { return chunk * Ws * range_blocks * 4 + 16; }      // block totals of the chunked passes' range scan
+    size_t pieces_bytes(uint32_t nseg) const { return chunk * Ws * nseg * RAW_POINT_BYTES; }  // first, last
+    size_t direct_bytes() const { return chunk * Ws * nb1 * RAW_POINT_BYTES; }
+    size_t heavy_bytes(size_t items, uint32_t heavy_stride) const { return items * heavy_stride * 4; }
+    size_t buckets_bytes() const { return chunk * Ws * nbk * RAW_POINT_BYTES; }
+    size_t partials_bytes(uint32_t blocks) const { return chunk * Ws * blocks * RAW_POINT_BYTES; }
+    // sparse: [counters: chunk x SP_CNT lines][partial sums: chunk x SP_PARTS raw points]
+    size_t sparse_counter_words() const { return chunk * SP_CNT * SP_PAD; }
+    size_t sparse_bytes() const { return sparse_counter_words() * 4 + chunk * SP_PARTS * RAW_POINT_BYTES + 64; }
+    // window sums: batch x Ws XYZZ, then (lean sort) one overflow flag per (item, bucket set)
+    size_t sum_flags_off() const { return batch * Ws * XYZZ_BYTES; }
+    size_t sums_bytes(bool lean_sort) const { return sum_flags_off() + (lean_sort ? batch * Ws * 4 : 0); }
+};
+
+inline MsmPlan msm_plan(const MsmShape& sh) {
+    MsmPlan p{};
+    const size_t n = sh.n, batch = sh.batch;
+    p.n = n; p.batch = batch; p.fb = sh.fb_c != 0;
+    int cb = p.fb ? sh.fb_c : choose_window_bits(n, sh.window_override);
+    if (!p.fb) {
+        // beyond 2^27 pairs the index leaves fewer than 4 entry bits for the second sort level; the first level has at most
+        // 2^11 bins (LDS of the partition), so the window narrows with n (15 bits up to 2^28 pairs ... 12 up to 2^31)
+        int ib = 1;
+        while (((size_t)1 << ib) < n) ++ib;
+        const int k2max = 31 - ib < 7 ? 31 - ib : 7;
+        if (cb - 1 - k2max > 11) cb = 12 + k2max;
+    }
+    p.c = cb;
+    const int W = p.W = num_windows(cb);  // windows of the recoding
+    // fixed-base mode: the W x n digits are one flat list over the W x n table entries -> ONE bucket set
+    const int Ws = p.Ws = p.fb ? 1 : W;
+    const size_t ns = p.ns = p.fb ? (size_t)W * n : n;
+    const uint32_t nbk = p.nbk = 1u << (cb - 1);
+    p.nb1 = nbk + 1;
+    // sort geometry: bucket - 1 = bin << k2 | sub; the partitioned entry packs sub above the index
+    int idx_bits = 1;
+    while (((size_t)1 << idx_bits) < ns) ++idx_bits;
+    int k2 = cb - 1 < 7 ? cb - 1 : 7;
+    if (k2 > 31 - idx_bits) k2 = 31 - idx_bits;
+    p.idx_bits = idx_bits; p.k2 = k2; p.k1 = cb - 1 - k2;
+    const uint32_t nbins = p.nbins = 1u << p.k1;
+    p.recode_lds = (size_t)Ws * nbins * 4;
+    p.recode_use_lds = p.recode_lds <= 64 * 1024;
+    // independent batch items (one MSM per column of create_proof, same bases) are processed
+    // `chunk` at a time by the SAME launches (blockIdx.z = item), so the latency-bound sort and
+    // reduction phases of one item are hidden behind the work of the others
+    size_t chunk = batch;
+    {
+        const size_t per_item = (size_t)W * n * 12 + 1;  // digits + parted + sorted dominate
+        // at most 64 items per launch set, inside the scratch budget (option msm_chunk_gb, default 4 GiB per digit array set)
+        const size_t cap = ((size_t)sh.chunk_gb << 30) / per_item;
+        if (chunk > cap) chunk = cap ? cap : 1;
+        if (chunk > 64) chunk = 64;
+        static_assert(64 <= SP_MAX_CHUNK, "chunk size against the pinned read-back area");
+    }
+    p.chunk = chunk;
+    // reduce geometry: each thread owns a slice of buckets and pays one short scalar multiplication for
+    // the slice offset, so long slices do less work per bucket but are a long serial chain: a lone MSM
+    // (latency-bound) gets 2048-4096 threads per window, a batch (throughput-bound) as few as 256
+    uint32_t tpw = nbk >= (1u << 15) ? 4096 : 2048;  // slices of >= 8 buckets (measured: 2^20..2^24 pairs gain 0.07-0.16 ms, 2^18 loses with 4096)
+    if (p.fb) tpw = 16384;  // one flat window per item: slices of 2 buckets while the batch is small (the cap below takes over for batches) -- the
+                            // opening's rounds are two such items each: reduce 240 -> 190 us per round, k = 18 opening 15.4 -> 14.6 ms
+    while (tpw > 256 && (size_t)Ws * tpw * chunk > ((size_t)1 << 16)) tpw >>= 1;  // 2^16 threads = one wave per SIMD (batch of 64 commits: 0.79 -> 0.62 ms)
+    if (tpw > nbk) tpw = nbk;
+    p.tpw = tpw;
+    p.slice = nbk / tpw;
+    p.rblocks = (tpw + 255) / 256;
+    // segment length: enough segments to fill the chip (>= ~2^18 threads) but at most 128 entries each
+    uint32_t seg_len0 = 128;
+    // (2^18, round 6: an opening's full-size round -- 2 x 4.2 M digit slots, half of them empty -- takes segments of 32 instead of 16: four pieces per
+    //  bucket for the combine instead of eight, k = 18 opening 8.2 -> 8.0 ms; 2^20 .. 2^22 MSMs and lone commitments unchanged; 2^17 loses: 9.0 ms)
+    while (seg_len0 > 16 && (size_t)W * n * chunk / seg_len0 < ((size_t)1 << 18)) seg_len0 >>= 1;  // W * n == Ws * ns
+    const MsmSegments s0 = msm_segments(Ws, seg_len0, (uint32_t)((ns + seg_len0 - 1) / seg_len0));
+    p.seg_len0 = s0.seg_len; p.nseg0 = s0.nseg; p.heavy_stride0 = s0.heavy_stride; p.heavy_blocks0 = s0.heavy_blocks;
+    p.max_heavy = msm_max_heavy(Ws, p.nseg0);
+    p.part_tiles = (uint32_t)((ns + PART_TILE - 1) / PART_TILE);
+    p.flag_bytes = p.fb ? ((size_t)chunk * p.part_tiles + 3) / 4 * 4 : 0;
+    // Batched commitments of WITNESS columns (flags, small words: a few 10^4 entries per column, most of them in a handful of buckets)
+    // leave the sorted lists almost empty, and fixed 128-entry segments then mean a few hundred threads each walking a serial chain of 128
+    // mixed additions (3 ms per batch of 64 flag columns at k = 18, the chip idle).  For batches the entry counts are read back after the
+    // histogram scan (one synchronisation per chunk, ~20 us) and the segment length is sized to the entries that exist.
+    p.adaptive = batch >= 8;
+    // LDS bin sort when the bins are big enough to fill a 1024-thread workgroup and fit with 6 % + 512 entries of slack
+    // (uniform digits: the largest of 8192 bins of 2^15 entries is 4.5 sigma = 800 entries above the mean)
+    const size_t avg_bin = p.avg_bin = ns / nbins;
+    p.bin_cap = (uint32_t)(((avg_bin + avg_bin / 16 + 512 + 1023) / 1024) * 1024);
+    p.use_bin_shape = avg_bin >= 4096 && p.bin_cap <= BIN_CAP_MAX;
+    p.range_blocks = (p.nb1 + RANGE_BLOCK - 1) / RANGE_BLOCK;  // <= 2^17 / 1024 + 1 = 129 < RANGE_BLOCK threads
+    p.sp_subcap = (uint32_t)(ns / 8 / SP_LISTS); p.sp_cap = p.sp_subcap * SP_LISTS;  // a column with more than W n / 8 entries is dense
+    p.sparse_shape_ok = p.fb && n >= 4096 && ns / 8 / SP_LISTS >= 1024 && sh.window_override == 0;
+    return p;
+}
+
+// full-size columns of a sparse chunk (nb of them): the slot count is the entry count
+inline MsmSegments msm_segments_dense(const MsmPlan& p, unsigned nb) {
+    uint32_t seg_len = 128;
+    while (seg_len > 16 && (size_t)p.W * p.n * nb / seg_len < ((size_t)1 << 19)) seg_len >>= 1;
+    return msm_segments(p.Ws, seg_len, (uint32_t)((p.ns + seg_len - 1) / seg_len));
+}
+// lists whose entry counts are known (compact lists, adaptive batches): `sum` entries in all, `most` in the longest list
+inline MsmSegments msm_segments_counted(const MsmPlan& p, size_t sum, uint32_t most) {
+    // segments for >= 2^17 live threads (round 4, compact lists: 2^16 2.67 / 1.84 / 2.13 / 2.96 / 2.85 ms for the five sparse batches of the k = 18
+    // proof, 2^17 2.37 / 1.85 / 2.03 / 2.88 / 2.88, 2^18 2.34 / 1.71 / 2.06 / 2.98 / 3.05: shorter segments shorten the accumulation's chains and
+    // lengthen the combine's)
+    constexpr int target_log = 17;
+    uint32_t seg_len = 128;
+    while (seg_len > 16 && sum / seg_len < ((size_t)1 << target_log)) seg_len >>= 1;
+    uint32_t nseg = (most + seg_len - 1) / seg_len;  // segments beyond the longest list would find nothing
+    if (nseg == 0) nseg = 1;
+    return msm_segments(p.Ws, seg_len, nseg);
 }
 
 }  // namespace hostplan

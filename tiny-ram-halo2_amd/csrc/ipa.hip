@@ -440,10 +440,9 @@ int ipa_create_proof_t(int curve, const trh_bases* gw, const u64* u_xy, uint32_t
     }
     u64 pt[12];
     if (fb) {  // the scalar of u is zero: the full-range (table) path
-        ctx().msm.dense_hint = true;  // s(X) is uniformly random: no sparse classification
-        const int rc_s = msm_enqueue(curve, gw->d_xy, gw->d_z, sp.p, n + 2, 1, n + 2, 1, s, fb);
-        ctx().msm.dense_hint = false;
-        TRH_TRY(rc_s);
+        MsmFlags dense;
+        dense.dense_hint = true;  // s(X) is uniformly random: no sparse classification
+        TRH_TRY(msm_enqueue(curve, gw->d_xy, gw->d_z, sp.p, n + 2, 1, n + 2, 1, s, fb, nullptr, dense));
     } else if (small_z)
     TRH_TRY(msm_enqueue(curve, gw->d_xy, small_z, sp.p, n + 2, 1, n + 2, 1, s));
     else
@@ -548,10 +547,9 @@ int ipa_create_proof_t(int curve, const trh_bases* gw, const u64* u_xy, uint32_t
             TRH_HIP_TRY(hipGetLastError());
         }
         u64 lrb[24], lr[2][12];
-        ctx().msm.dense_hint = true;  // p' . w: full-size values on half the rows
-        const int rc_r = msm_enqueue(curve, round_xy, round_z, lrsc.p, ncur + 2, 2, stride, canon ? 0 : 1, s, round_fb);
-        ctx().msm.dense_hint = false;
-        TRH_TRY(rc_r);
+        MsmFlags dense;
+        dense.dense_hint = true;  // p' . w: full-size values on half the rows
+        TRH_TRY(msm_enqueue(curve, round_xy, round_z, lrsc.p, ncur + 2, 2, stride, canon ? 0 : 1, s, round_fb, nullptr, dense));
         const double t_enq = ipa_trace ? tnow() : 0;
         TRH_TRY(msm_finish(curve, s, lrb, 2));
         const double t_fin = ipa_trace ? tnow() : 0;
@@ -617,10 +615,9 @@ int ipa_reserve(int curve, const trh_bases* gw, uint32_t k) {
     if (!c.helper && !c.helper_failed) {  // msm_finish's second Horner thread
         try { c.helper = new HostHelper(); } catch (...) { c.helper_failed = true; }
     }
-    c.msm.reserve_only = true;
-    const int rc = msm_enqueue(curve, sc[5].p, sc[6].p, sc[4].p, m + 2, 2, m + 2, 1, nullptr);
-    c.msm.reserve_only = false;
-    return rc;
+    MsmFlags reserve;
+    reserve.reserve_only = true;
+    return msm_enqueue(curve, sc[5].p, sc[6].p, sc[4].p, m + 2, 2, m + 2, 1, nullptr, nullptr, nullptr, reserve);
 }
 }  // namespace trh
 

@@ -26,32 +26,19 @@
 #include "curve_q4.h"
 #include "hostcombine.h"
 #include "hosthelper.h"
+#include "hostplan.h"
 
 namespace trh {
 
 namespace {
 
-constexpr int MAX_C = 18;
-constexpr int MAX_C_FIXED = 18;  // fixed-base tables: one bucket set per MSM, so wider windows pay
+// the constants the host plan is computed from, the window choice and the plan itself: hostplan.h (checked without a device)
+using hostplan::MAX_C; using hostplan::MAX_C_FIXED; using hostplan::MSM_TILE; using hostplan::SMALL_C; using hostplan::SMALL_MAX_N;
+using hostplan::PART_TILE; using hostplan::BIN_THREADS; using hostplan::BIN_PER_MAX; using hostplan::BIN_CAP_MAX; using hostplan::RANGE_BLOCK;
+using hostplan::HEAVY_PIECES; using hostplan::SP_LISTS; using hostplan::SP_CNT; using hostplan::SP_PAD; using hostplan::SP_PARTS; using hostplan::SP_MAX_CHUNK;
+using hostplan::num_windows;
+static_assert(sizeof(XYZZMem) == hostplan::XYZZ_BYTES && sizeof(XYZZzMem) == hostplan::RAW_POINT_BYTES, "point sizes of the plan's scratch layout");
 constexpr u32 SIGN_BIT = 0x80000000u;
-
-inline int ilog2_floor(size_t n) {
-    int l = 0;
-    while ((n >> (l + 1)) != 0) ++l;
-    return l;
-}
-
-inline int choose_window_bits(size_t n) {
-    int o = ctx().window_override;
-    if (o >= 2 && o <= MAX_C) return o;
-    // measured on MI355X (tools/window_sweep.py): below 2^15 pairs an MSM is latency-bound and the width
-    // hardly matters; from 2^16 the wide windows win (fewer mixed adds, more level-1 sort bins)
-    const int l = ilog2_floor(n ? n : 1);
-    // 2^24 / 2^25: c = 17 (15 full windows + an almost always empty carry window) beats 16 by 3 %; from 2^26 the index
-    // takes 26 of the 31 entry bits, which leaves 5 low bucket bits for the second sort level, and 16 wins again
-    return l < 9 ? 4 : l < 15 ? 8 : l == 15 ? 11 : l == 16 ? 10 : l == 17 ? 12 : l < 20 ? 15 : l < 24 ? 16 : l < 26 ? 17 : 16;
-}
-inline int num_windows(int c) { return 255 / c + 1; }
 
 // ---------------------------------------------------------------------------------------
 // 1. recode: one thread per scalar (grid-stride).  Writes digits[j][i] = bucket | sign << 31
@@ -168,7 +155,6 @@ __global__ void __launch_bounds__(1024) msm_offsets_kernel(u32* __restrict__ cou
 //     workgroup writes ~PART_TILE / nbins consecutive entries per bin.
 //     entry = point index | low k2 bucket bits << idx_bits | sign << 31
 // ---------------------------------------------------------------------------------------
-constexpr int PART_TILE = 16384;
 constexpr int PART_THREADS = 1024;
 __global__ void __launch_bounds__(PART_THREADS) msm_partition_kernel(const u32* __restrict__ digits, u32* __restrict__ bin_cursor,
                                                                      u32* __restrict__ parted, size_t n, int k2, u32 nbins, int idx_bits,
@@ -357,9 +343,6 @@ __global__ void __launch_bounds__(BS_THREADS) msm_bucket_pass_kernel(const u32* 
 //      chunked passes are not needed.  An oversize bin (skewed scalars) flips `oversize` in msm_offsets_kernel and this kernel
 //      returns; the chunked passes below, which return in the other case, then do the work.
 // ---------------------------------------------------------------------------------------
-constexpr int BIN_THREADS = 1024;
-constexpr int BIN_PER_MAX = 36;                        // entries per thread, kept in registers from the load to the last pass
-constexpr u32 BIN_CAP_MAX = BIN_THREADS * BIN_PER_MAX; // 36864 entries
 // (Tried: a stage of half a bin filled in two passes, two 512-thread workgroups per CU so that one loads while the other
 // scatters -- 72 entries per thread spill and the sort went from 1.61 to 2.29 ms at 2^24.  Round 2: a workgroup taking 8 consecutive
 // bins with the NEXT bin's 36 entries per thread in flight in a second register array while the current bin is sorted in the LDS:
@@ -450,7 +433,6 @@ __global__ void __launch_bounds__(BIN_THREADS) msm_bin_sort_kernel(const u32* __
 // per window: exclusive scan of the bucket counts -> starts / ends, cursor (in place of the counts).  Two launches over
 // 1024-bucket blocks (coalesced): block totals, then every block adds the totals before it to its own LDS scan -- one
 // workgroup per window walking 64 buckets per thread was a 0.18 ms latency chain at 2^16 buckets.
-constexpr int RANGE_BLOCK = 1024;
 __global__ void __launch_bounds__(RANGE_BLOCK) msm_bucket_block_sums_kernel(const u32* __restrict__ bucket_cnt, u32* __restrict__ block_sums, u32 nbk,
                                                                             const u32* __restrict__ oversize) {
     if (oversize && oversize[(size_t)blockIdx.z * gridDim.y + blockIdx.y] == 0u) return;
@@ -723,7 +705,6 @@ __global__ void __launch_bounds__(256) msm_accumulate_seg_kernel(const uint4* __
 // (Round 6: holding this kernel to two waves per SIMD costs it nothing -- 14.24 against 14.20 ms at 2^24 -- but the sort and reduction kernels
 // of neighbouring window groups that were to use the freed registers and LDS take their VALU issue slots and memory queue entries from it one
 // for one: 17.7 against 16.9 ms per MSM.  profiles/r06_overlap_ab.txt; the pipeline is in the history at 780c803, not in the library.)
-constexpr u32 HEAVY_PIECES = 64;
 
 // buckets spanning more than HEAVY_PIECES segments (skewed scalars; the short top window of 255-bit
 // scalars): one workgroup per listed bucket, threads stride over the pieces, LDS tree at the end
@@ -1086,14 +1067,9 @@ __global__ void __launch_bounds__(256) msm_table_kernel(const uint4* __restrict_
 //   final     msm_unit_final_kernel: window sum = the partial sums of the lists (+ the tiny column's digit sum, + the pipeline's sum)
 // Same group element, hence the same normalised point; which path a chunk or a column takes is decided by its digits alone.
 // ---------------------------------------------------------------------------------------
-constexpr int SP_LISTS = 16;              // compact lists per column (one counter each: a single counter per column would serialise its 1025 workgroups)
-constexpr int SP_CNT = 2 * SP_LISTS;      // counters per column: the SP_LISTS digit lists, then the SP_LISTS unit lists
-constexpr u32 SP_PAD = 32;                // u32 words between two list counters (one 128-byte line each)
 constexpr u32 SP_TINY = 256;              // a column with at most this many digit entries is summed directly (no sort, no buckets)
-constexpr int SP_PARTS = SP_LISTS + 1;    // partial sums per column: one per unit list, one for the digit entries of a tiny column
 constexpr u32 SP_VOTES = 2;               // sp_count[SP_VOTES] (a spare word of the first counter line): columns of the chunk that vote for the unit path
 constexpr u32 SP_DENSE = 0xFFFFFFFFu;     // counter 0 of a column the sampler found dense
-constexpr size_t SP_MAX_CHUNK = 256;      // items per launch set the pinned read-back area is sized for
 
 // scalar i of item z (the commitment blind for the last one) as canonical words
 template <class SF>
@@ -1357,9 +1333,7 @@ __global__ void __launch_bounds__(256) msm_sparse_remap_kernel(u32* __restrict__
 //             8 + 4 full additions deep instead of 32 for running sums
 // and writes the window sum where msm_finish expects it (host Horner over the 52 windows as for every per-window MSM).
 // ---------------------------------------------------------------------------------------
-constexpr int SMALL_C = 5;
 constexpr u32 SMALL_NBK = 1u << (SMALL_C - 1);  // 16
-constexpr u32 SMALL_MAX_N = 8448;               // LDS: one byte + one u16 per scalar
 struct SmallBias { u32 w[9]; };
 
 template <class BF>
@@ -1494,190 +1468,461 @@ __global__ void __launch_bounds__(256) msm_small_kernel(const uint4* __restrict_
 template <class BF> int msm_finish_t(hipStream_t s, u64* out_xyz, size_t batch);
 template <class BF> int point_sum_host_t(const u64* pts, size_t count, u64* out);
 
-// Above 2^25 pairs the entry index squeezes the second sort level (31 bits = index + low bucket bits) and the rate drops
-// (2^25: 815 M pairs/s, 2^26: 740, 2^27: 490, 2^28: 410): larger MSMs run as equal range tiles of at most 2^25 pairs, each
-// at the full rate; the tiles' points are added on the host (the same sum the range-sharded multi-GPU path forms).
-constexpr size_t MSM_TILE = (size_t)1 << 25;
+// ---------------------------------------------------------------------------------------
+// Host side of one enqueue: msm_enqueue_t routes the call (hostplan::msm_route) to enqueue_tiled, enqueue_small or enqueue_pipeline;
+// the pipeline builds the plan (hostplan::msm_plan), reserves the scratch of that plan and runs its chunks stage by stage.
+// ---------------------------------------------------------------------------------------
+// the arguments of one msm_enqueue call (fb: null when the table does not apply to this shape)
+struct MsmCall {
+    const void *bases_dev, *bases_z, *scalars_dev, *tails_dev;
+    size_t n, batch, stride;
+    int mont;
+    hipStream_t s;
+    const MsmFixedBase* fb;
+    MsmFlags f;
+};
+template <class SF, class BF> int msm_enqueue_t(const MsmCall& a);
+
+// the pinned mirror of the window sums
+int ensure_host_sums(MsmScratch& m, size_t bytes) {
+    if (bytes > m.host_sums_cap) {
+        if (m.host_sums) (void)hipHostFree(m.host_sums);
+        TRH_HIP_TRY(hipHostMalloc(&m.host_sums, bytes + 4096, hipHostMallocDefault));
+        m.host_sums_cap = bytes + 4096;
+    }
+    return TRH_OK;
+}
+
+// what msm_finish needs of the enqueued MSM
+void set_pending(MsmScratch& m, int curve, int windows, int c, const MsmCall& a, bool timed, bool lean) {
+    m.pending_curve = curve; m.pending_windows = windows; m.pending_c = c; m.pending_batch = a.batch; m.pending_stream = a.s; m.pending_owner = nullptr;
+    m.pending_in_tile = a.f.in_tile;
+    m.ev_valid = timed; m.lean_pending = lean;
+}
+
+// equal range tiles of `len` pairs, one after the other through the same scratch (MSM_TILE, hostplan.h)
+template <class SF, class BF>
+int enqueue_tiled(const MsmCall& a, size_t tiles, size_t len) {
+    MsmScratch& m = ctx().msm;
+    MsmCall t = a;
+    t.batch = 1; t.fb = nullptr; t.f.in_tile = true;
+    if (a.f.reserve_only) {  // trh_bases_reserve: the scratch of the longest tile (the first) is what every tile of this MSM needs; nothing to finish
+        t.n = t.stride = len; t.tails_dev = nullptr;
+        return msm_enqueue_t<SF, BF>(t);
+    }
+    m.range_tiles = tiles;
+    u64 acc[24];
+    memset(acc, 0, sizeof(acc));
+    int rc = TRH_OK;
+    for (size_t off = 0; off < a.n && rc == TRH_OK; off += len) {
+        const size_t cur = off + len < a.n ? len : a.n - off;
+        const bool last = off + cur == a.n;
+        t.bases_dev = (const char*)a.bases_dev + off * 64; t.bases_z = a.bases_z ? (const char*)a.bases_z + off * ZREC : nullptr; t.scalars_dev = (const char*)a.scalars_dev + off * 32;
+        t.n = t.stride = cur; t.tails_dev = last ? a.tails_dev : nullptr;
+        rc = msm_enqueue_t<SF, BF>(t);
+        if (rc != TRH_OK || last) break;
+        rc = msm_finish_t<BF>(a.s, acc + 12, 1);  // blocks: the next tile reuses the sort scratch anyway
+        if (rc == TRH_OK) rc = point_sum_host_t<BF>(acc, 2, acc);
+    }
+    if (rc != TRH_OK) return rc;
+    memcpy(m.tile_sum, acc, 96);
+    m.tile_sum_valid = true;
+    m.pending_in_tile = false;  // the last tile's finish is the whole MSM's: it adds the earlier tiles
+    return TRH_OK;
+}
+
+// one launch (msm_small_kernel)
+template <class SF, class BF>
+int enqueue_small(const MsmCall& a) {
+    MsmScratch& m = ctx().msm; hipStream_t s = a.s;
+    const size_t n = a.n, batch = a.batch;
+    const void* bases_z = a.bases_z;
+    const int W = num_windows(SMALL_C);
+    const size_t hs = batch * W * sizeof(XYZZMem);
+    TRH_TRY(m.window_sums.ensure(hs));
+    TRH_TRY(ensure_host_sums(m, hs));
+    if (!bases_z) TRH_TRY(m.bases_z.ensure(n * ZREC + ZREC));
+    if (a.f.reserve_only) return TRH_OK;
+    if (!bases_z) {
+        hipLaunchKernelGGL((msm_convert_bases_kernel<BF>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const uint4*)a.bases_dev, m.bases_z.as<uint4>(), n);
+        bases_z = m.bases_z.p;
+    }
+    SmallBias H{};  // sum over the windows of (2^(c-1) - 1) 2^(c j), 9 x 32 bits
+    for (int j = 0; j < W; ++j) {
+        const u64 v = (u64)(SMALL_NBK - 1) << ((SMALL_C * j) & 31);
+        const int k = (SMALL_C * j) >> 5;
+        if (k < 9) H.w[k] |= (u32)v;
+        if (k + 1 < 9) H.w[k + 1] |= (u32)(v >> 32);
+    }
+    if (opt().reduce_q4)
+        hipLaunchKernelGGL((msm_small_kernel<SF, BF, true>), dim3((unsigned)W, (unsigned)batch), dim3(256), 0, s, (const uint4*)bases_z, (const uint4*)a.scalars_dev, (u32)n, a.mont, a.stride,
+                           (const uint4*)a.tails_dev, H, m.window_sums.as<XYZZMem>());
+    else
+        hipLaunchKernelGGL((msm_small_kernel<SF, BF, false>), dim3((unsigned)W, (unsigned)batch), dim3(256), 0, s, (const uint4*)bases_z, (const uint4*)a.scalars_dev, (u32)n, a.mont, a.stride,
+                           (const uint4*)a.tails_dev, H, m.window_sums.as<XYZZMem>());
+    TRH_HIP_TRY(hipGetLastError());
+    TRH_HIP_TRY(hipMemcpyAsync(m.host_sums, m.window_sums.p, hs, hipMemcpyDeviceToHost, s));
+    set_pending(m, BF::ID, W, SMALL_C, a, false, false);
+    ++m.small_launches;
+    return TRH_OK;
+}
+
+// One pipeline enqueue: the plan, the call, where its scratch lies and what was decided for the whole call.
+struct MsmRun {
+    hostplan::MsmPlan p;
+    MsmCall a;
+    Ctx* c; MsmScratch* m; MsmLane* L;
+    const uint4* bz;                      // the bases the accumulation reads: table, the caller's lazy form, or the converted copy
+    unsigned char* tile_flags;            // regions of L.counts (MsmPlan's layout); tile_flags: fixed-base mode only
+    u32 *oversize, *totals;
+    bool use_bin, lean_sort, sparse_ok, timing;
+    const u32* lean_gate;                 // lean sort: the oversize flags, for the kernels that must do nothing where a bin overflowed; else null
+};
+// One chunk of items [b0, b0 + nb) from the digits to the window sums.
+//   PIPE_PLAIN    recode into the W x n digit space, entry counts read back for batches (adaptive segments)
+//   PIPE_DENSE    the same for columns the sparse classifier has found full-size (no read-back: the slot count is the entry count)
+//   PIPE_COMPACT  the digits are already there -- msm_sparse_emit_kernel's compact arrays of `cap` slots per item with their level-1
+//                 histogram -- and the sorted entries are remapped to flat table indices before the accumulation
+enum { PIPE_PLAIN, PIPE_DENSE, PIPE_COMPACT };
+struct MsmChunk {
+    size_t b0; unsigned nb; int mode;
+    bool compact, zero_fused, bin_sort;
+    size_t nse;                           // slots per item and bucket set
+    u32 entry_most;
+    hostplan::MsmSegments seg;
+};
+
+inline int mark(const MsmRun& r, int k) {  // phase boundary k of a timed run
+    if (r.timing) TRH_HIP_TRY(hipEventRecord(r.m->ev[k], r.a.s));
+    return TRH_OK;
+}
+
+// Every buffer and pinned area a launch of the run's plan needs.  (Not covered by a reservation: size_segments' resized first / last /
+// heavy and the quad reduction's partials in stage_reduce.)
+int reserve_scratch(const MsmRun& r) {
+    const hostplan::MsmPlan& p = r.p; MsmScratch& m = *r.m; MsmLane& L = *r.L;
+    TRH_TRY(L.digits.ensure(p.entries_bytes()));
+    TRH_TRY(L.parted.ensure(p.entries_bytes()));
+    TRH_TRY(L.sorted.ensure(p.entries_bytes()));
+    TRH_TRY(L.counts.ensure(p.counts_bytes()));
+    if (p.adaptive && !r.c->pinned_land) TRH_HIP_TRY(hipHostMalloc(&r.c->pinned_land, 4096, hipHostMallocDefault));  // (>= SP_MAX_CHUNK x 16 windows x 4 B)
+    TRH_TRY(L.bin_starts.ensure(p.bins_bytes(p.chunk)));
+    TRH_TRY(L.starts.ensure(p.ranges_bytes(p.chunk)));
+    TRH_TRY(L.bucket_cnt.ensure(p.ranges_bytes(p.chunk) + 16));
+    TRH_TRY(L.ends.ensure(p.ranges_bytes(p.chunk)));
+    TRH_TRY(L.seg_bucket.ensure(p.seg_bucket_bytes()));
+    TRH_TRY(L.first.ensure(p.pieces_bytes(p.nseg0)));
+    TRH_TRY(L.last.ensure(p.pieces_bytes(p.nseg0)));
+    TRH_TRY(L.direct.ensure(p.direct_bytes()));
+    TRH_TRY(L.heavy.ensure(p.heavy_bytes(p.chunk, p.heavy_stride0) + 16));
+    TRH_TRY(L.buckets.ensure(p.buckets_bytes()));
+    TRH_TRY(L.partials.ensure(p.partials_bytes(p.rblocks)));
+    if (!r.a.bases_z && !r.a.fb) TRH_TRY(m.bases_z.ensure(p.n * ZREC + ZREC));
+    TRH_TRY(m.window_sums.ensure(p.sums_bytes(r.lean_sort)));
+    TRH_TRY(ensure_host_sums(m, p.sums_bytes(r.lean_sort)));
+    if (r.sparse_ok) {
+        TRH_TRY(L.sparse.ensure(p.sparse_bytes()));
+        if (!m.sp_host) TRH_HIP_TRY(hipHostMalloc(&m.sp_host, SP_MAX_CHUNK * SP_CNT * 4 + 4 + SP_MAX_CHUNK + 64, hipHostMallocDefault));
+    }
+    return TRH_OK;
+}
+
+template <class SF>
+int stage_recode(const MsmRun& r, const MsmChunk& ch) {
+    const hostplan::MsmPlan& p = r.p; MsmLane& L = *r.L; hipStream_t s = r.a.s;
+    // small launches (a lone MSM, an IPA round): counts, oversize flags, heavy list and bucket counters cleared by one launch up front instead
+    // of four fill kernels along the way (none of them is written before the kernel that the old memset preceded; adaptive batches keep
+    // the memsets: their heavy list is sized after the read-back)
+    if (ch.zero_fused) {
+        auto up16 = [](size_t b) { return (u32)((b + 15) / 16); };
+        ZeroRanges zr{};
+        // range 0 is the whole counts buffer: bin counts, tile flags, oversize flags, entry totals (the buffers below are allocated 16 bytes
+        // longer than their contents, so that the 16-byte granules of this kernel never leave them)
+        zr.p[0] = (uint4*)L.counts.p; zr.n16[0] = up16(p.counts_used());
+        zr.p[1] = nullptr; zr.n16[1] = 0u;
+        zr.p[2] = (uint4*)L.heavy.p; zr.n16[2] = up16(p.heavy_bytes(ch.nb, p.heavy_stride0));
+        zr.p[3] = (uint4*)L.bucket_cnt.p; zr.n16[3] = up16(p.ranges_bytes(ch.nb));
+        const u32 most = zr.n16[3] > zr.n16[0] ? zr.n16[3] : zr.n16[0];
+        hipLaunchKernelGGL(msm_zero_ranges_kernel, dim3((most + 255) / 256 < 512 ? (most + 255) / 256 : 512), dim3(256), 0, s, zr);
+        TRH_HIP_TRY(hipGetLastError());
+    }
+    if (ch.compact) return TRH_OK;  // the digits are there
+    if (!ch.zero_fused) TRH_HIP_TRY(hipMemsetAsync(L.counts.p, 0, p.fb ? p.oversize_off() : p.bins_bytes(ch.nb), s));  // counts (+ the tile flags behind them)
+    const uint4* sc = (const uint4*)((const char*)r.a.scalars_dev + ch.b0 * r.a.stride * 32);
+    unsigned gb = (unsigned)((p.n + 255) / 256);
+    if (gb > 2048) gb = 2048;
+    hipLaunchKernelGGL((msm_recode_kernel<SF>), dim3(gb, 1, ch.nb), dim3(256), p.recode_use_lds ? p.recode_lds : 0, s, sc, p.n, r.a.mont, p.c, p.W,
+                       L.digits.as<u32>(), L.counts.as<u32>(), p.k2, p.nbins, p.recode_use_lds, r.a.stride, p.fb ? 1 : 0,
+                       r.a.tails_dev ? (const uint4*)r.a.tails_dev + 2 * ch.b0 : nullptr, r.tile_flags, 14u, p.part_tiles);
+    static_assert(PART_TILE == 1 << 14, "tile_log of msm_recode_kernel");
+    return TRH_OK;
+}
+
+// the segments of this chunk: the plan's, or sized to its entries (then with the entry counts read back: one synchronisation)
+int size_segments(const MsmRun& r, MsmChunk& ch, size_t entry_sum) {
+    const hostplan::MsmPlan& p = r.p; MsmLane& L = *r.L; hipStream_t s = r.a.s;
+    ch.seg = p.seg0();
+    bool resize = false;
+    if (ch.mode == PIPE_DENSE) {  // full-size columns: the slot count is the entry count
+        ch.seg = hostplan::msm_segments_dense(p, ch.nb);
+        resize = true;
+    } else if (ch.compact || (p.adaptive && (size_t)ch.nb * p.Ws * 4 <= 4096)) {
+        size_t sum = entry_sum;
+        u32 most = ch.entry_most;
+        if (!ch.compact) {
+            u32* ht = (u32*)r.c->pinned_land;
+            TRH_HIP_TRY(hipMemcpyAsync(ht, r.totals, (size_t)ch.nb * p.Ws * 4, hipMemcpyDeviceToHost, s));
+            TRH_HIP_TRY(hipStreamSynchronize(s));
+            sum = 0; most = 0;
+            for (size_t q = 0; q < (size_t)ch.nb * p.Ws; ++q) { sum += ht[q]; most = ht[q] > most ? ht[q] : most; }
+        }
+        ch.seg = hostplan::msm_segments_counted(p, sum, most);
+        resize = true;
+    }
+    if (resize) {
+        TRH_TRY(L.first.ensure(p.pieces_bytes(ch.seg.nseg)));
+        TRH_TRY(L.last.ensure(p.pieces_bytes(ch.seg.nseg)));
+        TRH_TRY(L.heavy.ensure(p.heavy_bytes(p.chunk, ch.seg.heavy_stride)));
+    }
+    // the fused zeroing cleared nb * heavy_stride0 words up front: it must not be combined with a resized heavy list
+    if (ch.zero_fused && (resize || ch.seg.heavy_stride != p.heavy_stride0)) { set_error("msm: internal error: fused zeroing with resized segments"); return TRH_EINVAL; }
+    return TRH_OK;
+}
+
+template <int P>
+void launch_bin_sort(const MsmRun& r, const MsmChunk& ch) {
+    const hostplan::MsmPlan& p = r.p; MsmLane& L = *r.L;
+    hipLaunchKernelGGL((msm_bin_sort_kernel<P>), dim3(p.nbins, p.Ws, ch.nb), dim3(BIN_THREADS), (size_t)p.bin_cap * 4, r.a.s, L.parted.as<u32>(), L.bin_starts.as<u32>(),
+                       L.counts.as<u32>(), L.sorted.as<u32>(), L.starts.as<u32>(), L.ends.as<u32>(), ch.nse, p.k2, p.nbins, p.idx_bits, p.nbk, r.oversize);
+}
+
+// offsets, segment sizing, partition, then the LDS bin sort and / or the chunked passes; compact lists: remap to table indices
+int stage_sort(const MsmRun& r, MsmChunk& ch, size_t entry_sum) {
+    const hostplan::MsmPlan& p = r.p; MsmScratch& m = *r.m; MsmLane& L = *r.L; hipStream_t s = r.a.s;
+    const unsigned nb = ch.nb; const int Ws = p.Ws; const size_t nse = ch.nse;
+    m.sort_flags = ch.bin_sort ? r.oversize : nullptr; m.sort_flag_count = ch.bin_sort ? nb * (u32)Ws : 0u;
+    if (ch.bin_sort && !ch.zero_fused) TRH_HIP_TRY(hipMemsetAsync(r.oversize, 0, p.set_words_bytes(), s));
+    hipLaunchKernelGGL(msm_offsets_kernel, dim3(Ws, 1, nb), dim3(1024), 0, s, L.counts.as<u32>(), L.bin_starts.as<u32>(), p.nbins, ch.bin_sort ? r.oversize : nullptr, p.bin_cap,
+                       (p.adaptive && ch.mode == PIPE_PLAIN) ? r.totals : nullptr);
+    TRH_TRY(size_segments(r, ch, entry_sum));
+    if (!ch.zero_fused) TRH_HIP_TRY(hipMemsetAsync(L.heavy.p, 0, p.heavy_bytes(nb, ch.seg.heavy_stride), s));
+    hipLaunchKernelGGL(msm_partition_kernel, dim3((unsigned)((nse + PART_TILE - 1) / PART_TILE), Ws, nb), dim3(PART_THREADS), (size_t)PART_TILE * 4 + (size_t)p.nbins * 12, s,
+                       L.digits.as<u32>(), L.counts.as<u32>(), L.parted.as<u32>(), nse, p.k2, p.nbins, p.idx_bits, ch.compact ? (const unsigned char*)nullptr : r.tile_flags);
+    if (ch.bin_sort) {
+        // (entries per thread: the smallest form that holds bin_cap)
+        if (p.bin_cap <= 8u * BIN_THREADS) launch_bin_sort<8>(r, ch);
+        else if (p.bin_cap <= 18u * BIN_THREADS) launch_bin_sort<18>(r, ch);
+        else launch_bin_sort<BIN_PER_MAX>(r, ch);
+    }
+    if (!r.lean_gate) {
+        const dim3 cgrid((unsigned)((nse + BS_CHUNK - 1) / BS_CHUNK), Ws, nb);
+        const u32* gate = ch.bin_sort ? r.oversize : nullptr;  // the chunked passes return at once when the bin sort did the work
+        if (!ch.zero_fused) TRH_HIP_TRY(hipMemsetAsync(L.bucket_cnt.p, 0, p.ranges_bytes(nb), s));
+        hipLaunchKernelGGL((msm_bucket_pass_kernel<false>), cgrid, dim3(BS_THREADS), 0, s, L.parted.as<u32>(), L.bin_starts.as<u32>(), L.counts.as<u32>(),
+                           L.bucket_cnt.as<u32>(), L.sorted.as<u32>(), nse, p.k2, p.nbins, p.idx_bits, p.nbk, gate);
+        // block totals live in seg_bucket, which is only filled afterwards
+        hipLaunchKernelGGL(msm_bucket_block_sums_kernel, dim3(p.range_blocks, Ws, nb), dim3(RANGE_BLOCK), 0, s, L.bucket_cnt.as<u32>(), L.seg_bucket.as<u32>(), p.nbk, gate);
+        hipLaunchKernelGGL(msm_bucket_ranges_kernel, dim3(p.range_blocks, Ws, nb), dim3(RANGE_BLOCK), 0, s, L.bucket_cnt.as<u32>(), L.seg_bucket.as<u32>(), L.starts.as<u32>(),
+                           L.ends.as<u32>(), p.nbk, gate);
+        hipLaunchKernelGGL((msm_bucket_pass_kernel<true>), cgrid, dim3(BS_THREADS), 0, s, L.parted.as<u32>(), L.bin_starts.as<u32>(), L.counts.as<u32>(),
+                           L.bucket_cnt.as<u32>(), L.sorted.as<u32>(), nse, p.k2, p.nbins, p.idx_bits, p.nbk, gate);
+    }
+    if (ch.compact) {
+        unsigned gr = (ch.entry_most + 255) / 256;
+        if (gr > 512) gr = 512;
+        hipLaunchKernelGGL(msm_sparse_remap_kernel, dim3(gr ? gr : 1, nb), dim3(256), 0, s, L.sorted.as<u32>(), L.digits.as<u32>() + (size_t)p.chunk * p.sp_cap, L.ends.as<u32>(), nse, p.nbk);
+    }
+    return TRH_OK;
+}
+
+template <class BF, int G>
+void launch_combine(const MsmRun& r, const MsmChunk& ch) {
+    const hostplan::MsmPlan& p = r.p; MsmLane& L = *r.L;
+    hipLaunchKernelGGL((msm_combine_kernel<BF, G>), dim3((unsigned)(((size_t)p.nbk * G + 255) / 256), p.Ws, ch.nb), dim3(256), 0, r.a.s, L.starts.as<u32>(), L.ends.as<u32>(),
+                       L.first.as<XYZZzMem>(), L.last.as<XYZZzMem>(), L.direct.as<XYZZzMem>(), L.buckets.as<XYZZzMem>(), p.nbk, ch.seg.nseg, ch.seg.seg_len, L.heavy.as<u32>(), ch.seg.heavy_stride,
+                       r.lean_gate);
+}
+
+// one thread per segment, then the pieces of every bucket into its sum
+template <class BF>
+int stage_accumulate(const MsmRun& r, const MsmChunk& ch) {
+    const hostplan::MsmPlan& p = r.p; MsmLane& L = *r.L; hipStream_t s = r.a.s;
+    const unsigned nb = ch.nb;
+    const u32 nbk = p.nbk, nseg = ch.seg.nseg, seg_len = ch.seg.seg_len;
+    if (ch.b0 == 0 && !r.a.bases_z && !r.a.fb)
+        hipLaunchKernelGGL((msm_convert_bases_kernel<BF>), dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, s, (const uint4*)r.a.bases_dev, r.m->bases_z.as<uint4>(), p.n);
+    hipLaunchKernelGGL((msm_accumulate_seg_kernel<BF>), dim3((nseg + 255) / 256, p.Ws, nb), dim3(256), 0, s, r.bz, L.sorted.as<u32>(),
+                       L.ends.as<u32>(), L.first.as<XYZZzMem>(), L.last.as<XYZZzMem>(), L.direct.as<XYZZzMem>(), ch.nse, nbk, nseg, seg_len, r.lean_gate);
+    TRH_TRY(mark(r, 5));
+    const size_t pieces = ch.compact ? 4 : p.ns / ((size_t)nbk * seg_len);  // expected pieces per bucket
+    // measured on the IPA opening at k = 18 (32 pieces per bucket): 24.0 ms with one lane per bucket, 23.0 with 4, 26.1 with 16
+    // (idle lanes of the wider groups still occupy the SIMD)
+    // sparse lists cut into short segments (adaptive): the few buckets that hold anything hold many pieces (an even-bits word column:
+    // 256 buckets of 512 entries = 32 pieces each, added one after the other by one thread: 1.6 ms per batch) while most groups find an
+    // empty bucket and leave at once -- a quarter wave per bucket
+    // (16 lanes per bucket for these: 2^15 buckets x 64 columns x 16 lanes of mostly empty groups cost more than the chains: 3.4 -> 5.4 ms)
+    // quad form only where the caller vouches for uniformly full-size scalars (dense_hint: the IPA's rounds, three or four pieces per bucket):
+    // opening 12.8 -> 12.4 ms; on a lone even-bits column (256 buckets of 32 pieces, which four lanes share better than one quad walks)
+    // it measured 0.52 -> 0.58 ms, full-size and word columns the same
+    if (pieces >= 3 && nbk >= 4 && !ch.compact && opt().reduce_q4 && r.a.f.dense_hint && (size_t)p.Ws * nb <= 8)
+        hipLaunchKernelGGL((msm_combine_q4_kernel<BF>), dim3((unsigned)(((size_t)nbk * 4 + 255) / 256), p.Ws, nb), dim3(256), 0, s, L.starts.as<u32>(), L.ends.as<u32>(),
+                           L.first.as<XYZZzMem>(), L.last.as<XYZZzMem>(), L.direct.as<XYZZzMem>(), L.buckets.as<XYZZzMem>(), nbk, nseg, seg_len, L.heavy.as<u32>(), ch.seg.heavy_stride,
+                           r.lean_gate);
+    else if (pieces >= 3 && nbk >= 4) launch_combine<BF, 4>(r, ch);
+    else launch_combine<BF, 1>(r, ch);
+    hipLaunchKernelGGL((msm_combine_heavy_kernel<BF>), dim3(ch.seg.heavy_blocks, 1, nb), dim3(256), 0, s, L.starts.as<u32>(), L.ends.as<u32>(), L.first.as<XYZZzMem>(),
+                       L.last.as<XYZZzMem>(), L.buckets.as<XYZZzMem>(), nbk, nseg, seg_len, L.heavy.as<u32>(), (u32)p.Ws, ch.seg.heavy_stride);
+    return TRH_OK;
+}
+
+// sum_b b * B_b per bucket set, into the window sums of items [b0, b0 + nb)
+template <class BF>
+int stage_reduce(const MsmRun& r, const MsmChunk& ch) {
+    const hostplan::MsmPlan& p = r.p; MsmScratch& m = *r.m; MsmLane& L = *r.L; hipStream_t s = r.a.s;
+    const unsigned nb = ch.nb; const int Ws = p.Ws; const u32 nbk = p.nbk;
+    u32* const sum_flags = (u32*)((char*)m.window_sums.p + p.sum_flags_off());
+    // compact lists keep the geometry of the plain ones (round 4: shorter slices made their reduction SLOWER -- 1024 threads per item
+    // 0.37 - 0.64 ms per batch of 64, 8192: 0.45 - 1.38: it is bound by its 2 x 2^15 x 64 point additions, not by its depth)
+    const u32 r_tpw = p.tpw, r_slice = p.slice, r_blocks = p.rblocks;
+    // quad-lane form (curve_q4.h) when the launch is ONE latency chain -- at most 8 bucket sets (a lone fixed-base commitment, an IPA
+    // round, a small fixed-base batch) and four lanes per slice within 2^16 lanes (one wave per SIMD).  Measured
+    // (profiles/r05_q4_reduce_ab.txt): IPA k = 18 14.9 -> 13.0 ms, a lone 2^18 commitment 0.71 -> 0.61 ms; with 16 windows the quads
+    // crowd each other out (2^24: reduction 0.43 -> 0.52 ms) and 2^17 lanes lose to 2^16 (IPA 13.9 against 13.0 ms).  Option
+    // reduce_q4 = 0 keeps the one-thread-per-slice kernels everywhere
+    const int q4_knob = opt().reduce_q4;
+    constexpr int q4_lanes_log = 16, q4_sets = 8;  // (16 - 32 sets / 2^17 - 2^19 lanes lose at 2^18 .. 2^22: profiles/r06_q4_small_raw.txt; 2^15 / 2^14 lanes: opening 8.2 -> 8.6 ms)
+    u32 q4_tpw = r_tpw;
+    while (q4_tpw > 1024 && (size_t)q4_tpw * 4 * Ws * nb > ((size_t)1 << q4_lanes_log)) q4_tpw >>= 1;
+    if (q4_knob && !ch.compact && (size_t)Ws * nb <= (size_t)q4_sets && q4_tpw >= 64 && (size_t)q4_tpw * 4 * Ws * nb <= ((size_t)1 << q4_lanes_log) && nbk % q4_tpw == 0) {
+        const u32 q4_blocks = (q4_tpw + 63) / 64;
+        TRH_TRY(L.partials.ensure(p.partials_bytes(q4_blocks)));
+        hipLaunchKernelGGL((msm_reduce_q4_kernel<BF>), dim3(q4_blocks, Ws, nb), dim3(256), 0, s, L.buckets.as<XYZZzMem>(), L.partials.as<XYZZzMem>(), nbk, nbk / q4_tpw, q4_tpw);
+        hipLaunchKernelGGL((msm_window_sum_q4_kernel<BF>), dim3(Ws, 1, nb), dim3(256), 0, s, L.partials.as<XYZZzMem>(), m.window_sums.as<XYZZMem>() + ch.b0 * Ws, q4_blocks,
+                           r.lean_gate, sum_flags, (u32)(nb * Ws));
+    } else {
+        hipLaunchKernelGGL((msm_reduce_kernel<BF>), dim3(r_blocks, Ws, nb), dim3(256), 0, s, L.buckets.as<XYZZzMem>(), L.partials.as<XYZZzMem>(), nbk, r_slice, r_tpw);
+        hipLaunchKernelGGL((msm_window_sum_kernel<BF>), dim3(Ws, 1, nb), dim3(256), 0, s, L.partials.as<XYZZzMem>(), m.window_sums.as<XYZZMem>() + ch.b0 * Ws, r_blocks,
+                           r.lean_gate, sum_flags, (u32)(nb * Ws));
+    }
+    return TRH_OK;
+}
 
 template <class SF, class BF>
-int msm_enqueue_t(const void* bases_dev, const void* bases_z, const void* scalars_dev, size_t n, size_t batch, size_t stride, int mont, hipStream_t s, const MsmFixedBase* fb,
-                  const void* tails_dev) {
-    Ctx& c = ctx();
-    MsmScratch& m = c.msm;
-    MsmLane& L = m.lane;
-    if (fb && (n == 0 || !msm_fixed_base_fits(n, fb->c))) fb = nullptr;
-    if (!m.in_tile) m.tile_sum_valid = false;
-    if (!m.in_tile && !m.reserve_only) m.range_tiles = 0;
-    m.sort_flags = nullptr; m.sort_flag_count = 0;
-    if (!fb && batch == 1 && n > MSM_TILE && !m.in_tile && c.window_override == 0) {
-        const size_t tiles = (n + MSM_TILE - 1) / MSM_TILE, len = (n + tiles - 1) / tiles;
-        if (m.reserve_only) {  // trh_bases_reserve: the scratch of the longest tile (the first) is what every tile of this MSM needs; nothing to finish
-            m.in_tile = true;
-            const int rc = msm_enqueue_t<SF, BF>(bases_dev, bases_z, scalars_dev, len, 1, len, mont, s, nullptr, nullptr);
-            m.in_tile = false;
-            return rc;
-        }
-        m.range_tiles = tiles;
-        u64 acc[24];
-        memset(acc, 0, sizeof(acc));
-        m.in_tile = true;
-        int rc = TRH_OK;
-        for (size_t off = 0; off < n && rc == TRH_OK; off += len) {
-            const size_t cur = off + len < n ? len : n - off;
-            const bool last = off + cur == n;
-            rc = msm_enqueue_t<SF, BF>((const char*)bases_dev + off * 64, bases_z ? (const char*)bases_z + off * ZREC : nullptr, (const char*)scalars_dev + off * 32, cur, 1, cur,
-                                       mont, s, nullptr, last ? tails_dev : nullptr);
-            if (rc != TRH_OK || last) break;
-            rc = msm_finish_t<BF>(s, acc + 12, 1);  // blocks: the next tile reuses the sort scratch anyway
-            if (rc == TRH_OK) rc = point_sum_host_t<BF>(acc, 2, acc);
-        }
-        m.in_tile = false;
-        if (rc != TRH_OK) return rc;
-        memcpy(m.tile_sum, acc, 96);
-        m.tile_sum_valid = true;
-        return TRH_OK;
-    }
-    if (!fb && n != 0 && n <= SMALL_MAX_N && batch <= 4 && c.window_override == 0 && !m.in_tile && !m.force_fallback) {  // one launch (msm_small_kernel)
-        const int W = num_windows(SMALL_C);
-        const size_t hs = batch * W * sizeof(XYZZMem);
-        TRH_TRY(m.window_sums.ensure(hs));
-        if (hs > m.host_sums_cap) {
-            if (m.host_sums) (void)hipHostFree(m.host_sums);
-            TRH_HIP_TRY(hipHostMalloc(&m.host_sums, hs + 4096, hipHostMallocDefault));
-            m.host_sums_cap = hs + 4096;
-        }
-        if (!bases_z) TRH_TRY(m.bases_z.ensure(n * ZREC + ZREC));
-        if (m.reserve_only) return TRH_OK;
-        if (!bases_z) {
-            hipLaunchKernelGGL((msm_convert_bases_kernel<BF>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const uint4*)bases_dev, m.bases_z.as<uint4>(), n);
-            bases_z = m.bases_z.p;
-        }
-        SmallBias H{};  // sum over the windows of (2^(c-1) - 1) 2^(c j), 9 x 32 bits
-        for (int j = 0; j < W; ++j) {
-            const u64 v = (u64)(SMALL_NBK - 1) << ((SMALL_C * j) & 31);
-            const int k = (SMALL_C * j) >> 5;
-            if (k < 9) H.w[k] |= (u32)v;
-            if (k + 1 < 9) H.w[k + 1] |= (u32)(v >> 32);
-        }
-        if (opt().reduce_q4)
-            hipLaunchKernelGGL((msm_small_kernel<SF, BF, true>), dim3((unsigned)W, (unsigned)batch), dim3(256), 0, s, (const uint4*)bases_z, (const uint4*)scalars_dev, (u32)n, mont, stride,
-                               (const uint4*)tails_dev, H, m.window_sums.as<XYZZMem>());
-        else
-            hipLaunchKernelGGL((msm_small_kernel<SF, BF, false>), dim3((unsigned)W, (unsigned)batch), dim3(256), 0, s, (const uint4*)bases_z, (const uint4*)scalars_dev, (u32)n, mont, stride,
-                               (const uint4*)tails_dev, H, m.window_sums.as<XYZZMem>());
-        TRH_HIP_TRY(hipGetLastError());
-        TRH_HIP_TRY(hipMemcpyAsync(m.host_sums, m.window_sums.p, hs, hipMemcpyDeviceToHost, s));
-        m.pending_curve = BF::ID; m.pending_windows = W; m.pending_c = SMALL_C; m.pending_batch = batch; m.pending_stream = s; m.pending_owner = nullptr;
-        m.ev_valid = false; m.lean_pending = false;
-        ++m.small_launches;
-        return TRH_OK;
-    }
-    int cb = fb ? fb->c : choose_window_bits(n);
-    if (!fb) {
-        // beyond 2^27 pairs the index leaves fewer than 4 entry bits for the second sort level; the first level has at most
-        // 2^11 bins (LDS of the partition), so the window narrows with n (15 bits up to 2^28 pairs ... 12 up to 2^31)
-        int ib = 1;
-        while (((size_t)1 << ib) < n) ++ib;
-        const int k2max = 31 - ib < 7 ? 31 - ib : 7;
-        if (cb - 1 - k2max > 11) cb = 12 + k2max;
-    }
-    const int W = fb ? fb->W : num_windows(cb);  // windows of the recoding
-    // fixed-base mode: the W x n digits are one flat list over the W x n table entries -> ONE bucket set
-    const int Ws = fb ? 1 : W;
-    const size_t ns = fb ? (size_t)W * n : n;
-    const u32 nbk = 1u << (cb - 1), nb1 = nbk + 1;
-    // sort geometry: bucket - 1 = bin << k2 | sub; the partitioned entry packs sub above the index
-    int idx_bits = 1;
-    while (((size_t)1 << idx_bits) < ns) ++idx_bits;
-    int k2 = cb - 1 < 7 ? cb - 1 : 7;
-    if (k2 > 31 - idx_bits) k2 = 31 - idx_bits;
-    const int k1 = cb - 1 - k2;
-    const u32 nbins = 1u << k1;
-    const size_t recode_lds = (size_t)Ws * nbins * 4;
-    const int recode_use_lds = recode_lds <= 64 * 1024;
-    // independent batch items (one MSM per column of create_proof, same bases) are processed
-    // `chunk` at a time by the SAME launches (blockIdx.z = item), so the latency-bound sort and
-    // reduction phases of one item are hidden behind the work of the others
-    size_t chunk = batch;
-    {
-        const size_t per_item = (size_t)W * n * 12 + 1;  // digits + parted + sorted dominate
-        // at most 64 items per launch set, inside the scratch budget (option msm_chunk_gb, default 4 GiB per digit array set)
-        const size_t cap = ((size_t)opt().msm_chunk_gb << 30) / per_item;
-        if (chunk > cap) chunk = cap ? cap : 1;
-        if (chunk > 64) chunk = 64;
-        static_assert(64 <= SP_MAX_CHUNK, "chunk size against the pinned read-back area");
-    }
-    // reduce geometry: each thread owns a slice of buckets and pays one short scalar multiplication for
-    // the slice offset, so long slices do less work per bucket but are a long serial chain: a lone MSM
-    // (latency-bound) gets 2048-4096 threads per window, a batch (throughput-bound) as few as 256
-    u32 tpw = nbk >= (1u << 15) ? 4096 : 2048;  // slices of >= 8 buckets (measured: 2^20..2^24 pairs gain 0.07-0.16 ms, 2^18 loses with 4096)
-    if (fb) tpw = 16384;  // one flat window per item: slices of 2 buckets while the batch is small (the cap below takes over for batches) -- the
-                          // opening's rounds are two such items each: reduce 240 -> 190 us per round, k = 18 opening 15.4 -> 14.6 ms
-    while (tpw > 256 && (size_t)Ws * tpw * chunk > ((size_t)1 << 16)) tpw >>= 1;  // 2^16 threads = one wave per SIMD (batch of 64 commits: 0.79 -> 0.62 ms)
-    if (tpw > nbk) tpw = nbk;
-    const u32 slice = nbk / tpw;
-    const u32 rblocks = (tpw + 255) / 256;
-    // segment length: enough segments to fill the chip (>= ~2^18 threads) but at most 128 entries each
-    u32 seg_len0 = 128;
-    // (2^18, round 6: an opening's full-size round -- 2 x 4.2 M digit slots, half of them empty -- takes segments of 32 instead of 16: four pieces per
-    //  bucket for the combine instead of eight, k = 18 opening 8.2 -> 8.0 ms; 2^20 .. 2^22 MSMs and lone commitments unchanged; 2^17 loses: 9.0 ms)
-    while (seg_len0 > 16 && (size_t)W * n * chunk / seg_len0 < ((size_t)1 << 18)) seg_len0 >>= 1;  // W * n == Ws * ns
-    const u32 nseg0 = (u32)((ns + seg_len0 - 1) / seg_len0);
-    // a heavy bucket spans > HEAVY_PIECES segments, so there are fewer than W * nseg / HEAVY_PIECES of them
-    const size_t max_heavy = (size_t)Ws * nseg0 / HEAVY_PIECES + 1;
-    const u32 heavy_stride0 = (u32)(max_heavy + 1);
-    const unsigned heavy_blocks0 = (unsigned)(max_heavy < 256 ? max_heavy : 256);
+int run_chunk(const MsmRun& r, size_t b0, unsigned nb, int mode, size_t entry_sum, u32 entry_most) {
+    MsmChunk ch{};
+    ch.b0 = b0; ch.nb = nb; ch.mode = mode; ch.entry_most = entry_most;
+    ch.compact = mode == PIPE_COMPACT;
+    ch.nse = ch.compact ? (size_t)r.p.sp_cap : r.p.ns;
+    ch.zero_fused = !ch.compact && r.p.batch < 8 && mode != PIPE_DENSE;
+    ch.bin_sort = r.use_bin && !ch.compact;  // compact lists: ~2^11 entries per bin, and a flag column has them all in one: the chunked passes
+    TRH_TRY(mark(r, 0));
+    TRH_TRY(stage_recode<SF>(r, ch));
+    TRH_TRY(mark(r, 1));
+    TRH_TRY(stage_sort(r, ch, entry_sum));
+    TRH_TRY(mark(r, 2));
+    TRH_TRY(stage_accumulate<BF>(r, ch));
+    TRH_TRY(mark(r, 3));
+    TRH_TRY(stage_reduce<BF>(r, ch));
+    return mark(r, 4);
+}
 
-    TRH_TRY(L.digits.ensure(chunk * W * n * 4 + 16));
-    TRH_TRY(L.parted.ensure(chunk * W * n * 4 + 16));
-    TRH_TRY(L.sorted.ensure(chunk * W * n * 4 + 16));
-    // L.counts: [bin counts][fixed-base mode: one byte per (item, partition tile)][oversize-bin flags of the LDS bin sort][entry totals per item and window]
-    const u32 part_tiles = (u32)((ns + PART_TILE - 1) / PART_TILE);
-    const size_t flag_bytes = fb ? ((size_t)chunk * part_tiles + 3) / 4 * 4 : 0;
-    TRH_TRY(L.counts.ensure(chunk * Ws * nbins * 4 + flag_bytes + 2 * chunk * Ws * 4 + 16));
-    unsigned char* const tile_flags = fb ? (unsigned char*)(L.counts.as<u32>() + chunk * Ws * nbins) : nullptr;
-    u32* const oversize = (u32*)((char*)L.counts.p + chunk * Ws * nbins * 4 + flag_bytes);
-    u32* const totals = oversize + chunk * Ws;
-    // Batched commitments of WITNESS columns (flags, small words: a few 10^4 entries per column, most of them in a handful of buckets)
-    // leave the sorted lists almost empty, and fixed 128-entry segments then mean a few hundred threads each walking a serial chain of 128
-    // mixed additions (3 ms per batch of 64 flag columns at k = 18, the chip idle).  For batches the entry counts are read back after the
-    // histogram scan (one synchronisation per chunk, ~20 us) and the segment length is sized to the entries that exist.
-    const bool adaptive = batch >= 8;
-    if (adaptive && !c.pinned_land) TRH_HIP_TRY(hipHostMalloc(&c.pinned_land, 4096, hipHostMallocDefault));  // (>= SP_MAX_CHUNK x 16 windows x 4 B)
-    // LDS bin sort when the bins are big enough to fill a 1024-thread workgroup and fit with 6 % + 512 entries of slack
-    // (uniform digits: the largest of 8192 bins of 2^15 entries is 4.5 sigma = 800 entries above the mean)
-    const size_t avg_bin = ns / nbins;
-    u32 bin_cap = (u32)(((avg_bin + avg_bin / 16 + 512 + 1023) / 1024) * 1024);
-    const bool use_bin = avg_bin >= 4096 && bin_cap <= BIN_CAP_MAX && opt().bin_sort;
-    TRH_TRY(L.bin_starts.ensure(chunk * Ws * nbins * 4));
-    TRH_TRY(L.starts.ensure(chunk * Ws * nb1 * 4));
-    TRH_TRY(L.bucket_cnt.ensure(chunk * Ws * nb1 * 4 + 16));
-    TRH_TRY(L.ends.ensure(chunk * Ws * nb1 * 4));
-    const unsigned range_blocks = (nb1 + RANGE_BLOCK - 1) / RANGE_BLOCK;  // <= 2^17 / 1024 + 1 = 129 < RANGE_BLOCK threads
-    TRH_TRY(L.seg_bucket.ensure(chunk * Ws * range_blocks * 4 + 16));  // block totals of the chunked passes' range scan
-    TRH_TRY(L.first.ensure(chunk * Ws * nseg0 * sizeof(XYZZzMem)));
-    TRH_TRY(L.last.ensure(chunk * Ws * nseg0 * sizeof(XYZZzMem)));
-    TRH_TRY(L.direct.ensure(chunk * Ws * nb1 * sizeof(XYZZzMem)));
-    TRH_TRY(L.heavy.ensure(chunk * heavy_stride0 * 4 + 16));
-    TRH_TRY(L.buckets.ensure(chunk * Ws * nbk * sizeof(XYZZzMem)));
-    TRH_TRY(L.partials.ensure(chunk * Ws * rblocks * sizeof(XYZZzMem)));
-    if (!bases_z && !fb) TRH_TRY(m.bases_z.ensure(n * ZREC + ZREC));
-    const uint4* bz = fb ? (const uint4*)fb->table : bases_z ? (const uint4*)bases_z : m.bases_z.as<uint4>();
+// Fixed-base mode (the commitments of create_proof): the sparse columns of a chunk take the compact pipeline in one pass over the whole
+// chunk (the dense columns' lists are empty there), the dense ones the plain pipeline in runs of consecutive items, which overwrite
+// their window sums.  One synchronisation per chunk either way (the plain path's adaptive read-back is not needed).
+template <class SF, class BF>
+int sparse_chunk(const MsmRun& r, size_t b0, unsigned nb) {
+    const hostplan::MsmPlan& p = r.p; MsmScratch& m = *r.m; MsmLane& L = *r.L; hipStream_t s = r.a.s;
+    const size_t n = p.n, chunk = p.chunk;
+    const u32 sp_subcap = p.sp_subcap, sp_cap = p.sp_cap, nbins = p.nbins;
+    const uint4* sc = (const uint4*)((const char*)r.a.scalars_dev + b0 * r.a.stride * 32);
+    const uint4* tl = r.a.tails_dev ? (const uint4*)r.a.tails_dev + 2 * b0 : nullptr;
+    u32* const sp_count = L.sparse.as<u32>();
+    XYZZzMem* const part = (XYZZzMem*)(sp_count + p.sparse_counter_words());
+    u32* const digits = L.digits.as<u32>();                       // [chunk][cap] compact digits, [chunk][cap] flat table indices, [chunk][cap] unit entries
+    u32* const flat = digits + (size_t)chunk * sp_cap;            // (3 x chunk x W n / 8 x 4 B: three eighths of the buffer)
+    u32* const units = flat + (size_t)chunk * sp_cap;
+    u32* const hc = (u32*)m.sp_host;                       // [nb][SP_CNT] counters, the chunk's votes, then nb class bytes
+    u32* const hvotes = hc + SP_MAX_CHUNK * SP_CNT;
+    unsigned char* const hd = (unsigned char*)(hvotes + 1);
+    TRH_HIP_TRY(hipMemsetAsync(sp_count, 0, (size_t)nb * SP_CNT * SP_PAD * 4, s));
+    hipLaunchKernelGGL((msm_sparse_sample_kernel<SF>), dim3(nb), dim3(256), 0, s, sc, n, r.a.mont, p.c, p.W, r.a.stride, tl, sp_count, 2 * sp_cap);
+    // Measured on the k = 18 proof, chunk by chunk on one box: the compact pipeline alone is no faster than the plain one (word columns
+    // 2.93 against 2.55 ms, sorted / even-bits 2.92 against 3.08, mixed 2.42 against 2.37); what pays is the unit path (flag chunks 0.64 /
+    // 0.96 against 1.64 / 1.82 ms).  So the sampler's vote is read first (one short synchronisation) and a chunk that is not flag-like
+    // goes through the plain pipeline as if the path did not exist.
+    TRH_HIP_TRY(hipMemcpyAsync(hvotes, sp_count + SP_VOTES, 4, hipMemcpyDeviceToHost, s));
+    TRH_HIP_TRY(hipStreamSynchronize(s));
+    if (*hvotes != nb) return run_chunk<SF, BF>(r, b0, nb, PIPE_PLAIN, 0, 0);
+    TRH_HIP_TRY(hipMemsetAsync(digits, 0, (size_t)nb * sp_cap * 4, s));
+    TRH_HIP_TRY(hipMemsetAsync(L.counts.p, 0, (size_t)nb * nbins * 4, s));
+    unsigned gbe = (unsigned)((n + 255) / 256);
+    if (gbe > 1024) gbe = 1024;
+    hipLaunchKernelGGL((msm_sparse_emit_kernel<SF>), dim3(gbe, 1, nb), dim3(256), 0, s, sc, n, r.a.mont, p.c, p.W, r.a.stride, tl, sp_count, digits, flat, units, sp_subcap, L.counts.as<u32>(), p.k2, nbins);
+    // unit path: the lists (and the digit entries of tiny columns) are summed while the host reads the counters; the kernel reads the
+    // chunk's vote and classifies the columns by the same rule as the host below
+    hipLaunchKernelGGL((msm_unit_sum_kernel<BF>), dim3(SP_PARTS, nb), dim3(256), 0, s, r.bz, sp_count, units, digits, flat, sp_subcap, part);
+    TRH_HIP_TRY(hipMemcpy2DAsync(hc, 4, sp_count, SP_PAD * 4, 4, (size_t)nb * SP_CNT, hipMemcpyDeviceToHost, s));
+    TRH_HIP_TRY(hipMemcpyAsync(hvotes, sp_count + SP_VOTES, 4, hipMemcpyDeviceToHost, s));
+    TRH_HIP_TRY(hipStreamSynchronize(s));
+    const int unit_mode = *hvotes == nb;
+    size_t sum = 0;
+    u32 most = 0, n_general = 0, n_neutral = 0, n_dense = 0;
+    for (unsigned z = 0; z < nb; ++z) {
+        const int cls = sp_classify(hc + (size_t)z * SP_CNT, 1, sp_subcap, unit_mode);
+        hd[z] = (unsigned char)cls;
+        size_t cz = 0;
+        for (int g = 0; g < SP_LISTS; ++g) cz += hc[(size_t)z * SP_CNT + g];
+        if (cls == SP_CLASS_DENSE) {
+            ++n_dense;
+            if (hc[(size_t)z * SP_CNT] != SP_DENSE) ++n_neutral;  // it emitted until a list ran full
+        } else if (cls == SP_CLASS_TINY) {
+            if (cz) ++n_neutral;
+        } else {
+            ++n_general; sum += cz; most = cz > most ? (u32)cz : most;
+        }
+    }
+    const bool run_compact = n_general != 0 && most != 0;
+    if (run_compact) {
+        if (n_neutral)  // what the columns that stay out of the compact pipeline appended must not be sorted
+            hipLaunchKernelGGL(msm_sparse_neutralise_kernel, dim3(64, nb), dim3(256), 0, s, sp_count, sp_subcap, digits, (size_t)sp_cap, L.counts.as<u32>(), nbins);
+        TRH_TRY((run_chunk<SF, BF>(r, b0, nb, PIPE_COMPACT, sum, most)));
+    }
+    if (n_dense < nb && (unit_mode || !run_compact))
+        hipLaunchKernelGGL((msm_unit_final_kernel<BF>), dim3(nb), dim3(64), 0, s, sp_count, sp_subcap, part, m.window_sums.as<XYZZMem>() + b0, run_compact ? 1 : 0);
+    for (unsigned z = 0; z < nb;) {  // the dense columns, in runs
+        if (hd[z] != SP_CLASS_DENSE) { ++z; continue; }
+        unsigned e = z + 1;
+        while (e < nb && hd[e] == SP_CLASS_DENSE) ++e;
+        TRH_TRY((run_chunk<SF, BF>(r, b0 + z, e - z, PIPE_DENSE, 0, 0)));
+        z = e;
+    }
+    return TRH_OK;
+}
+
+// recode -> sort -> accumulate -> reduce over the plan of this shape
+template <class SF, class BF>
+int enqueue_pipeline(const MsmCall& a, const hostplan::MsmShape& sh) {
+    MsmRun r{};
+    r.p = hostplan::msm_plan(sh);
+    r.a = a;
+    r.c = &ctx(); r.m = &r.c->msm; r.L = &r.m->lane;
+    const hostplan::MsmPlan& p = r.p; Ctx& c = *r.c; MsmScratch& m = *r.m; hipStream_t s = a.s;
+    const size_t n = a.n, batch = a.batch;
+    r.use_bin = p.use_bin_shape && opt().bin_sort;
     // Lean sort: a caller that vouches for uniformly random scalars (dense_hint: the IPA's rounds) gets the whole-bin LDS sort WITHOUT the four
     // launches of the chunked fallback behind it (they return at once unless a bin overflowed the LDS: 19 us of a round's 680).  The "a bin
     // did overflow" flags travel to the host behind the window sums, and msm_finish repeats the MSM with the fallback when one is set
     // (the scalars must stay as they are until msm_finish: true of every caller that sets dense_hint).
     // (a shape that overflowed before -- k = 16: the 3-bit top window of the c = 14 table puts n / 5 extra entries into each of the buckets 1 .. 4 of
     //  the shared set, every round -- is not tried again: the opening's rounds all have that shape and would each pay the MSM twice)
-    const bool lean_sort = m.dense_hint && !m.force_fallback && use_bin && batch <= chunk && (size_t)batch * Ws <= 256 && n != 0 && !(m.lean_off_n == n && m.lean_off_c == cb);
-    const size_t flag_off = batch * Ws * sizeof(XYZZMem);
-    TRH_TRY(m.window_sums.ensure(flag_off + (lean_sort ? batch * Ws * 4 : 0)));
-    const size_t hs = flag_off + (lean_sort ? batch * Ws * 4 : 0);
-    if (hs > m.host_sums_cap) {
-        if (m.host_sums) (void)hipHostFree(m.host_sums);
-        TRH_HIP_TRY(hipHostMalloc(&m.host_sums, hs + 4096, hipHostMallocDefault));
-        m.host_sums_cap = hs + 4096;
-    }
+    r.lean_sort = a.f.dense_hint && !a.f.force_fallback && r.use_bin && batch <= p.chunk && (size_t)batch * p.Ws <= 256 && n != 0 && !(m.lean_off_n == n && m.lean_off_c == p.c);
+    // unit path (see msm_sparse_emit_kernel): fixed-base mode only (one flat bucket set per item).  Lone commitments ask the sampler too
+    // (tools/lone_sparse_probe.py at k = 18, device scalars: a flag column 0.716 -> 0.417 ms; the vote -- one 12 us kernel and a short
+    // synchronisation -- costs the others 0.02 - 0.06 ms: word 0.629 -> 0.650, even-bits 0.689 -> 0.723, full-size 0.646 -> 0.710; over the
+    // 497 single-call commitments of the literal k = 18 replay 515 -> 460 ms).  The IPA's round MSMs never ask (dense_hint).  The compact pipeline without the unit path loses on a lone commitment (round 4, first half: flag
+    // 0.735 vs 0.719 ms, even-bits 0.791 vs 0.691): a lone MSM's time is its latency chain, not the digit slots
+    r.sparse_ok = opt().sparse && p.sparse_shape_ok && !a.f.dense_hint && !a.f.no_sparse_vote;
+    TRH_TRY(reserve_scratch(r));
     if (!(c.attr_done & ATTR_MSM)) {  // per device
         TRH_HIP_TRY(hipFuncSetAttribute((const void*)msm_bin_sort_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * BIN_THREADS * 4));
         TRH_HIP_TRY(hipFuncSetAttribute((const void*)msm_bin_sort_kernel<18>, hipFuncAttributeMaxDynamicSharedMemorySize, 18 * BIN_THREADS * 4));
@@ -1685,292 +1930,54 @@ int msm_enqueue_t(const void* bases_dev, const void* bases_z, const void* scalar
         TRH_HIP_TRY(hipFuncSetAttribute((const void*)msm_partition_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PART_TILE * 4 + 2048 * 12));
         c.attr_done |= ATTR_MSM;
     }
-    // unit path (see msm_sparse_emit_kernel): fixed-base mode only (one flat bucket set per item).  Lone commitments ask the sampler too
-    // (tools/lone_sparse_probe.py at k = 18, device scalars: a flag column 0.716 -> 0.417 ms; the vote -- one 12 us kernel and a short
-    // synchronisation -- costs the others 0.02 - 0.06 ms: word 0.629 -> 0.650, even-bits 0.689 -> 0.723, full-size 0.646 -> 0.710; over the
-    // 497 single-call commitments of the literal k = 18 replay 515 -> 460 ms).  The IPA's round MSMs never ask (dense_hint).  The compact pipeline without the unit path loses on a lone commitment (round 4, first half: flag
-    // 0.735 vs 0.719 ms, even-bits 0.791 vs 0.691): a lone MSM's time is its latency chain, not the digit slots
-    const bool sparse_ok = opt().sparse && fb && !m.dense_hint && !m.no_sparse_vote && n >= 4096 && ns / 8 / SP_LISTS >= 1024 && c.window_override == 0;
-    if (sparse_ok) {
-        // [counters: chunk x SP_CNT lines][partial sums: chunk x SP_PARTS raw points]
-        TRH_TRY(L.sparse.ensure((size_t)chunk * SP_CNT * SP_PAD * 4 + (size_t)chunk * SP_PARTS * sizeof(XYZZzMem) + 64));
-        if (!m.sp_host) TRH_HIP_TRY(hipHostMalloc(&m.sp_host, SP_MAX_CHUNK * SP_CNT * 4 + 4 + SP_MAX_CHUNK + 64, hipHostMallocDefault));
-    }
-    if (m.reserve_only) return TRH_OK;  // trh_bases_reserve: the buffers above are what a launch of this shape needs
-    const bool timing = c.timing && batch <= chunk && !sparse_ok;  // one pass over the phases
-    if (timing && !m.ev[0]) for (int k = 0; k < 6; ++k) TRH_HIP_TRY(hipEventCreate(&m.ev[k]));
+    if (a.f.reserve_only) return TRH_OK;  // trh_bases_reserve: the buffers above are what a launch of this shape needs
+    r.bz = a.fb ? (const uint4*)a.fb->table : a.bases_z ? (const uint4*)a.bases_z : m.bases_z.as<uint4>();
+    r.tile_flags = a.fb ? (unsigned char*)r.L->counts.p + p.tile_flags_off() : nullptr;
+    r.oversize = (u32*)((char*)r.L->counts.p + p.oversize_off());
+    r.totals = (u32*)((char*)r.L->counts.p + p.totals_off());
+    r.lean_gate = r.lean_sort ? r.oversize : nullptr;  // (lean_sort: dense_hint, so no compact lists -- every chunk of the run is bin-sorted)
+    r.timing = c.timing && batch <= p.chunk && !r.sparse_ok;  // one pass over the phases
+    if (r.timing && !m.ev[0]) for (int k = 0; k < 6; ++k) TRH_HIP_TRY(hipEventCreate(&m.ev[k]));
 
+    const size_t hs = p.sums_bytes(r.lean_sort);
     if (!n) {
         TRH_HIP_TRY(hipMemsetAsync(m.window_sums.p, 0, hs, s));
-        if (timing) for (int k = 0; k <= 5; ++k) TRH_HIP_TRY(hipEventRecord(m.ev[k], s));
+        if (r.timing) for (int k = 0; k <= 5; ++k) TRH_HIP_TRY(hipEventRecord(m.ev[k], s));
     }
-    // One chunk of items [b0, b0 + nb) from the digits to the window sums.
-    //   PIPE_PLAIN    recode into the W x n digit space, entry counts read back for batches (adaptive segments)
-    //   PIPE_DENSE    the same for columns the sparse classifier has found full-size (no read-back: the slot count is the entry count)
-    //   PIPE_COMPACT  the digits are already there -- msm_sparse_emit_kernel's compact arrays of `cap` slots per item with their level-1
-    //                 histogram -- and the sorted entries are remapped to flat table indices before the accumulation
-    enum { PIPE_PLAIN, PIPE_DENSE, PIPE_COMPACT };
-    const u32 sp_subcap = (u32)(ns / 8 / SP_LISTS), sp_cap = sp_subcap * SP_LISTS;  // a column with more than W n / 8 entries is dense
-    auto pipeline = [&](size_t b0, unsigned nb, int mode, size_t entry_sum, u32 entry_most) -> int {
-        const bool compact = mode == PIPE_COMPACT;
-        const size_t nse = compact ? (size_t)sp_cap : ns;  // slots per item and bucket set
-        const uint4* sc = (const uint4*)((const char*)scalars_dev + b0 * stride * 32);
-        if (timing) TRH_HIP_TRY(hipEventRecord(m.ev[0], s));
-        // small launches (a lone MSM, an IPA round): counts, oversize flags, heavy list and bucket counters cleared by one launch up front instead
-        // of four fill kernels along the way (none of them is written before the kernel that the old memset preceded; adaptive batches keep
-        // the memsets: their heavy list is sized after the read-back)
-        const bool zero_fused = !compact && batch < 8 && mode != PIPE_DENSE;
-        if (zero_fused) {
-            auto up16 = [](size_t b) { return (u32)((b + 15) / 16); };
-            ZeroRanges zr{};
-            // range 0 is the whole counts buffer: bin counts, tile flags, oversize flags, entry totals (the buffers below are allocated 16 bytes
-            // longer than their contents, so that the 16-byte granules of this kernel never leave them)
-            zr.p[0] = (uint4*)L.counts.p; zr.n16[0] = up16((size_t)chunk * Ws * nbins * 4 + flag_bytes + 2 * (size_t)chunk * Ws * 4);
-            zr.p[1] = nullptr; zr.n16[1] = 0u;
-            zr.p[2] = (uint4*)L.heavy.p; zr.n16[2] = up16((size_t)nb * heavy_stride0 * 4);
-            zr.p[3] = (uint4*)L.bucket_cnt.p; zr.n16[3] = up16((size_t)nb * Ws * nb1 * 4);
-            const u32 most = zr.n16[3] > zr.n16[0] ? zr.n16[3] : zr.n16[0];
-            hipLaunchKernelGGL(msm_zero_ranges_kernel, dim3((most + 255) / 256 < 512 ? (most + 255) / 256 : 512), dim3(256), 0, s, zr);
-            TRH_HIP_TRY(hipGetLastError());
-        }
-        if (!compact) {
-            if (!zero_fused) TRH_HIP_TRY(hipMemsetAsync(L.counts.p, 0, fb ? (size_t)chunk * Ws * nbins * 4 + flag_bytes : (size_t)nb * Ws * nbins * 4, s));  // counts (+ the tile flags behind them)
-            unsigned gb = (unsigned)((n + 255) / 256);
-            if (gb > 2048) gb = 2048;
-            hipLaunchKernelGGL((msm_recode_kernel<SF>), dim3(gb, 1, nb), dim3(256), recode_use_lds ? recode_lds : 0, s, sc, n, mont, cb, W,
-                               L.digits.as<u32>(), L.counts.as<u32>(), k2, nbins, recode_use_lds, stride, fb ? 1 : 0,
-                               tails_dev ? (const uint4*)tails_dev + 2 * b0 : nullptr, tile_flags, 14u, part_tiles);
-            static_assert(PART_TILE == 1 << 14, "tile_log of msm_recode_kernel");
-        }
-        if (timing) TRH_HIP_TRY(hipEventRecord(m.ev[1], s));
-        const bool bin_sort = use_bin && !compact;  // compact lists: ~2^11 entries per bin, and a flag column has them all in one: the chunked passes
-        m.sort_flags = bin_sort ? oversize : nullptr; m.sort_flag_count = bin_sort ? nb * (u32)Ws : 0u;
-        if (bin_sort && !zero_fused) TRH_HIP_TRY(hipMemsetAsync(oversize, 0, (size_t)chunk * Ws * 4, s));
-        hipLaunchKernelGGL(msm_offsets_kernel, dim3(Ws, 1, nb), dim3(1024), 0, s, L.counts.as<u32>(), L.bin_starts.as<u32>(), nbins, bin_sort ? oversize : nullptr, bin_cap,
-                           (adaptive && mode == PIPE_PLAIN) ? totals : nullptr);
-        u32 seg_len = seg_len0, nseg = nseg0, heavy_stride = heavy_stride0;
-        unsigned heavy_blocks = heavy_blocks0;
-        bool resize = false;
-        if (mode == PIPE_DENSE) {  // full-size columns: the slot count is the entry count
-            seg_len = 128;
-            while (seg_len > 16 && (size_t)W * n * nb / seg_len < ((size_t)1 << 19)) seg_len >>= 1;
-            nseg = (u32)((ns + seg_len - 1) / seg_len);
-            resize = true;
-        } else if (compact || (adaptive && (size_t)nb * Ws * 4 <= 4096)) {
-            size_t sum = entry_sum;
-            u32 most = entry_most;
-            if (!compact) {
-                u32* ht = (u32*)c.pinned_land;
-                TRH_HIP_TRY(hipMemcpyAsync(ht, totals, (size_t)nb * Ws * 4, hipMemcpyDeviceToHost, s));
-                TRH_HIP_TRY(hipStreamSynchronize(s));
-                sum = 0; most = 0;
-                for (size_t q = 0; q < (size_t)nb * Ws; ++q) { sum += ht[q]; most = ht[q] > most ? ht[q] : most; }
-            }
-            // segments for >= 2^17 live threads (round 4, compact lists: 2^16 2.67 / 1.84 / 2.13 / 2.96 / 2.85 ms for the five sparse batches of the k = 18
-            // proof, 2^17 2.37 / 1.85 / 2.03 / 2.88 / 2.88, 2^18 2.34 / 1.71 / 2.06 / 2.98 / 3.05: shorter segments shorten the accumulation's chains and
-            // lengthen the combine's)
-            constexpr int target_log = 17;
-            seg_len = 128;
-            while (seg_len > 16 && sum / seg_len < ((size_t)1 << target_log)) seg_len >>= 1;
-            nseg = (most + seg_len - 1) / seg_len;  // segments beyond the longest list would find nothing
-            if (nseg == 0) nseg = 1;
-            resize = true;
-        }
-        if (resize) {
-            const size_t mh = (size_t)Ws * nseg / HEAVY_PIECES + 1;
-            heavy_stride = (u32)(mh + 1);
-            heavy_blocks = (unsigned)(mh < 256 ? mh : 256);
-            TRH_TRY(L.first.ensure(chunk * Ws * nseg * sizeof(XYZZzMem)));
-            TRH_TRY(L.last.ensure(chunk * Ws * nseg * sizeof(XYZZzMem)));
-            TRH_TRY(L.heavy.ensure(chunk * heavy_stride * 4));
-        }
-        // the fused zeroing cleared nb * heavy_stride0 words up front: it must not be combined with a resized heavy list
-        if (zero_fused && (resize || heavy_stride != heavy_stride0)) { set_error("msm: internal error: fused zeroing with resized segments"); return TRH_EINVAL; }
-        if (!zero_fused) TRH_HIP_TRY(hipMemsetAsync(L.heavy.p, 0, (size_t)nb * heavy_stride * 4, s));
-        hipLaunchKernelGGL(msm_partition_kernel, dim3((unsigned)((nse + PART_TILE - 1) / PART_TILE), Ws, nb), dim3(PART_THREADS), (size_t)PART_TILE * 4 + (size_t)nbins * 12, s,
-                           L.digits.as<u32>(), L.counts.as<u32>(), L.parted.as<u32>(), nse, k2, nbins, idx_bits, compact ? (const unsigned char*)nullptr : tile_flags);
-        {
-            const dim3 cgrid((unsigned)((nse + BS_CHUNK - 1) / BS_CHUNK), Ws, nb);
-            const u32* gate = bin_sort ? oversize : nullptr;  // the chunked passes return at once when the bin sort did the work
-            if (bin_sort) {
-#define TRH_LAUNCH_BIN_SORT(P)                                                                                                                      \
-    hipLaunchKernelGGL((msm_bin_sort_kernel<P>), dim3(nbins, Ws, nb), dim3(BIN_THREADS), (size_t)bin_cap * 4, s, L.parted.as<u32>(), L.bin_starts.as<u32>(), \
-                       L.counts.as<u32>(), L.sorted.as<u32>(), L.starts.as<u32>(), L.ends.as<u32>(), nse, k2, nbins, idx_bits, nbk, oversize)
-                // (entries per thread: the smallest form that holds bin_cap)
-                if (bin_cap <= 8u * BIN_THREADS) TRH_LAUNCH_BIN_SORT(8);
-                else if (bin_cap <= 18u * BIN_THREADS) TRH_LAUNCH_BIN_SORT(18);
-                else TRH_LAUNCH_BIN_SORT(BIN_PER_MAX);
-#undef TRH_LAUNCH_BIN_SORT
-            }
-            if (!(lean_sort && bin_sort)) {
-            if (!zero_fused) TRH_HIP_TRY(hipMemsetAsync(L.bucket_cnt.p, 0, (size_t)nb * Ws * nb1 * 4, s));
-            hipLaunchKernelGGL((msm_bucket_pass_kernel<false>), cgrid, dim3(BS_THREADS), 0, s, L.parted.as<u32>(), L.bin_starts.as<u32>(), L.counts.as<u32>(),
-                               L.bucket_cnt.as<u32>(), L.sorted.as<u32>(), nse, k2, nbins, idx_bits, nbk, gate);
-            // block totals live in seg_bucket, which is only filled afterwards
-            hipLaunchKernelGGL(msm_bucket_block_sums_kernel, dim3(range_blocks, Ws, nb), dim3(RANGE_BLOCK), 0, s, L.bucket_cnt.as<u32>(), L.seg_bucket.as<u32>(), nbk, gate);
-            hipLaunchKernelGGL(msm_bucket_ranges_kernel, dim3(range_blocks, Ws, nb), dim3(RANGE_BLOCK), 0, s, L.bucket_cnt.as<u32>(), L.seg_bucket.as<u32>(), L.starts.as<u32>(),
-                               L.ends.as<u32>(), nbk, gate);
-            hipLaunchKernelGGL((msm_bucket_pass_kernel<true>), cgrid, dim3(BS_THREADS), 0, s, L.parted.as<u32>(), L.bin_starts.as<u32>(), L.counts.as<u32>(),
-                               L.bucket_cnt.as<u32>(), L.sorted.as<u32>(), nse, k2, nbins, idx_bits, nbk, gate);
-            }
-            if (compact) {
-                unsigned gr = (entry_most + 255) / 256;
-                if (gr > 512) gr = 512;
-                hipLaunchKernelGGL(msm_sparse_remap_kernel, dim3(gr ? gr : 1, nb), dim3(256), 0, s, L.sorted.as<u32>(), L.digits.as<u32>() + (size_t)chunk * sp_cap, L.ends.as<u32>(), nse, nbk);
-            }
-        }
-        if (timing) TRH_HIP_TRY(hipEventRecord(m.ev[2], s));
-        if (b0 == 0 && !bases_z && !fb)
-            hipLaunchKernelGGL((msm_convert_bases_kernel<BF>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const uint4*)bases_dev, m.bases_z.as<uint4>(), n);
-        hipLaunchKernelGGL((msm_accumulate_seg_kernel<BF>), dim3((nseg + 255) / 256, Ws, nb), dim3(256), 0, s, bz, L.sorted.as<u32>(),
-                           L.ends.as<u32>(), L.first.as<XYZZzMem>(), L.last.as<XYZZzMem>(), L.direct.as<XYZZzMem>(), nse, nbk, nseg, seg_len,
-                           (lean_sort && bin_sort) ? oversize : (const u32*)nullptr);
-        if (timing) TRH_HIP_TRY(hipEventRecord(m.ev[5], s));
-        {
-            const size_t pieces = compact ? 4 : ns / ((size_t)nbk * seg_len);  // expected pieces per bucket
-#define TRH_LAUNCH_COMBINE(G)                                                                                                                          \
-    hipLaunchKernelGGL((msm_combine_kernel<BF, G>), dim3((unsigned)(((size_t)nbk * G + 255) / 256), Ws, nb), dim3(256), 0, s, L.starts.as<u32>(), L.ends.as<u32>(), \
-                       L.first.as<XYZZzMem>(), L.last.as<XYZZzMem>(), L.direct.as<XYZZzMem>(), L.buckets.as<XYZZzMem>(), nbk, nseg, seg_len, L.heavy.as<u32>(), heavy_stride, \
-                       (lean_sort && bin_sort) ? oversize : (const u32*)nullptr)
-            // measured on the IPA opening at k = 18 (32 pieces per bucket): 24.0 ms with one lane per bucket, 23.0 with 4, 26.1 with 16
-            // (idle lanes of the wider groups still occupy the SIMD)
-            // sparse lists cut into short segments (adaptive): the few buckets that hold anything hold many pieces (an even-bits word column:
-            // 256 buckets of 512 entries = 32 pieces each, added one after the other by one thread: 1.6 ms per batch) while most groups find an
-            // empty bucket and leave at once -- a quarter wave per bucket
-            // (16 lanes per bucket for these: 2^15 buckets x 64 columns x 16 lanes of mostly empty groups cost more than the chains: 3.4 -> 5.4 ms)
-            // quad form only where the caller vouches for uniformly full-size scalars (dense_hint: the IPA's rounds, three or four pieces per bucket):
-            // opening 12.8 -> 12.4 ms; on a lone even-bits column (256 buckets of 32 pieces, which four lanes share better than one quad walks)
-            // it measured 0.52 -> 0.58 ms, full-size and word columns the same
-            if (pieces >= 3 && nbk >= 4 && !compact && opt().reduce_q4 && m.dense_hint && (size_t)Ws * nb <= 8)
-                hipLaunchKernelGGL((msm_combine_q4_kernel<BF>), dim3((unsigned)(((size_t)nbk * 4 + 255) / 256), Ws, nb), dim3(256), 0, s, L.starts.as<u32>(), L.ends.as<u32>(),
-                                   L.first.as<XYZZzMem>(), L.last.as<XYZZzMem>(), L.direct.as<XYZZzMem>(), L.buckets.as<XYZZzMem>(), nbk, nseg, seg_len, L.heavy.as<u32>(), heavy_stride,
-                                   (lean_sort && bin_sort) ? oversize : (const u32*)nullptr);
-            else if (pieces >= 3 && nbk >= 4) TRH_LAUNCH_COMBINE(4);
-            else TRH_LAUNCH_COMBINE(1);
-#undef TRH_LAUNCH_COMBINE
-        }
-        hipLaunchKernelGGL((msm_combine_heavy_kernel<BF>), dim3(heavy_blocks, 1, nb), dim3(256), 0, s, L.starts.as<u32>(), L.ends.as<u32>(), L.first.as<XYZZzMem>(),
-                           L.last.as<XYZZzMem>(), L.buckets.as<XYZZzMem>(), nbk, nseg, seg_len, L.heavy.as<u32>(), (u32)Ws, heavy_stride);
-        if (timing) TRH_HIP_TRY(hipEventRecord(m.ev[3], s));
-        {
-            // compact lists keep the geometry of the plain ones (round 4: shorter slices made their reduction SLOWER -- 1024 threads per item
-            // 0.37 - 0.64 ms per batch of 64, 8192: 0.45 - 1.38: it is bound by its 2 x 2^15 x 64 point additions, not by its depth)
-            const u32 r_tpw = tpw, r_slice = slice, r_blocks = rblocks;
-            // quad-lane form (curve_q4.h) when the launch is ONE latency chain -- at most 8 bucket sets (a lone fixed-base commitment, an IPA
-            // round, a small fixed-base batch) and four lanes per slice within 2^16 lanes (one wave per SIMD).  Measured
-            // (profiles/r05_q4_reduce_ab.txt): IPA k = 18 14.9 -> 13.0 ms, a lone 2^18 commitment 0.71 -> 0.61 ms; with 16 windows the quads
-            // crowd each other out (2^24: reduction 0.43 -> 0.52 ms) and 2^17 lanes lose to 2^16 (IPA 13.9 against 13.0 ms).  Option
-            // reduce_q4 = 0 keeps the one-thread-per-slice kernels everywhere
-            const int q4_knob = opt().reduce_q4;
-            constexpr int q4_lanes_log = 16, q4_sets = 8;  // (16 - 32 sets / 2^17 - 2^19 lanes lose at 2^18 .. 2^22: profiles/r06_q4_small_raw.txt; 2^15 / 2^14 lanes: opening 8.2 -> 8.6 ms)
-            u32 q4_tpw = r_tpw;
-            while (q4_tpw > 1024 && (size_t)q4_tpw * 4 * Ws * nb > ((size_t)1 << q4_lanes_log)) q4_tpw >>= 1;
-            if (q4_knob && !compact && (size_t)Ws * nb <= (size_t)q4_sets && q4_tpw >= 64 && (size_t)q4_tpw * 4 * Ws * nb <= ((size_t)1 << q4_lanes_log) && nbk % q4_tpw == 0) {
-                const u32 q4_blocks = (q4_tpw + 63) / 64;
-                TRH_TRY(L.partials.ensure((size_t)chunk * Ws * q4_blocks * sizeof(XYZZzMem)));
-                hipLaunchKernelGGL((msm_reduce_q4_kernel<BF>), dim3(q4_blocks, Ws, nb), dim3(256), 0, s, L.buckets.as<XYZZzMem>(), L.partials.as<XYZZzMem>(), nbk, nbk / q4_tpw, q4_tpw);
-                hipLaunchKernelGGL((msm_window_sum_q4_kernel<BF>), dim3(Ws, 1, nb), dim3(256), 0, s, L.partials.as<XYZZzMem>(), m.window_sums.as<XYZZMem>() + b0 * Ws, q4_blocks,
-                                   lean_sort ? oversize : (const u32*)nullptr, (u32*)((char*)m.window_sums.p + flag_off), (u32)(nb * Ws));
-            } else {
-            hipLaunchKernelGGL((msm_reduce_kernel<BF>), dim3(r_blocks, Ws, nb), dim3(256), 0, s, L.buckets.as<XYZZzMem>(), L.partials.as<XYZZzMem>(), nbk, r_slice, r_tpw);
-            hipLaunchKernelGGL((msm_window_sum_kernel<BF>), dim3(Ws, 1, nb), dim3(256), 0, s, L.partials.as<XYZZzMem>(), m.window_sums.as<XYZZMem>() + b0 * Ws, r_blocks,
-                               lean_sort ? oversize : (const u32*)nullptr, (u32*)((char*)m.window_sums.p + flag_off), (u32)(nb * Ws));
-            }
-        }
-        if (timing) TRH_HIP_TRY(hipEventRecord(m.ev[4], s));
-        return TRH_OK;
-    };
-
-    // Fixed-base mode (the commitments of create_proof): the sparse columns of a chunk take the compact pipeline in one pass over the whole
-    // chunk (the dense columns' lists are empty there), the dense ones the plain pipeline in runs of consecutive items, which overwrite
-    // their window sums.  One synchronisation per chunk either way (the plain path's adaptive read-back is not needed).
-    auto sparse_chunk = [&](size_t b0, unsigned nb) -> int {
-        const uint4* sc = (const uint4*)((const char*)scalars_dev + b0 * stride * 32);
-        const uint4* tl = tails_dev ? (const uint4*)tails_dev + 2 * b0 : nullptr;
-        u32* const sp_count = L.sparse.as<u32>();
-        XYZZzMem* const part = (XYZZzMem*)(sp_count + (size_t)chunk * SP_CNT * SP_PAD);
-        u32* const digits = L.digits.as<u32>();                       // [chunk][cap] compact digits, [chunk][cap] flat table indices, [chunk][cap] unit entries
-        u32* const flat = digits + (size_t)chunk * sp_cap;            // (3 x chunk x W n / 8 x 4 B: three eighths of the buffer)
-        u32* const units = flat + (size_t)chunk * sp_cap;
-        u32* const hc = (u32*)m.sp_host;                       // [nb][SP_CNT] counters, the chunk's votes, then nb class bytes
-        u32* const hvotes = hc + SP_MAX_CHUNK * SP_CNT;
-        unsigned char* const hd = (unsigned char*)(hvotes + 1);
-        TRH_HIP_TRY(hipMemsetAsync(sp_count, 0, (size_t)nb * SP_CNT * SP_PAD * 4, s));
-        hipLaunchKernelGGL((msm_sparse_sample_kernel<SF>), dim3(nb), dim3(256), 0, s, sc, n, mont, cb, W, stride, tl, sp_count, 2 * sp_cap);
-        // Measured on the k = 18 proof, chunk by chunk on one box: the compact pipeline alone is no faster than the plain one (word columns
-        // 2.93 against 2.55 ms, sorted / even-bits 2.92 against 3.08, mixed 2.42 against 2.37); what pays is the unit path (flag chunks 0.64 /
-        // 0.96 against 1.64 / 1.82 ms).  So the sampler's vote is read first (one short synchronisation) and a chunk that is not flag-like
-        // goes through the plain pipeline as if the path did not exist.
-        TRH_HIP_TRY(hipMemcpyAsync(hvotes, sp_count + SP_VOTES, 4, hipMemcpyDeviceToHost, s));
-        TRH_HIP_TRY(hipStreamSynchronize(s));
-        if (*hvotes != nb) return pipeline(b0, nb, PIPE_PLAIN, 0, 0);
-        TRH_HIP_TRY(hipMemsetAsync(digits, 0, (size_t)nb * sp_cap * 4, s));
-        TRH_HIP_TRY(hipMemsetAsync(L.counts.p, 0, (size_t)nb * nbins * 4, s));
-        unsigned gbe = (unsigned)((n + 255) / 256);
-        if (gbe > 1024) gbe = 1024;
-        hipLaunchKernelGGL((msm_sparse_emit_kernel<SF>), dim3(gbe, 1, nb), dim3(256), 0, s, sc, n, mont, cb, W, stride, tl, sp_count, digits, flat, units, sp_subcap, L.counts.as<u32>(), k2, nbins);
-        // unit path: the lists (and the digit entries of tiny columns) are summed while the host reads the counters; the kernel reads the
-        // chunk's vote and classifies the columns by the same rule as the host below
-        hipLaunchKernelGGL((msm_unit_sum_kernel<BF>), dim3(SP_PARTS, nb), dim3(256), 0, s, bz, sp_count, units, digits, flat, sp_subcap, part);
-        TRH_HIP_TRY(hipMemcpy2DAsync(hc, 4, sp_count, SP_PAD * 4, 4, (size_t)nb * SP_CNT, hipMemcpyDeviceToHost, s));
-        TRH_HIP_TRY(hipMemcpyAsync(hvotes, sp_count + SP_VOTES, 4, hipMemcpyDeviceToHost, s));
-        TRH_HIP_TRY(hipStreamSynchronize(s));
-        const int unit_mode = *hvotes == nb;
-        size_t sum = 0;
-        u32 most = 0, n_general = 0, n_neutral = 0, n_dense = 0;
-        for (unsigned z = 0; z < nb; ++z) {
-            const int cls = sp_classify(hc + (size_t)z * SP_CNT, 1, sp_subcap, unit_mode);
-            hd[z] = (unsigned char)cls;
-            size_t cz = 0;
-            for (int g = 0; g < SP_LISTS; ++g) cz += hc[(size_t)z * SP_CNT + g];
-            if (cls == SP_CLASS_DENSE) {
-                ++n_dense;
-                if (hc[(size_t)z * SP_CNT] != SP_DENSE) ++n_neutral;  // it emitted until a list ran full
-            } else if (cls == SP_CLASS_TINY) {
-                if (cz) ++n_neutral;
-            } else {
-                ++n_general; sum += cz; most = cz > most ? (u32)cz : most;
-            }
-        }
-        const bool run_compact = n_general != 0 && most != 0;
-        if (run_compact) {
-            if (n_neutral)  // what the columns that stay out of the compact pipeline appended must not be sorted
-                hipLaunchKernelGGL(msm_sparse_neutralise_kernel, dim3(64, nb), dim3(256), 0, s, sp_count, sp_subcap, digits, (size_t)sp_cap, L.counts.as<u32>(), nbins);
-            TRH_TRY(pipeline(b0, nb, PIPE_COMPACT, sum, most));
-        }
-        if (n_dense < nb && (unit_mode || !run_compact))
-            hipLaunchKernelGGL((msm_unit_final_kernel<BF>), dim3(nb), dim3(64), 0, s, sp_count, sp_subcap, part, m.window_sums.as<XYZZMem>() + b0, run_compact ? 1 : 0);
-        for (unsigned z = 0; z < nb;) {  // the dense columns, in runs
-            if (hd[z] != SP_CLASS_DENSE) { ++z; continue; }
-            unsigned e = z + 1;
-            while (e < nb && hd[e] == SP_CLASS_DENSE) ++e;
-            TRH_TRY(pipeline(b0 + z, e - z, PIPE_DENSE, 0, 0));
-            z = e;
-        }
-        return TRH_OK;
-    };
-    for (size_t b0 = 0; n && b0 < batch; b0 += chunk) {
-        const unsigned nb = (unsigned)(b0 + chunk <= batch ? chunk : batch - b0);
-        if (sparse_ok) TRH_TRY(sparse_chunk(b0, nb));
-        else TRH_TRY(pipeline(b0, nb, PIPE_PLAIN, 0, 0));
+    for (size_t b0 = 0; n && b0 < batch; b0 += p.chunk) {
+        const unsigned nb = (unsigned)(b0 + p.chunk <= batch ? p.chunk : batch - b0);
+        if (r.sparse_ok) TRH_TRY((sparse_chunk<SF, BF>(r, b0, nb)));
+        else TRH_TRY((run_chunk<SF, BF>(r, b0, nb, PIPE_PLAIN, 0, 0)));
     }
     TRH_HIP_TRY(hipGetLastError());
     TRH_HIP_TRY(hipMemcpyAsync(m.host_sums, m.window_sums.p, hs, hipMemcpyDeviceToHost, s));
-    m.pending_curve = BF::ID;
-    m.pending_windows = Ws;
-    m.pending_c = cb;
-    m.pending_batch = batch;
-    m.pending_stream = s;
-    m.pending_owner = nullptr;
-    m.ev_valid = timing;
-    m.lean_pending = lean_sort;
-    if (lean_sort) {  // what msm_finish needs to run this MSM again with the chunked passes
-        m.retry.bases_dev = bases_dev; m.retry.bases_z = bases_z; m.retry.scalars_dev = scalars_dev; m.retry.tails_dev = tails_dev;
-        m.retry.n = n; m.retry.batch = batch; m.retry.stride = stride; m.retry.mont = mont;
-        m.retry.has_fb = fb != nullptr;
-        if (fb) m.retry.fb = *fb;
+    set_pending(m, BF::ID, p.Ws, p.c, a, r.timing, r.lean_sort);
+    if (r.lean_sort) {  // what msm_finish needs to run this MSM again with the chunked passes
+        m.retry.bases_dev = a.bases_dev; m.retry.bases_z = a.bases_z; m.retry.scalars_dev = a.scalars_dev; m.retry.tails_dev = a.tails_dev;
+        m.retry.n = n; m.retry.batch = batch; m.retry.stride = a.stride; m.retry.mont = a.mont;
+        m.retry.has_fb = a.fb != nullptr;
+        if (a.fb) m.retry.fb = *a.fb;
+        m.retry.flags = a.f;
     }
     return TRH_OK;
+}
+
+template <class SF, class BF>
+int msm_enqueue_t(const MsmCall& call) {
+    Ctx& c = ctx();
+    MsmScratch& m = c.msm;
+    MsmCall a = call;
+    if (a.fb && (a.n == 0 || !msm_fixed_base_fits(a.n, a.fb->c))) a.fb = nullptr;
+    if (!a.f.in_tile) m.tile_sum_valid = false;
+    if (!a.f.in_tile && !a.f.reserve_only) m.range_tiles = 0;
+    m.sort_flags = nullptr; m.sort_flag_count = 0;
+    const hostplan::MsmShape sh{a.n, a.batch, a.fb ? a.fb->c : 0, c.window_override, (unsigned)opt().msm_chunk_gb};
+    size_t tiles = 0, len = 0;
+    switch (hostplan::msm_route(sh, a.f.in_tile, a.f.force_fallback, &tiles, &len)) {
+        case hostplan::MSM_ROUTE_TILED: return enqueue_tiled<SF, BF>(a, tiles, len);
+        case hostplan::MSM_ROUTE_SMALL: return enqueue_small<SF, BF>(a);
+        default: return enqueue_pipeline<SF, BF>(a, sh);
+    }
 }
 
 // host: Horner over windows, normalise
@@ -1986,6 +1993,7 @@ int msm_finish_t(hipStream_t s, u64* out_xyz, size_t batch) {
     MsmScratch& m = c.msm;
     if (m.pending_curve != BF::ID || m.pending_batch != batch || m.pending_stream != s) { set_error("msm_finish: no matching MSM enqueued on this context and stream"); return TRH_EINVAL; }
     const int curve_id = m.pending_curve;
+    const bool inner_tile = m.pending_in_tile;
     m.pending_curve = -1;  // whatever happens below, the context is free for the next MSM
     TRH_HIP_TRY(hipStreamSynchronize(s));
     if (m.lean_pending) {  // the lean sort's promise: no bin overflowed the LDS of msm_bin_sort_kernel.  Otherwise: once more, with the chunked passes
@@ -1994,11 +2002,10 @@ int msm_finish_t(hipStream_t s, u64* out_xyz, size_t batch) {
         bool over = false;
         for (size_t q = 0; q < batch * (size_t)m.pending_windows; ++q) over = over || fl[q] != 0;
         if (over) {
-            const bool hint = m.dense_hint;
-            m.force_fallback = true; m.dense_hint = true;
+            MsmFlags again = m.retry.flags;
+            again.force_fallback = true; again.dense_hint = true;
             const int rc = msm_enqueue(curve_id, m.retry.bases_dev, m.retry.bases_z, m.retry.scalars_dev, m.retry.n, m.retry.batch, m.retry.stride, m.retry.mont, s,
-                                       m.retry.has_fb ? &m.retry.fb : nullptr, m.retry.tails_dev);
-            m.force_fallback = false; m.dense_hint = hint;
+                                       m.retry.has_fb ? &m.retry.fb : nullptr, m.retry.tails_dev, again);
             m.pending_curve = -1;
             TRH_TRY(rc);
             TRH_HIP_TRY(hipStreamSynchronize(s));
@@ -2041,7 +2048,7 @@ int msm_finish_t(hipStream_t s, u64* out_xyz, size_t batch) {
     }
     c.last.window_bits = m.pending_c;
     c.last.windows = m.pending_windows;
-    if (m.tile_sum_valid && !m.in_tile) {  // last tile of a tiled MSM: add the earlier tiles
+    if (m.tile_sum_valid && !inner_tile) {  // last tile of a tiled MSM: add the earlier tiles
         u64 two[24];
         memcpy(two, m.tile_sum, 96);
         memcpy(two + 12, out_xyz, 96);
@@ -2070,10 +2077,7 @@ int point_sum_host_t(const u64* pts, size_t count, u64* out) {
 size_t msm_small_max_pairs() { return SMALL_MAX_N; }
 int msm_fixed_base_windows(int c) { return num_windows(c); }
 // the partitioned entries pack 7 low bucket bits above the flat table index
-bool msm_fixed_base_fits(size_t n, int c) {
-    if (c < 2 || c > MAX_C_FIXED) return false;
-    return (size_t)num_windows(c) * n <= ((size_t)1 << 24);
-}
+bool msm_fixed_base_fits(size_t n, int c) { return hostplan::msm_fixed_base_fits(n, c); }
 int msm_build_table(int curve, const void* bases_dev, size_t n, int c, void* table_dev, hipStream_t s) {
     if (!n) return TRH_OK;
     const int W = num_windows(c);
@@ -2084,10 +2088,11 @@ int msm_build_table(int curve, const void* bases_dev, size_t n, int c, void* tab
     return TRH_OK;
 }
 int msm_enqueue(int curve, const void* bases_dev, const void* bases_z, const void* scalars_dev, size_t n, size_t batch, size_t stride, int mont, hipStream_t s, const MsmFixedBase* fb,
-                const void* tails_dev) {
+                const void* tails_dev, MsmFlags flags) {
+    const MsmCall a{bases_dev, bases_z, scalars_dev, tails_dev, n, batch, stride, mont, s, fb, flags};
     // pallas: base Fp, scalar Fq; vesta: base Fq, scalar Fp
-    if (curve == TRH_PALLAS) return msm_enqueue_t<FqParams, FpParams>(bases_dev, bases_z, scalars_dev, n, batch, stride, mont, s, fb, tails_dev);
-    return msm_enqueue_t<FpParams, FqParams>(bases_dev, bases_z, scalars_dev, n, batch, stride, mont, s, fb, tails_dev);
+    if (curve == TRH_PALLAS) return msm_enqueue_t<FqParams, FpParams>(a);
+    return msm_enqueue_t<FpParams, FqParams>(a);
 }
 int msm_convert_bases(int curve, const void* in_dev, void* out_dev, size_t n, hipStream_t s) {
     if (!n) return TRH_OK;
