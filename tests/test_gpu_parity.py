@@ -58,6 +58,47 @@ def test_field_ops_random_vs_cpu(field):
     assert (api.field_op_dev(field, "inv", a[:2048]) == cpu_ref.field_op(field, "inv", a[:2048])).all()
 
 
+def _edge_residues(f):
+    """about forty Montgomery words (memory form, < m) at the edges of the canonical nine-limb 30-bit representation"""
+    m = f.m
+    vals = [0, 1, m - 1, m - 2, 1 << 254, (1 << 254) - 1, f.R, f.R2]
+    for k in range(1, 9):
+        vals += [1 << (30 * k), (1 << (30 * k)) - 1, (1 << (30 * k)) + 1]
+    ones = sum(((1 << 30) - 1) << (60 * k) for k in range(4))  # all-ones limbs alternating with zero limbs
+    vals += [(1 << 254) - 1 - ones, ones, ones << 30, (1 << 240) - 1, ((1 << 30) - 1) << 210, ((1 << 254) - 1) ^ ((1 << 120) - 1)]
+    vals = sorted(set(vals))
+    assert all(0 <= v < m for v in vals) and 35 <= len(vals) <= 45
+    return vals
+
+
+@pytest.mark.parametrize("field", FIELDS)
+def test_field_ops_edge_cross_product(field):
+    """the canonical domain (Fe, ops of trh_field_op_dev) over the full cross product of an edge set of Montgomery words -- a = b and
+    a = m - b among the pairs -- against big integers; the known-answer file pairs its edge values row by row only"""
+    f = o.FIELDS[field]
+    m = f.m
+    vals = _edge_residues(f)
+    vals += [m - v for v in vals if v and (m - v) not in vals]
+    rinv = pow(f.R, -1, m)
+    to_rows = lambda xs: np.array([o.int_to_limbs(x) for x in xs], dtype=np.uint64)
+    av = [a for a in vals for _ in vals]
+    bv = [b for _ in vals for b in vals]
+    assert any(a == b for a, b in zip(av, bv)) and any(a and a == m - b for a, b in zip(av, bv))
+    a, b = to_rows(av), to_rows(bv)
+    for op, fn in (("add", lambda x, y: (x + y) % m), ("sub", lambda x, y: (x - y) % m), ("mul", lambda x, y: x * y * rinv % m)):
+        got = api.field_op_dev(field, op, a, b)
+        want = to_rows([fn(x, y) for x, y in zip(av, bv)])
+        bad = np.nonzero((got != want).any(axis=1))[0]
+        assert bad.size == 0, f"{op}[{field}]: {bad.size} pairs, first a={av[bad[0]]:#x} b={bv[bad[0]]:#x}"
+    u = to_rows(vals)
+    for op, fn in (("sqr", lambda x: x * x * rinv % m), ("neg", lambda x: (-x) % m), ("from_mont", lambda x: x * rinv % m),
+                   ("to_mont", lambda x: x * f.R % m), ("inv", lambda x: pow(x * rinv % m, -1, m) * f.R % m if x else 0)):
+        got = api.field_op_dev(field, op, u)
+        want = to_rows([fn(x) for x in vals])
+        bad = np.nonzero((got != want).any(axis=1))[0]
+        assert bad.size == 0, f"{op}[{field}]: {bad.size} values, first a={vals[bad[0]]:#x}"
+
+
 @pytest.mark.parametrize("curve", CURVES)
 def test_point_ops_golden(curve):
     kat = load_json("curve_kat.json")[curve]

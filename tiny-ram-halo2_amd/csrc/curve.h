@@ -167,8 +167,9 @@ template <class F> TRH_HD XYZZ<F> xyzz_from_jacobian(const Jacobian<F>& j) {
 
 // ---------------------------------------------------------------------------------------
 // Lazy-domain points (field.h "Signed lazy domain with 29-bit limbs"): the MSM's bucket arithmetic.
-// Coordinates are NORMALISED Fy values (signed, |x| < 4 m, |y| < 1.5 m, zz, zzz in (-0.02 m, 1.02 m) -- loose enough: the
-// arithmetic tolerates 16 m); identity <=> zz is exactly zero.  AffineZ coordinates are in [0, 1.01 m); identity <=> x and y
+// Coordinates are NORMALISED Fy values (signed, |x| < 4 m, |y| < 1.5 m, zz, zzz in (-1.02 m, 1.02 m): fy_one is positive, every
+// product lies in (-|a b| / 2^261 - m, |a b| / 2^261], so an accumulator's zz, zzz are negative after its first addition -- loose enough:
+// the arithmetic tolerates 16 m, and tests/lazy29_gen.py feeds every formula both signs); identity <=> zz is exactly zero.  AffineZ coordinates are in [0, 1.01 m); identity <=> x and y
 // exactly zero.  Differences that only feed one multiplication stay lazy (no carry chain), and every y3 = A B - C D shares one
 // Montgomery reduction (fy_mul2).  The exceptional cases of the full addition (P + P, P + (-P)) are a doubling / the identity in this domain too.
 // ---------------------------------------------------------------------------------------
