@@ -441,10 +441,12 @@ int sort_columns(Scratch& sc, size_t n, u32 cols, bool general, u64* varies, int
     return TRH_OK;
 }
 
-// `batch` lookups at once; general: the all-limbs sort (the redo of a lookup whose fast sort met a tie between different values)
+// `batch` lookups at once; general: the all-limbs sort (the redo of a lookup whose fast sort met a tie between different values).
+// tie_out[l] = 1: the fast sort of lookup l left a tie (its columns and its missing flag are not final, the redo decides);
+// missing_out[l] = 1: an input value of lookup l was not found in its table.  The verdict over the flags is the caller's.
 template <class F>
-int lookup_permute_batch_t(const void* inputs, const void* tables, size_t n, size_t stride, u32 batch, void* out_inputs, void* out_tables, bool general, u32* bad_out /* batch, or null */,
-                           hipStream_t s) {
+int lookup_permute_batch_t(const void* inputs, const void* tables, size_t n, size_t stride, u32 batch, void* out_inputs, void* out_tables, bool general, u32* tie_out /* batch */,
+                           u32* missing_out /* batch */, hipStream_t s) {
     Scratch& sc = scratch();
     const u32 cols = 2 * batch;
     const size_t cn = (size_t)cols * n, bn = (size_t)batch * n;
@@ -496,13 +498,8 @@ int lookup_permute_batch_t(const void* inputs, const void* tables, size_t n, siz
     TRH_HIP_TRY(hipMemcpyAsync(sc.host, bad, words * 4, hipMemcpyDeviceToHost, s));
     TRH_HIP_TRY(hipStreamSynchronize(s));
     for (u32 l = 0; l < batch; ++l) {
-        const bool tie = sc.host[l] || sc.host[batch + l];
-        if (bad_out) bad_out[l] = tie ? 1u : 0u;
-        // a tie leaves the order of its members open, so a "missing" verdict of this pass is not final either: the redo decides
-        if (!tie && sc.host[cols + l]) {
-            set_error("lookup_permute: an input value of lookup %u does not occur in its table (halo2: Error::ConstraintSystemFailure)", l);
-            return TRH_EINVAL;
-        }
+        tie_out[l] = (sc.host[l] || sc.host[batch + l]) ? 1u : 0u;
+        missing_out[l] = sc.host[cols + l] ? 1u : 0u;
     }
     return TRH_OK;
 }
@@ -510,22 +507,27 @@ int lookup_permute_batch_t(const void* inputs, const void* tables, size_t n, siz
 template <class F>
 int lookup_permute_all_t(const void* inputs, const void* tables, size_t n, size_t stride, size_t batch, void* out_inputs, void* out_tables, hipStream_t s) {
     // chunks of at most 32 lookups bound the scratch (2^18 rows: 32 lookups = 64 columns = 0.9 GiB)
-    std::vector<u32> bad;
+    std::vector<u32> tie, missing;
     for (size_t b0 = 0; b0 < batch; b0 += 32) {
         const u32 nb = (u32)(batch - b0 < 32 ? batch - b0 : 32);
         const char* in = (const char*)inputs + b0 * stride * 32;
         const char* tb = (const char*)tables + b0 * stride * 32;
         char* oi = (char*)out_inputs + b0 * stride * 32;
         char* ot = (char*)out_tables + b0 * stride * 32;
-        bad.assign(nb, 0);
-        TRH_TRY((lookup_permute_batch_t<F>(in, tb, n, stride, nb, oi, ot, false, bad.data(), s)));
+        tie.assign(nb, 0); missing.assign(nb, 0);
+        TRH_TRY((lookup_permute_batch_t<F>(in, tb, n, stride, nb, oi, ot, false, tie.data(), missing.data(), s)));
+        // in index order, so that the error names the FIRST lookup of the call that fails (halo2 fails at the first in order): a plain
+        // lookup's missing flag is final, a tied one's (rare: two different values share the bits the fast path sorted by) is the redo's
         for (u32 l = 0; l < nb; ++l) {
-            if (!bad[l]) continue;  // rare: two different values share the limb the fast path sorted by
-            const int rc = lookup_permute_batch_t<F>(in + (size_t)l * stride * 32, tb + (size_t)l * stride * 32, n, stride, 1, oi + (size_t)l * stride * 32, ot + (size_t)l * stride * 32, true,
-                                                     nullptr, s);
-            if (rc != TRH_OK) {
-                if (rc == TRH_EINVAL) set_error("lookup_permute: an input value of lookup %zu does not occur in its table (halo2: Error::ConstraintSystemFailure)", b0 + l);
-                return rc;
+            u32 miss = missing[l];
+            if (tie[l]) {
+                u32 tie1 = 0;
+                TRH_TRY((lookup_permute_batch_t<F>(in + (size_t)l * stride * 32, tb + (size_t)l * stride * 32, n, stride, 1, oi + (size_t)l * stride * 32, ot + (size_t)l * stride * 32, true,
+                                                   &tie1, &miss, s)));
+            }
+            if (miss) {
+                set_error("lookup_permute: an input value of lookup %zu does not occur in its table (halo2: Error::ConstraintSystemFailure)", b0 + l);
+                return TRH_EINVAL;
             }
         }
     }
