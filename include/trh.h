@@ -434,6 +434,30 @@ int trh_expr_eval_blocks_dev(trh_expr_t e, const void* const* columns_dev, void*
 int trh_point_fft_dev(int curve, void* points_dev, uint32_t log_n, const uint64_t omega[4],
                       const uint64_t* scale_or_null, void* stream);
 
+/* ---- GroupEncoding / ff::Field::sqrt: the 32-byte compressed points of pasta_curves (`to_bytes` / `from_bytes`) and the field square
+ *      root they need -- what `Params::read` / `Params::write` (halo2_proofs 0.2.0 poly/commitment.rs) and a transcript's read_point /
+ *      write_point are made of.  Encoding: x canonical (not Montgomery), 32 bytes little endian, bit 7 of byte 31 = parity of canonical y;
+ *      the identity is 32 zero bytes.  Invalid: x >= the modulus, x^3 + 5 not a square (x = 0 included).                              */
+/* out[i] = sqrt(a[i]) (n x 4 u64 Montgomery in and out, 16-byte aligned), is_square[i] = 1 / 0.  The root returned is the one whose CANONICAL
+ * value is even (sqrt(0) = 0); a non-square gives 0 and flag 0.  pasta_curves itself promises no particular root.  Every element costs the
+ * same fixed instruction sequence (csrc/fieldsqrt.h).                                                                                  */
+int trh_field_sqrt_dev(int field, const void* a_dev, void* out_dev, void* is_square_dev /* n x u8 */, size_t n, void* stream);
+/* n x 64-byte affine PODs -> n x 32-byte encodings */
+int trh_points_compress_dev(int curve, const void* xy_dev, void* bytes_dev, size_t n, void* stream);
+/* n x 32-byte encodings (4-byte aligned) -> n x 64-byte affine PODs; an invalid encoding gives the all-zero POD and ok[i] = 0 (ok_dev: n x u8, may
+ * be NULL).  Returns TRH_OK when the kernel ran; *first_bad = the smallest invalid index, n when every encoding was valid (synchronises the
+ * stream to read it; NULL = no synchronisation, look at ok_dev)                                                                          */
+int trh_points_decompress_dev(int curve, const void* bytes_dev, void* xy_dev, void* ok_dev_or_null, size_t n, void* stream, uint64_t* first_bad_or_null);
+/* Params::read's inner loop: n encodings in host memory -> an OWNED resident set, exactly as trh_bases_create_* would have made from the decoded
+ * points (same sharding under trh_init_multi, usable with trh_bases_precompute / reserve / every trh_msm*); 32 instead of 64 bytes per point
+ * cross the link.  An invalid encoding: TRH_EINVAL, trh_last_error() names the first bad index, *out untouched, nothing leaked.             */
+int trh_bases_create_compressed(int curve, const uint8_t* bytes_host, size_t n, trh_bases_t* out);
+/* Params::write: bases [offset, offset + n) of a resident set as n x 32 bytes in host memory */
+int trh_bases_download_compressed(trh_bases_t b, size_t offset, size_t n, uint8_t* bytes_host);
+/* host-side, no device needed (like trh_point_sum): a transcript's write_point / read_point of single commitments */
+int trh_point_to_bytes(int curve, const uint64_t xyz[12], uint8_t out[32]);    /* Jacobian in, any Z (Z = 0: the identity) */
+int trh_point_from_bytes(int curve, const uint8_t in[32], uint64_t out_xy[8]); /* TRH_EINVAL on an invalid encoding (out_xy zeroed) */
+
 /* ---- element-wise field / group ops on device memory (parity tests of the device arithmetic;
  *      op: 0 add, 1 sub, 2 mul, 3 sqr, 4 neg, 5 inv, 6 to_mont, 7 from_mont) ------------------ */
 int trh_field_op_dev(int field, int op, const void* a_dev, const void* b_dev, void* out_dev, size_t n, void* stream);

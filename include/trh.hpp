@@ -18,6 +18,7 @@
 #ifndef TRH_HPP
 #define TRH_HPP
 
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
@@ -47,6 +48,7 @@ struct Point { Limbs x, y, z; };         // pasta's Point layout, normalised to 
 enum class Curve : int { Pallas = TRH_PALLAS, Vesta = TRH_VESTA };
 enum class Field : int { Fp = TRH_FP, Fq = TRH_FQ };
 inline Field scalar_field(Curve c) { return c == Curve::Pallas ? Field::Fq : Field::Fp; }
+inline Field base_field(Curve c) { return c == Curve::Pallas ? Field::Fp : Field::Fq; }
 
 // ---- a little host field arithmetic (constants of expressions, checks in the example driver) ---------------
 namespace host {
@@ -163,6 +165,8 @@ public:
     Bases(Curve c, const std::vector<Affine>& xy) {
         check((c == Curve::Pallas ? trh_bases_create_pallas : trh_bases_create_vesta)((const uint64_t*)xy.data(), xy.size(), &h_), "bases_create");
     }
+    // n x 32-byte compressed points (pasta `to_bytes`) in host memory, decoded on the device; Error names the first invalid encoding
+    static Bases from_compressed(Curve c, const uint8_t* bytes, size_t n) { Bases b; check(trh_bases_create_compressed((int)c, bytes, n, &b.h_), "bases_create_compressed"); return b; }
     static Bases generate(Curve c, uint64_t s0, uint64_t d, size_t n) { Bases b; check(trh_bases_generate((int)c, s0, d, 0, n, &b.h_), "bases_generate"); return b; }
     Bases(const Bases&) = delete;
     Bases& operator=(const Bases&) = delete;
@@ -175,6 +179,10 @@ public:
     // setup-time: the calling context's MSM scratch for batches of `batch` MSMs over the first n bases (the first batch then allocates nothing)
     void reserve(size_t n, size_t batch) const { check(trh_bases_reserve(h_, n, batch), "bases_reserve"); }
     std::vector<Affine> download() const { std::vector<Affine> v(len()); check(trh_bases_download(h_, 0, v.size(), (uint64_t*)v.data()), "bases_download"); return v; }
+    std::vector<Affine> download(size_t offset, size_t n) const { std::vector<Affine> v(n); check(trh_bases_download(h_, offset, n, (uint64_t*)v.data()), "bases_download"); return v; }
+    std::vector<uint8_t> download_compressed(size_t offset, size_t n) const {
+        std::vector<uint8_t> v(32 * n); check(trh_bases_download_compressed(h_, offset, n, v.data()), "bases_download_compressed"); return v;
+    }
     Point msm(const std::vector<Limbs>& scalars, size_t offset = 0) const {
         Point out; check(trh_msm(h_, offset, (const uint64_t*)scalars.data(), scalars.size(), 1, (uint64_t*)&out), "msm"); return out;
     }
@@ -197,6 +205,49 @@ public:
         g_ = Bases::generate(c, s0, d, n + 1); g_lagrange_ = Bases::generate(c, s0 + 77, d + 2, n + 1);
         const auto gh = g_.download(); w = gh[n]; u = Bases::generate(c, 4242, 1, 1).download()[0];
         if (fixed_base_tables) precompute();
+    }
+    // Params::read / Params::write (halo2_proofs 0.2.0 poly/commitment.rs): k as u32 little endian, then g[0 .. n), g_lagrange[0 .. n), w, u as
+    // 32-byte compressed points.  read sends the encodings to the device as they are and decodes them there (no host square roots, 32 bytes per
+    // point over the link); an invalid encoding or a short file throws Error.
+    static Params read(Curve c, const std::vector<uint8_t>& file, bool fixed_base_tables = true) {
+        require(file.size() >= 4, "Params::read: the file holds k");
+        const uint32_t k = (uint32_t)file[0] | (uint32_t)file[1] << 8 | (uint32_t)file[2] << 16 | (uint32_t)file[3] << 24;
+        require(k <= 30, "Params::read: k <= 30");
+        Params p;
+        p.curve = c; p.k = k; p.n = (size_t)1 << k;
+        const size_t n = p.n;
+        require(file.size() >= 4 + 32 * (2 * n + 2), "Params::read: the file holds 2 n + 2 points");
+        const uint8_t *g = file.data() + 4, *gl = g + 32 * n, *w = gl + 32 * n, *u = w + 32;
+        std::vector<uint8_t> set(g, g + 32 * n);   // g || w
+        set.insert(set.end(), w, w + 32);
+        p.g_ = Bases::from_compressed(c, set.data(), n + 1);
+        std::copy(gl, gl + 32 * n, set.begin());     // g_lagrange || w
+        p.g_lagrange_ = Bases::from_compressed(c, set.data(), n + 1);
+        p.w = p.g_.download(n, 1)[0];
+        check(trh_point_from_bytes((int)c, u, (uint64_t*)&p.u), "Params::read: u");
+        if (fixed_base_tables) {
+            for (Bases* b : {&p.g_, &p.g_lagrange_}) { try { b->precompute(0); } catch (const Error&) { /* outside the table range: per-window path */ } }
+            try {
+                std::copy(g, g + 32 * n, set.begin());   // g || w || u
+                set.insert(set.end(), u, u + 32);
+                Bases b = Bases::from_compressed(c, set.data(), n + 2);
+                b.precompute(0);
+                p.ipa_ = std::move(b);
+            } catch (const Error&) { /* the opening uses g || w and the per-window path */ }
+        }
+        return p;
+    }
+    std::vector<uint8_t> write() const {
+        std::vector<uint8_t> out{(uint8_t)k, (uint8_t)(k >> 8), (uint8_t)(k >> 16), (uint8_t)(k >> 24)};
+        for (const Bases* b : {&g_, &g_lagrange_}) { const auto e = b->download_compressed(0, n); out.insert(out.end(), e.begin(), e.end()); }
+        const auto we = g_.download_compressed(n, 1);
+        out.insert(out.end(), we.begin(), we.end());
+        const bool u_identity = u.x == Limbs{0, 0, 0, 0} && u.y == Limbs{0, 0, 0, 0};
+        const Point up{u.x, u.y, u_identity ? Limbs{0, 0, 0, 0} : host::one(base_field(curve))};
+        uint8_t ue[32];
+        check(trh_point_to_bytes((int)curve, (const uint64_t*)&up, ue), "point_to_bytes");
+        out.insert(out.end(), ue, ue + 32);
+        return out;
     }
     void precompute() {
         for (Bases* b : {&g_, &g_lagrange_}) { try { b->precompute(0); } catch (const Error&) { /* outside the table range: per-window path */ } }
@@ -232,6 +283,7 @@ public:
     size_t n;
     Affine w{}, u{};
 private:
+    Params() : curve(Curve::Pallas), k(0), n(1) {}  // filled by read()
     Point commit_host(const Bases& b, const std::vector<Limbs>& poly, const Limbs& blind) const {
         require(poly.size() == n, "poly.len() == params.n");
         std::vector<Limbs> sc(poly); sc.push_back(blind);

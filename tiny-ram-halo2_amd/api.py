@@ -184,6 +184,13 @@ _SIGNATURES = {
     "trh_host_alloc": ([ctypes.POINTER(_vp), ctypes.c_size_t], ctypes.c_int),
     "trh_host_free": ([_vp], ctypes.c_int),
     "trh_io_stats": ([ctypes.POINTER(IoStats), ctypes.c_int], ctypes.c_int),
+    "trh_field_sqrt_dev": ([ctypes.c_int, _vp, _vp, _vp, ctypes.c_size_t, _vp], ctypes.c_int),
+    "trh_points_compress_dev": ([ctypes.c_int, _vp, _vp, ctypes.c_size_t, _vp], ctypes.c_int),
+    "trh_points_decompress_dev": ([ctypes.c_int, _vp, _vp, _vp, ctypes.c_size_t, _vp, _u64p], ctypes.c_int),
+    "trh_bases_create_compressed": ([ctypes.c_int, _vp, ctypes.c_size_t, ctypes.POINTER(_vp)], ctypes.c_int),
+    "trh_bases_download_compressed": ([_vp, ctypes.c_size_t, ctypes.c_size_t, _vp], ctypes.c_int),
+    "trh_point_to_bytes": ([ctypes.c_int, _u64p, _vp], ctypes.c_int),
+    "trh_point_from_bytes": ([ctypes.c_int, _vp, _u64p], ctypes.c_int),
     "trh_set_timing": ([ctypes.c_int], ctypes.c_int),
     "trh_last_timing": ([ctypes.POINTER(Timing)], ctypes.c_int),
 }
@@ -517,6 +524,44 @@ def prefix_product_dev(field: str, a_dev, out_dev, n: int, stream=None):
     _check(lib().trh_field_prefix_product_dev(FIELD_ID[field], _devptr(a_dev), _devptr(out_dev), n, stream))
 
 
+# ---------------------------------------------------------------------------------------
+# ff::Field::sqrt and GroupEncoding (the 32-byte compressed points): csrc/fieldsqrt.h, csrc/encoding.hip
+# ---------------------------------------------------------------------------------------
+def field_sqrt_dev(field: str, a_dev, out_dev, is_square_dev, n: int, stream=None):
+    """out[i] = the root of a[i] with an even canonical value (0 for a non-square), is_square[i] = 1 / 0; device memory, n x 4 u64 and n x u8"""
+    _check(lib().trh_field_sqrt_dev(FIELD_ID[field], _devptr(a_dev), _devptr(out_dev), _devptr(is_square_dev), n, stream))
+
+
+def points_compress_dev(curve: str, xy_dev, bytes_dev, n: int, stream=None):
+    """n x 64-byte affine PODs -> n x 32-byte encodings (pasta `to_bytes`), device memory"""
+    _check(lib().trh_points_compress_dev(CURVE_ID[curve], _devptr(xy_dev), _devptr(bytes_dev), n, stream))
+
+
+def points_decompress_dev(curve: str, bytes_dev, xy_dev, n: int, ok_dev=None, stream=None, first_bad: bool = True):
+    """n x 32-byte encodings -> n x 64-byte affine PODs (pasta `from_bytes`; an invalid encoding: all-zero POD, ok[i] = 0).  Returns the
+    smallest invalid index, n when there is none (synchronises the stream); with first_bad=False nothing is read back and None is returned"""
+    fb = ctypes.c_uint64(0)
+    _check(lib().trh_points_decompress_dev(CURVE_ID[curve], _devptr(bytes_dev), _devptr(xy_dev), None if ok_dev is None else _devptr(ok_dev), n, stream,
+                                           ctypes.byref(fb) if first_bad else None))
+    return int(fb.value) if first_bad else None
+
+
+def point_to_bytes(curve: str, xyz) -> bytes:
+    """a Jacobian point (12 limbs, any Z) -> its 32-byte encoding; host-side, no device needed"""
+    p = _c(xyz).reshape(12)
+    out = ctypes.create_string_buffer(32)
+    _check(lib().trh_point_to_bytes(CURVE_ID[curve], _p(p), out))
+    return out.raw
+
+
+def point_from_bytes(curve: str, data: bytes) -> np.ndarray:
+    """a 32-byte encoding -> the 8-limb affine POD (identity: all zero); TrhError on an invalid encoding; host-side, no device needed"""
+    assert len(data) == 32
+    out = np.zeros(8, dtype=np.uint64)
+    _check(lib().trh_point_from_bytes(CURVE_ID[curve], ctypes.c_char_p(bytes(data)), _p(out)))
+    return out
+
+
 def set_timing(on: bool):
     _check(lib().trh_set_timing(1 if on else 0))
 
@@ -547,6 +592,16 @@ class Bases:
         h = _vp()
         fn = lib().trh_bases_create_pallas if curve == "pallas" else lib().trh_bases_create_vesta
         _check(fn(_p(xy), xy.shape[0], ctypes.byref(h)))
+        return cls(curve, h)
+
+    @classmethod
+    def from_compressed(cls, curve: str, data) -> "Bases":
+        """n x 32-byte encodings in host memory (bytes, or a uint8 array) -> a resident set; the points are decoded on the device
+        (trh_bases_create_compressed).  TrhError names the first invalid encoding."""
+        buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        assert buf.size % 32 == 0
+        h = _vp()
+        _check(lib().trh_bases_create_compressed(CURVE_ID[curve], buf.ctypes.data_as(_vp), buf.size // 32, ctypes.byref(h)))
         return cls(curve, h)
 
     @classmethod
@@ -581,6 +636,13 @@ class Bases:
         out = np.empty((n, 8), dtype=np.uint64)
         _check(lib().trh_bases_download(self.handle, offset, n, _p(out)))
         return out
+
+    def download_compressed(self, offset: int = 0, n: int | None = None) -> bytes:
+        """bases [offset, offset + n) as n x 32-byte encodings, encoded on the device (trh_bases_download_compressed)"""
+        n = len(self) - offset if n is None else n
+        out = np.empty(n * 32, dtype=np.uint8)
+        _check(lib().trh_bases_download_compressed(self.handle, offset, n, out.ctypes.data_as(_vp)))
+        return out.tobytes()
 
     def msm(self, scalars, offset: int = 0, montgomery: bool = True) -> np.ndarray:
         s = _c(scalars, 4)

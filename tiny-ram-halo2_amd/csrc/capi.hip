@@ -221,6 +221,7 @@ static void destroy_ctx(Ctx* c) {
             msm_release();
             lookup_release();
             ntt_release_tables();
+            encoding_release();
             for (DevBuf& d : c->ipa) d.release();
             c->io.release();
             stage_release(*c);
@@ -386,7 +387,7 @@ void bases_cache_clear() {
     for (BasesCandidate& c : g_seen) c = BasesCandidate{0, nullptr, 0, 0};
 }
 
-int sharded_create(int curve, const uint64_t* xy_host, uint64_t s0, uint64_t d, uint64_t first, size_t n, trh_bases_t* out);
+int sharded_create(int curve, const uint64_t* xy_host, uint64_t s0, uint64_t d, uint64_t first, size_t n, trh_bases_t* out, const uint8_t* comp = nullptr);
 int msm_sharded(trh_bases* B, size_t offset, const void* scalars, bool scalars_on_host, size_t n, int mont, hipStream_t caller_stream, uint64_t* out);
 
 const void* lazy_bases(trh_bases_t b, size_t offset, hipStream_t s);
@@ -510,8 +511,10 @@ int best_multiexp_host(int curve, const uint64_t* coeffs, const uint64_t* bases,
     return msm_host_tiled(curve, coeffs, bases, nullptr, 0, n, 1, out);
 }
 
-// one resident set on the entered context's device: uploaded from the host, or generated (xy == null)
-int bases_create_local(int curve, const uint64_t* xy, uint64_t s0, uint64_t d, uint64_t first, size_t n, trh_bases_t* out) {
+// one resident set on the entered context's device: uploaded from the host, decoded from 32-byte encodings (comp != null; index_base: the
+// position of comp[0] in the caller's array, for the message that names an invalid one), or generated (xy == null)
+int bases_create_local(int curve, const uint64_t* xy, uint64_t s0, uint64_t d, uint64_t first, size_t n, trh_bases_t* out, const uint8_t* comp = nullptr,
+                       size_t index_base = 0) {
     trh_bases* b = new trh_bases{curve, nullptr, n, true};
     b->owner = &ctx();
     hipError_t e = hipMalloc(&b->d_xy, n * 64 + 64);
@@ -521,6 +524,22 @@ int bases_create_local(int curve, const uint64_t* xy, uint64_t s0, uint64_t d, u
         delete b;
         set_error("bases_create: %s", hipGetErrorString(e));
         return e == hipErrorOutOfMemory ? TRH_ENOMEM : TRH_EHIP;
+    }
+    if (comp) {
+        if (n) {
+            void* d_enc = nullptr;
+            u64 bad = n;
+            int rc = TRH_OK;
+            e = hipMalloc(&d_enc, n * 32);
+            if (e == hipSuccess) e = hipMemcpy(d_enc, comp, n * 32, hipMemcpyHostToDevice);
+            if (e != hipSuccess) { set_error("bases_create_compressed: %s", hipGetErrorString(e)); rc = e == hipErrorOutOfMemory ? TRH_ENOMEM : TRH_EHIP; }
+            if (rc == TRH_OK) rc = points_decompress_device(curve, d_enc, b->d_xy, nullptr, n, 0, &bad);
+            if (d_enc) (void)hipFree(d_enc);
+            if (rc == TRH_OK && bad < n) { set_error("bases_create_compressed: encoding %zu is not a point of the curve", index_base + (size_t)bad); rc = TRH_EINVAL; }
+            if (rc != TRH_OK) { (void)hipFree(b->d_xy); delete b; return rc; }
+        }
+        *out = b;
+        return TRH_OK;
     }
     if (!xy && n) {
         int rc = bases_generate_device(curve, s0, d, first, n, b->d_xy, 0);
@@ -538,7 +557,7 @@ int bases_create_local(int curve, const uint64_t* xy, uint64_t s0, uint64_t d, u
 // on the host (point_sum_host).  No RCCL here: EC addition is not a reduce op, the payload is 96 B per GPU, the result is
 // consumed by the host (transcript), and everything happens inside ONE process -- a collective would only add a rendezvous.
 // (bench.py's process-per-GPU harness does use RCCL's all_gather for the same 96-byte partials: there the ranks are processes.)
-int sharded_create(int curve, const uint64_t* xy_host, uint64_t s0, uint64_t d, uint64_t first, size_t n, trh_bases_t* out) {
+int sharded_create(int curve, const uint64_t* xy_host, uint64_t s0, uint64_t d, uint64_t first, size_t n, trh_bases_t* out, const uint8_t* comp) {
     const size_t G = g_group.size();
     std::unique_ptr<trh_bases> B(new trh_bases{curve, nullptr, n, true});
     B->owner = g_default;
@@ -551,7 +570,7 @@ int sharded_create(int curve, const uint64_t* xy_host, uint64_t s0, uint64_t d, 
         {
             Enter en;
             rc = en.begin(nullptr, g_group[g]);
-            if (rc == TRH_OK) rc = bases_create_local(curve, xy_host ? xy_host + 8 * lo : nullptr, s0, d, first + lo, hi - lo, &sh);
+            if (rc == TRH_OK) rc = bases_create_local(curve, xy_host ? xy_host + 8 * lo : nullptr, s0, d, first + lo, hi - lo, &sh, comp ? comp + 32 * lo : nullptr, lo);
         }
         if (rc != TRH_OK) { for (trh_bases* q : B->shards) trh_bases_destroy(q); return rc; }
         B->shards.push_back(sh);
@@ -855,6 +874,45 @@ static int bases_create(int curve, const uint64_t* xy, size_t n, trh_bases_t* ou
 }
 int trh_bases_create_pallas(const uint64_t* xy, size_t n, trh_bases_t* out) { return bases_create(TRH_PALLAS, xy, n, out); }
 int trh_bases_create_vesta(const uint64_t* xy, size_t n, trh_bases_t* out) { return bases_create(TRH_VESTA, xy, n, out); }
+
+int trh_bases_create_compressed(int curve, const uint8_t* bytes_host, size_t n, trh_bases_t* out) {
+    TRH_TRY(require_init());
+    TRH_TRY(check_curve(curve));
+    if (!out || (n && !bytes_host)) { set_error("bases_create_compressed: null pointer"); return TRH_EINVAL; }
+    trh_bases_t made = nullptr;  // *out is written on success only
+    int rc;
+    if (g_group.size() > 1 && n >= g_shard_min && thread_ctx() == g_default) rc = sharded_create(curve, nullptr, 0, 0, 0, n, &made, bytes_host);
+    else {
+        TRH_ENTER(0);
+        static const uint8_t none[1] = {0};
+        rc = bases_create_local(curve, nullptr, 0, 0, 0, n, &made, n ? bytes_host : none);
+    }
+    if (rc == TRH_OK) *out = made;
+    return rc;
+}
+
+int trh_bases_download_compressed(trh_bases_t b, size_t offset, size_t n, uint8_t* bytes_host) {
+    if (!b || (n && !bytes_host) || offset + n > b->n) { set_error("bases_download_compressed: bad range"); return TRH_EINVAL; }
+    if (!b->shards.empty()) {
+        for (size_t g = 0; g < b->shards.size(); ++g) {
+            const size_t lo = b->shard_off[g] > offset ? b->shard_off[g] : offset;
+            const size_t hi = b->shard_off[g + 1] < offset + n ? b->shard_off[g + 1] : offset + n;
+            if (hi > lo) TRH_TRY(trh_bases_download_compressed(b->shards[g], lo - b->shard_off[g], hi - lo, bytes_host + 32 * (lo - offset)));
+        }
+        return TRH_OK;
+    }
+    if (!n) return TRH_OK;
+    TRH_ENTER_CTX(0, b->owner);
+    void* d_enc = nullptr;
+    TRH_HIP_TRY(hipMalloc(&d_enc, n * 32));
+    int rc = points_compress_device(b->curve, (const char*)b->d_xy + offset * 64, d_enc, n, 0);
+    if (rc == TRH_OK) {
+        hipError_t e = hipMemcpy(bytes_host, d_enc, n * 32, hipMemcpyDeviceToHost);  // ordered behind the kernel on the null stream
+        if (e != hipSuccess) { set_error("bases_download_compressed: %s", hipGetErrorString(e)); rc = TRH_EHIP; }
+    }
+    (void)hipFree(d_enc);
+    return rc;
+}
 
 int trh_bases_wrap_device(int curve, const void* xy_dev, size_t n, trh_bases_t* out) {
     TRH_TRY(check_curve(curve));

@@ -205,6 +205,8 @@ struct Ctx {
     Stage stage;
     DevBuf pfft;  // curve-point FFT work array + twiddle scalars
     DevBuf scan, scan2;  // prefix-product block totals / batch-inversion running products
+    DevBuf sqrt_tab[2];     // fieldsqrt.h's table per field (encoding.hip; uploaded at first use, kept like the twiddle tables)
+    DevBuf enc_first_bad;   // one word: the smallest invalid index of the last decompression
     DevBuf ipa[11];  // vectors of the IPA prover (b, s', p', weights, round scalars, g‖w‖u and its lazy copy, the second halves of the p' / b ping-pong pairs,
                      // the generator fold's buckets and bucket lists -- ipafold.hip), kept across proofs
     DevBuf factors;  // ring of 16 small factor tables for the scale kernels
@@ -361,6 +363,11 @@ int point_sum_host(int curve, const u64* pts, size_t count, u64* out);
 int bases_generate_device(int curve, u64 s0, u64 d, u64 first, size_t n, void* out_dev, hipStream_t s);
 void msm_release();
 void lookup_release();
+// encoding.hip: the 32-byte point encoding on device buffers (bytes: n x 32 B, xy: n x 64 B affine PODs, ok: n bytes or null).  An invalid
+// encoding decodes to the all-zero POD; first_bad (optional) receives the smallest invalid index, n if there is none -- and synchronises s
+int points_decompress_device(int curve, const void* bytes_dev, void* xy_dev, void* ok_dev, size_t n, hipStream_t s, u64* first_bad);
+int points_compress_device(int curve, const void* xy_dev, void* bytes_dev, size_t n, hipStream_t s);
+void encoding_release();
 
 }  // namespace trh
 

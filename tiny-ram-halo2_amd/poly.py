@@ -18,6 +18,7 @@ assertions as the Rust types:
 from __future__ import annotations
 
 import os
+import re
 
 import numpy as np
 
@@ -287,6 +288,76 @@ class Params:
             except api.TrhError:
                 pass
         return self._ipa
+
+    # ---- Params::read / Params::write (halo2_proofs 0.2.0 poly/commitment.rs): k as u32 little endian, then g[0 .. n), g_lagrange[0 .. n), w, u
+    # as 32-byte compressed points (pasta `to_bytes`): 4 + 32 (2 n + 2) bytes ----
+    @classmethod
+    def read(cls, curve: str, fileobj, precompute: bool = True) -> "Params":
+        """Params::read.  The encodings go to the device as they are (32 bytes per point) and are decoded there (api.Bases.from_compressed):
+        no square root runs on the host and no point passes through host memory as a 64-byte POD, except w and u themselves, which the
+        host-side callers of the opening need.  ValueError names the section and index of an invalid encoding."""
+        head = fileobj.read(4)
+        if len(head) != 4:
+            raise ValueError("Params.read: truncated file (no k)")
+        k = int.from_bytes(head, "little")
+        if k > 30:
+            raise ValueError(f"Params.read: k = {k} is not a supported size")
+        n = 1 << k
+        body = fileobj.read(32 * (2 * n + 2))
+        if len(body) != 32 * (2 * n + 2):
+            raise ValueError(f"Params.read: truncated file ({4 + len(body)} bytes, k = {k} needs {4 + 32 * (2 * n + 2)})")
+        body = np.frombuffer(body, dtype=np.uint8)
+        g, gl, w, u = body[:32 * n], body[32 * n:64 * n], body[64 * n:64 * n + 32], body[64 * n + 32:]
+
+        def decode(parts):
+            """the sections back to back as one resident set; an invalid encoding is reported by its own section's name and index"""
+            try:
+                return api.Bases.from_compressed(curve, np.concatenate([a for _, a in parts]))
+            except api.TrhError as e:
+                m = re.search(r"encoding (\d+) is not a point", str(e))
+                if not m:
+                    raise
+                idx = int(m.group(1))
+                for name, a in parts:
+                    if idx < a.size // 32:
+                        raise ValueError(f"Params.read: {name}[{idx}] is not the encoding of a point of {curve}") from e
+                    idx -= a.size // 32
+                raise
+
+        self = cls.__new__(cls)
+        self.curve, self.k, self.n = curve, k, n
+        self._g = decode([("g", g), ("w", w)])
+        self._g_lagrange = decode([("g_lagrange", gl), ("w", w)])
+        self.w = self._g.download(n, 1)
+        self._ipa = None
+        if precompute:
+            for b in (self._g, self._g_lagrange):
+                try:
+                    b.precompute(0)
+                except api.TrhError:
+                    pass
+        gwu = decode([("g", g), ("w", w), ("u", u)])
+        self.u = gwu.download(n + 1, 1).reshape(8)
+        self._ipa = self._g
+        if int(api.lib().trh_bases_precomputed_window_bits(self._g.handle)) != 0:  # as ipa_bases(): only for Params that use tables at all
+            try:
+                gwu.precompute(int(os.environ.get("TRH_IPA_TABLE_BITS", "0")))
+                self._ipa = gwu
+            except api.TrhError:
+                pass
+        return self
+
+    def write(self, fileobj):
+        """Params::write: the resident sets are encoded on the device (api.Bases.download_compressed)"""
+        if getattr(self, "u", None) is None:
+            raise ValueError("Params.write: the file format carries u, and these Params were made without it")
+        u = np.ascontiguousarray(self.u, dtype=np.uint64).reshape(8)
+        one = _mont(api.BASE_FIELD[self.curve], 1) if u.any() else np.zeros(4, dtype=np.uint64)
+        fileobj.write(int(self.k).to_bytes(4, "little"))
+        fileobj.write(self._g.download_compressed(0, self.n))
+        fileobj.write(self._g_lagrange.download_compressed(0, self.n))
+        fileobj.write(self._g.download_compressed(self.n, 1))
+        fileobj.write(api.point_to_bytes(self.curve, np.concatenate([u, one])))
 
     @staticmethod
     def g_lagrange_from_g(curve: str, k: int, g_dev):
