@@ -1,7 +1,8 @@
 """CPU tests of csrc/fieldsqrt.h and of the host-side point encoding (trh_point_to_bytes / trh_point_from_bytes), no GPU.
 fe_sqrt runs in a stand-alone program (tests/native/fieldsqrt_vec_test.cpp) under -fsanitize=undefined over records written here; the
 flag, r^2 = a and the even-root convention are checked against oracle/pasta.py (tests/encoding_cases.py).  The two C-ABI entries run
-through ctypes on a machine without a device, as trh_point_sum does; tests/test_gpu_encoding.py sends the same records through the kernels."""
+through ctypes on a machine without a device, as trh_point_sum does; tests/test_gpu_encoding.py sends the same records through the kernels.
+The id dispatch those entries go through (csrc/dispatch.h) has its own stand-alone program, tests/native/dispatch_test.cpp."""
 import ctypes
 import os
 import random
@@ -54,6 +55,15 @@ def test_fe_sqrt_host_branch_matches_the_oracle(sqrt_exe, tmp_path, field):
     assert raw.shape[0] == len(a)
     bad = ec.check_sqrt(field, raw[:, :32].copy().view(np.uint64), raw[:, 32])
     assert not bad, "\n".join(bad[:20])
+
+
+def test_dispatch_tags_pair_the_fields_with_the_curves(tmp_path):
+    """csrc/dispatch.h (with_field / with_curve) through tests/native/dispatch_test.cpp, built like fieldsqrt_vec_test"""
+    exe = str(tmp_path / "dispatch_test")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-w", "-fsanitize=undefined", "-fno-sanitize-recover=all",
+                           os.path.join(ROOT, "tests", "native", "dispatch_test.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60, env=dict(os.environ, UBSAN_OPTIONS="print_stacktrace=1"))
+    assert r.returncode == 0 and "dispatch: ok" in r.stdout and "runtime error" not in r.stderr, r.stdout + r.stderr
 
 
 def _points(curve, count=64):

@@ -278,6 +278,15 @@ static int create_checked_ctx(int device, Ctx** out) {
     return TRH_OK;
 }
 
+int check_curve(int curve) {
+    if (curve != TRH_PALLAS && curve != TRH_VESTA) { set_error("unknown curve id %d", curve); return TRH_EINVAL; }
+    return TRH_OK;
+}
+int check_field(int field) {
+    if (field != TRH_FP && field != TRH_FQ) { set_error("unknown field id %d", field); return TRH_EINVAL; }
+    return TRH_OK;
+}
+
 namespace {
 
 template <class F>
@@ -340,15 +349,6 @@ __global__ void __launch_bounds__(64) point_op_q4_kernel(int op, const JacobianM
     XYZZz<F> full;
     full.x = q4_perm<F, 0, 0, 0, 0>(r); full.y = q4_perm<F, 1, 1, 1, 1>(r); full.zz = q4_perm<F, 2, 2, 2, 2>(r); full.zzz = q4_perm<F, 3, 3, 3, 3>(r);
     if (q == 0) jac_store(jac_from_affine(xyzz_to_affine(xyzzz_to_canonical(full))), out[i]);
-}
-
-int check_curve(int curve) {
-    if (curve != TRH_PALLAS && curve != TRH_VESTA) { set_error("unknown curve id %d", curve); return TRH_EINVAL; }
-    return TRH_OK;
-}
-int check_field(int field) {
-    if (field != TRH_FP && field != TRH_FQ) { set_error("unknown field id %d", field); return TRH_EINVAL; }
-    return TRH_OK;
 }
 
 // ---- cache of base sets seen by the host-pointer entry points ---------------------------------------------------
@@ -1212,8 +1212,7 @@ int trh_field_op_dev(int field, int op, const void* a, const void* b, void* out,
     TRH_ENTER(stream);
     if (!n) return TRH_OK;
     const unsigned gb = (unsigned)((n + 255) / 256);
-    if (field == TRH_FP) hipLaunchKernelGGL((field_op_kernel<FpParams>), dim3(gb), dim3(256), 0, (hipStream_t)stream, op, (const uint4*)a, (const uint4*)b, (uint4*)out, n);
-    else hipLaunchKernelGGL((field_op_kernel<FqParams>), dim3(gb), dim3(256), 0, (hipStream_t)stream, op, (const uint4*)a, (const uint4*)b, (uint4*)out, n);
+    with_field(field, [&](auto f) { hipLaunchKernelGGL((field_op_kernel<decltype(f)>), dim3(gb), dim3(256), 0, (hipStream_t)stream, op, (const uint4*)a, (const uint4*)b, (uint4*)out, n); });
     TRH_HIP_TRY(hipGetLastError());
     return TRH_OK;
 }
@@ -1223,14 +1222,12 @@ int trh_point_op_dev(int curve, int op, const void* p, const void* q, void* out,
     if (!n) return TRH_OK;
     if (op == 3 || op == 4) {
         const unsigned gq = (unsigned)((n * 4 + 63) / 64);
-        if (curve == TRH_PALLAS) hipLaunchKernelGGL((point_op_q4_kernel<FpParams>), dim3(gq), dim3(64), 0, (hipStream_t)stream, op, (const JacobianMem*)p, q, (JacobianMem*)out, n);
-        else hipLaunchKernelGGL((point_op_q4_kernel<FqParams>), dim3(gq), dim3(64), 0, (hipStream_t)stream, op, (const JacobianMem*)p, q, (JacobianMem*)out, n);
+        with_curve(curve, [&](auto cv) { hipLaunchKernelGGL((point_op_q4_kernel<typename decltype(cv)::Base>), dim3(gq), dim3(64), 0, (hipStream_t)stream, op, (const JacobianMem*)p, q, (JacobianMem*)out, n); });
         TRH_HIP_TRY(hipGetLastError());
         return TRH_OK;
     }
     const unsigned gb = (unsigned)((n + 63) / 64);
-    if (curve == TRH_PALLAS) hipLaunchKernelGGL((point_op_kernel<FpParams>), dim3(gb), dim3(64), 0, (hipStream_t)stream, op, (const JacobianMem*)p, q, (JacobianMem*)out, n);
-    else hipLaunchKernelGGL((point_op_kernel<FqParams>), dim3(gb), dim3(64), 0, (hipStream_t)stream, op, (const JacobianMem*)p, q, (JacobianMem*)out, n);
+    with_curve(curve, [&](auto cv) { hipLaunchKernelGGL((point_op_kernel<typename decltype(cv)::Base>), dim3(gb), dim3(64), 0, (hipStream_t)stream, op, (const JacobianMem*)p, q, (JacobianMem*)out, n); });
     TRH_HIP_TRY(hipGetLastError());
     return TRH_OK;
 }

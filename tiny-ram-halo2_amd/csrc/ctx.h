@@ -20,6 +20,7 @@
 
 #include "../../include/trh.h"
 #include "curve.h"
+#include "dispatch.h"
 
 struct trh_bases;
 namespace trh { class CopyPool; }
@@ -234,6 +235,9 @@ enum { ATTR_MSM = 1u, ATTR_NTT = 2u, ATTR_EXPR = 4u };
 
 Ctx& ctx();  // the context entered (TRH_ENTER) by the calling thread
 int require_init();
+// capi.hip: TRH_EINVAL and the error text for an id that with_field / with_curve (dispatch.h) must not see
+int check_field(int field);
+int check_curve(int curve);
 
 // Scope of one entry point: resolve the thread's context (trh_ctx_set_current, else the process default of trh_init), lock it,
 // make its device current for the calling thread, order `stream` behind the context's previous stream.

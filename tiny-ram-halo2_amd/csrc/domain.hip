@@ -235,7 +235,7 @@ extern "C" {
 int trh_domain_reserve(trh_domain* d, size_t batch);
 int trh_domain_create(int field, uint32_t j, uint32_t k, trh_domain** out) {
     TRH_TRY(require_init());
-    if (field != TRH_FP && field != TRH_FQ) { set_error("unknown field id %d", field); return TRH_EINVAL; }
+    TRH_TRY(check_field(field));
     if (!out || j < 2 || k > 27) { set_error("domain_create: bad arguments"); return TRH_EINVAL; }
     trh_domain* d = new trh_domain();
     d->field = field; d->j = j; d->k = k;
@@ -243,7 +243,7 @@ int trh_domain_create(int field, uint32_t j, uint32_t k, trh_domain** out) {
     while (((uint64_t)1 << ek) < ((uint64_t)1 << k) * (j - 1)) ++ek;
     if (ek > 27) { delete d; set_error("domain_create: extended_k %u > 27 unsupported", ek); return TRH_EINVAL; }
     d->extended_k = ek;
-    if (field == TRH_FP) build_domain<FpParams>(d); else build_domain<FqParams>(d);
+    with_field(field, [&](auto f) { build_domain<decltype(f)>(d); });
     TRH_ENTER(0);
     Range range("trh_domain_create");
     d->device = ctx().device;
@@ -285,7 +285,7 @@ int trh_domain_reserve(trh_domain* d, size_t batch) {
     const uint32_t D = d->j - 1, nblk = 1u << (d->extended_k - d->k);
     TRH_TRY(ntt_prepare(d->field, d->k, (const u64*)&d->omega_inv, ntt_can_fold_scale(d->k) ? (const u64*)&d->ifft_divisor : nullptr, batch, 0, s));
     if (D <= 8 && D <= nblk) {
-        TRH_TRY(d->field == TRH_FP ? build_blocks<FpParams>(d, s) : build_blocks<FqParams>(d, s));
+        TRH_TRY(with_field(d->field, [&](auto f) { return build_blocks<decltype(f)>(d, s); }));
         const void* pre = nullptr;
         TRH_TRY(pre_block_table(d, D, s, &pre));
         TRH_TRY(ntt_prepare(d->field, d->k, (const u64*)&d->omega, nullptr, batch * D, D, s));
@@ -330,8 +330,7 @@ int trh_domain_coeff_to_extended(trh_domain* d, const void* coeff_dev, void* ext
     }
     if (total) {
         const unsigned gb = (unsigned)((total + 255) / 256);
-        if (d->field == TRH_FP) hipLaunchKernelGGL((pad_coset_kernel<FpParams>), dim3(gb), dim3(256), 0, (hipStream_t)stream, (const uint4*)coeff_dev, (uint4*)ext_dev, batch, n, N, (const uint4*)tab(d, T_INTO));
-        else hipLaunchKernelGGL((pad_coset_kernel<FqParams>), dim3(gb), dim3(256), 0, (hipStream_t)stream, (const uint4*)coeff_dev, (uint4*)ext_dev, batch, n, N, (const uint4*)tab(d, T_INTO));
+        with_field(d->field, [&](auto f) { hipLaunchKernelGGL((pad_coset_kernel<decltype(f)>), dim3(gb), dim3(256), 0, (hipStream_t)stream, (const uint4*)coeff_dev, (uint4*)ext_dev, batch, n, N, (const uint4*)tab(d, T_INTO)); });
         TRH_HIP_TRY(hipGetLastError());
     }
     return ntt_device(d->field, ext_dev, d->extended_k, (const u64*)&d->extended_omega, batch, (hipStream_t)stream);
@@ -384,7 +383,7 @@ int trh_domain_coeff_to_extended_blocks(trh_domain* d, const void* coeff_dev, vo
     Ctx& c = ctx();
     (void)c;
     hipStream_t s = (hipStream_t)stream;
-    TRH_TRY(d->field == TRH_FP ? build_blocks<FpParams>(d, s) : build_blocks<FqParams>(d, s));
+    TRH_TRY(with_field(d->field, [&](auto f) { return build_blocks<decltype(f)>(d, s); }));
     const void* pre_tab = nullptr;
     TRH_TRY(pre_block_table(d, n_blocks, s, &pre_tab));
     if (ntt_can_fuse(d->k) && ntt_lazy_shift() == 5) {  // the scaling rides on the loads of pass 0
@@ -409,7 +408,7 @@ int trh_domain_blocks_to_quotient(trh_domain* d, void* num_blocks_dev, void* h_c
     TRH_ENTER(stream);
     Range range("trh_domain_blocks_to_quotient");
     hipStream_t s = (hipStream_t)stream;
-    TRH_TRY(d->field == TRH_FP ? build_blocks<FpParams>(d, s) : build_blocks<FqParams>(d, s));
+    TRH_TRY(with_field(d->field, [&](auto f) { return build_blocks<decltype(f)>(d, s); }));
     const uint32_t D = d->j - 1;
     const size_t n = (size_t)1 << d->k;
     if (ntt_can_fuse(d->k) && ntt_lazy_shift() == 5) {
@@ -422,8 +421,7 @@ int trh_domain_blocks_to_quotient(trh_domain* d, void* num_blocks_dev, void* h_c
     }
     const uint4* mat = (const uint4*)d->d_vinv + (divide_by_vanishing ? (size_t)2 * D * D : 0);
     const unsigned gb = (unsigned)((n + 255) / 256);
-    if (d->field == TRH_FP) hipLaunchKernelGGL((block_combine_kernel<FpParams>), dim3(gb), dim3(256), 0, s, (const uint4*)num_blocks_dev, (uint4*)h_coeff_dev, mat, D, n);
-    else hipLaunchKernelGGL((block_combine_kernel<FqParams>), dim3(gb), dim3(256), 0, s, (const uint4*)num_blocks_dev, (uint4*)h_coeff_dev, mat, D, n);
+    with_field(d->field, [&](auto f) { hipLaunchKernelGGL((block_combine_kernel<decltype(f)>), dim3(gb), dim3(256), 0, s, (const uint4*)num_blocks_dev, (uint4*)h_coeff_dev, mat, D, n); });
     TRH_HIP_TRY(hipGetLastError());
     return TRH_OK;
 }

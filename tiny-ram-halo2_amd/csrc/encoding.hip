@@ -124,22 +124,15 @@ template <class F> bool point_from_bytes_t(const uint8_t* in, uint64_t* out_xy) 
     return valid;
 }
 
-int enc_check_curve(int curve) {
-    if (curve != TRH_PALLAS && curve != TRH_VESTA) { set_error("unknown curve id %d", curve); return TRH_EINVAL; }
-    return TRH_OK;
-}
-
 }  // namespace
 
 int points_decompress_device(int curve, const void* bytes_dev, void* xy_dev, void* ok_dev, size_t n, hipStream_t s, u64* first_bad) {
     if (!n) { if (first_bad) *first_bad = 0; return TRH_OK; }
-    if (curve == TRH_PALLAS) return decompress_t<FpParams>(bytes_dev, xy_dev, ok_dev, n, s, first_bad);
-    return decompress_t<FqParams>(bytes_dev, xy_dev, ok_dev, n, s, first_bad);
+    return with_curve(curve, [&](auto cv) { return decompress_t<typename decltype(cv)::Base>(bytes_dev, xy_dev, ok_dev, n, s, first_bad); });
 }
 int points_compress_device(int curve, const void* xy_dev, void* bytes_dev, size_t n, hipStream_t s) {
     if (!n) return TRH_OK;
-    if (curve == TRH_PALLAS) hipLaunchKernelGGL((compress_kernel<FpParams>), dim3(enc_grid(n)), dim3(ENC_BLOCK), 0, s, (const uint4*)xy_dev, (u32*)bytes_dev, n);
-    else hipLaunchKernelGGL((compress_kernel<FqParams>), dim3(enc_grid(n)), dim3(ENC_BLOCK), 0, s, (const uint4*)xy_dev, (u32*)bytes_dev, n);
+    with_curve(curve, [&](auto cv) { hipLaunchKernelGGL((compress_kernel<typename decltype(cv)::Base>), dim3(enc_grid(n)), dim3(ENC_BLOCK), 0, s, (const uint4*)xy_dev, (u32*)bytes_dev, n); });
     TRH_HIP_TRY(hipGetLastError());
     return TRH_OK;
 }
@@ -155,18 +148,17 @@ using namespace trh;
 extern "C" {
 
 int trh_field_sqrt_dev(int field, const void* a_dev, void* out_dev, void* is_square_dev, size_t n, void* stream) {
-    if (field != TRH_FP && field != TRH_FQ) { set_error("unknown field id %d", field); return TRH_EINVAL; }
+    TRH_TRY(check_field(field));
     if (n && (!a_dev || !out_dev || !is_square_dev)) { set_error("field_sqrt_dev: null pointer"); return TRH_EINVAL; }
     if ((((uintptr_t)a_dev | (uintptr_t)out_dev) & 15) != 0) { set_error("field_sqrt_dev: elements must be 16-byte aligned"); return TRH_EINVAL; }
     TRH_ENTER(stream);
     if (!n) return TRH_OK;
     Range range("trh_field_sqrt_dev");
-    if (field == TRH_FP) return field_sqrt_t<FpParams>(a_dev, out_dev, is_square_dev, n, (hipStream_t)stream);
-    return field_sqrt_t<FqParams>(a_dev, out_dev, is_square_dev, n, (hipStream_t)stream);
+    return with_field(field, [&](auto f) { return field_sqrt_t<decltype(f)>(a_dev, out_dev, is_square_dev, n, (hipStream_t)stream); });
 }
 
 int trh_points_compress_dev(int curve, const void* xy_dev, void* bytes_dev, size_t n, void* stream) {
-    TRH_TRY(enc_check_curve(curve));
+    TRH_TRY(check_curve(curve));
     if (n && (!xy_dev || !bytes_dev)) { set_error("points_compress_dev: null pointer"); return TRH_EINVAL; }
     if (((uintptr_t)xy_dev & 15) != 0 || ((uintptr_t)bytes_dev & 3) != 0) { set_error("points_compress_dev: points must be 16-byte, encodings 4-byte aligned"); return TRH_EINVAL; }
     TRH_ENTER(stream);
@@ -175,7 +167,7 @@ int trh_points_compress_dev(int curve, const void* xy_dev, void* bytes_dev, size
 }
 
 int trh_points_decompress_dev(int curve, const void* bytes_dev, void* xy_dev, void* ok_dev_or_null, size_t n, void* stream, uint64_t* first_bad_or_null) {
-    TRH_TRY(enc_check_curve(curve));
+    TRH_TRY(check_curve(curve));
     if (n && (!xy_dev || !bytes_dev)) { set_error("points_decompress_dev: null pointer"); return TRH_EINVAL; }
     if (((uintptr_t)xy_dev & 15) != 0 || ((uintptr_t)bytes_dev & 3) != 0) { set_error("points_decompress_dev: points must be 16-byte, encodings 4-byte aligned"); return TRH_EINVAL; }
     TRH_ENTER(stream);
@@ -184,17 +176,16 @@ int trh_points_decompress_dev(int curve, const void* bytes_dev, void* xy_dev, vo
 }
 
 int trh_point_to_bytes(int curve, const uint64_t xyz[12], uint8_t out[32]) {
-    TRH_TRY(enc_check_curve(curve));
+    TRH_TRY(check_curve(curve));
     if (!xyz || !out) { set_error("point_to_bytes: null pointer"); return TRH_EINVAL; }
-    if (curve == TRH_PALLAS) point_to_bytes_t<FpParams>(xyz, out);
-    else point_to_bytes_t<FqParams>(xyz, out);
+    with_curve(curve, [&](auto cv) { point_to_bytes_t<typename decltype(cv)::Base>(xyz, out); });
     return TRH_OK;
 }
 
 int trh_point_from_bytes(int curve, const uint8_t in[32], uint64_t out_xy[8]) {
-    TRH_TRY(enc_check_curve(curve));
+    TRH_TRY(check_curve(curve));
     if (!in || !out_xy) { set_error("point_from_bytes: null pointer"); return TRH_EINVAL; }
-    const bool valid = curve == TRH_PALLAS ? point_from_bytes_t<FpParams>(in, out_xy) : point_from_bytes_t<FqParams>(in, out_xy);
+    const bool valid = with_curve(curve, [&](auto cv) { return point_from_bytes_t<typename decltype(cv)::Base>(in, out_xy); });
     if (!valid) { set_error("point_from_bytes: not the encoding of a point"); return TRH_EINVAL; }
     return TRH_OK;
 }

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "devmem.h"
 
 struct trh_expr {
     int field;
@@ -86,12 +87,7 @@ __device__ __forceinline__ Fy<F> lds_get(const unsigned char* smem, u32 slot) {
     v.l[8] = (i32)c[threadIdx.x];
     return v;
 }
-// a constant of the program: stored by the host as the words of (c 2^261 mod m), non-negative and below m
-template <class F>
-__device__ __forceinline__ Fy<F> ldg_const(const uint4* p) {
-    const uint4 a = p[0], b = p[1];
-    return fy_load<F>(a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w);
-}
+// a constant of the program is stored by the host as the words of (c 2^261 mod m), non-negative and below m: load_fy reads it as it is
 // a column element: canonical Montgomery words (x 2^256 mod m) -> the domain value 32 (x 2^256) = x 2^261 + k m, 0 <= value < 32 m:
 // limb k is the 29-bit window at bit 29 k - 5 of the words (the unpacking of fy_load, five bits lower)
 template <class F>
@@ -137,7 +133,7 @@ __global__ void __launch_bounds__(THREADS) expr_eval_kernel(const DevInsn* __res
             case TRH_EXPR_PUSH_CONST:
                 if (in.slot != NO_SLOT) lds_put<F>(smem, in.slot, Nx);
                 Nx = T;
-                T = ldg_const<F>(consts + 2 * (size_t)in.a);
+                T = load_fy<F>(consts + 2 * (size_t)in.a);
                 break;
             case TRH_EXPR_PUSH_LOCAL:
                 if (in.slot != NO_SLOT) lds_put<F>(smem, in.slot, Nx);
@@ -149,11 +145,11 @@ __global__ void __launch_bounds__(THREADS) expr_eval_kernel(const DevInsn* __res
             case TRH_EXPR_MUL: T = fy_mul(Nx, T); if (in.slot != NO_SLOT) Nx = lds_get<F>(smem, in.slot); break;
             case TRH_EXPR_NEG: T = fy_sub(fy_zero<F>(), T); break;
             case TRH_EXPR_SQR: T = fy_sqr(T); break;
-            case TRH_EXPR_MUL_CONST: T = fy_mul(T, ldg_const<F>(consts + 2 * (size_t)in.a)); break;
-            case TRH_EXPR_ADD_CONST: T = fy_add(T, ldg_const<F>(consts + 2 * (size_t)in.a)); break;
+            case TRH_EXPR_MUL_CONST: T = fy_mul(T, load_fy<F>(consts + 2 * (size_t)in.a)); break;
+            case TRH_EXPR_ADD_CONST: T = fy_add(T, load_fy<F>(consts + 2 * (size_t)in.a)); break;
             case TRH_EXPR_STORE_LOCAL: lds_put<F>(smem, in.a, T); break;  // keeps T
             case TRH_EXPR_FOLD:  // acc = acc * const + T; pop
-                ACC = fy_add(fy_mul(ACC, ldg_const<F>(consts + 2 * (size_t)in.a)), T);
+                ACC = fy_add(fy_mul(ACC, load_fy<F>(consts + 2 * (size_t)in.a)), T);
                 T = Nx;
                 if (in.slot != NO_SLOT) Nx = lds_get<F>(smem, in.slot);
                 break;
@@ -214,7 +210,7 @@ extern "C" {
 int trh_expr_create(int field, const trh_expr_insn_t* insns, size_t n_insn, const uint64_t* consts, size_t n_consts, size_t n_columns, size_t n_outputs,
                     size_t n_locals, trh_expr** out) {
     TRH_TRY(require_init());
-    if (field != TRH_FP && field != TRH_FQ) { set_error("unknown field id %d", field); return TRH_EINVAL; }
+    TRH_TRY(check_field(field));
     if (!out || !insns || !n_insn || (n_consts && !consts)) { set_error("expr_create: null pointer / empty program"); return TRH_EINVAL; }
     if (n_columns > 65535 || n_outputs == 0 || n_outputs > 65535 || n_consts > 65535 || n_locals > 64) { set_error("expr_create: table sizes out of range"); return TRH_EINVAL; }
     // pass 1: stack depth at every instruction, maximum depth (the two top entries live in registers), and a magnitude bound (in
@@ -327,8 +323,7 @@ int trh_expr_create(int field, const trh_expr_insn_t* insns, size_t n_insn, cons
     if (err == hipSuccess) err = hipMemcpy(e->d_prog, dev.data(), n_dev * sizeof(DevInsn), hipMemcpyHostToDevice);
     std::vector<uint64_t> dom(4 * (n_consts ? n_consts : 1));
     for (size_t i = 0; i < n_consts; ++i) {
-        if (field == TRH_FP) const_to_domain<FpParams>(consts + 4 * i, dom.data() + 4 * i);
-        else const_to_domain<FqParams>(consts + 4 * i, dom.data() + 4 * i);
+        with_field(field, [&](auto f) { const_to_domain<decltype(f)>(consts + 4 * i, dom.data() + 4 * i); });
     }
     if (err == hipSuccess && n_consts) err = hipMemcpy(e->d_consts, dom.data(), n_consts * 32, hipMemcpyHostToDevice);
     if (err != hipSuccess) {
@@ -367,7 +362,7 @@ int trh_expr_set_const(trh_expr* e, uint32_t index, const uint64_t value[4]) {
     Ctx& c = ctx();
     (void)c;
     uint64_t dom[4];
-    if (e->field == TRH_FP) const_to_domain<FpParams>(value, dom); else const_to_domain<FqParams>(value, dom);
+    with_field(e->field, [&](auto f) { const_to_domain<decltype(f)>(value, dom); });
     TRH_HIP_TRY(hipMemcpy((char*)e->d_consts + (size_t)index * 32, dom, 32, hipMemcpyHostToDevice));
     return TRH_OK;
 }
@@ -402,12 +397,10 @@ static int expr_eval(trh_expr* e, const void* const* columns_dev, void* const* o
     const size_t N = n_blocks ? (size_t)n_blocks << log_n : (size_t)1 << log_n;
     const unsigned blocks = (unsigned)((N + THREADS - 1) / THREADS);
     const size_t lds = (size_t)e->lds_slots * THREADS * 36;
-    if (e->field == TRH_FP)
-        hipLaunchKernelGGL((expr_eval_kernel<FpParams>), dim3(blocks), dim3(THREADS), lds, s, (const DevInsn*)e->d_prog, e->n_insn, (const uint4* const*)e->d_ptrs, e->n_columns,
+    with_field(e->field, [&](auto f) {
+        hipLaunchKernelGGL((expr_eval_kernel<decltype(f)>), dim3(blocks), dim3(THREADS), lds, s, (const DevInsn*)e->d_prog, e->n_insn, (const uint4* const*)e->d_ptrs, e->n_columns,
                            (const uint4*)e->d_consts, log_n, rot_step, n_blocks);
-    else
-        hipLaunchKernelGGL((expr_eval_kernel<FqParams>), dim3(blocks), dim3(THREADS), lds, s, (const DevInsn*)e->d_prog, e->n_insn, (const uint4* const*)e->d_ptrs, e->n_columns,
-                           (const uint4*)e->d_consts, log_n, rot_step, n_blocks);
+    });
     TRH_HIP_TRY(hipGetLastError());
     TRH_HIP_TRY(hipStreamSynchronize(s));  // h_ptrs is reused by the next call
     return TRH_OK;

@@ -14,24 +14,12 @@
 #include <chrono>
 
 #include "ctx.h"
+#include "devmem.h"
 #include "hostcombine.h"
 #include "hosthelper.h"
 
 namespace trh {
 namespace {
-
-template <class F>
-__device__ __forceinline__ Fe<F> ld(const uint4* p) {
-    uint4 a = p[0], b = p[1];
-    return fe_load<F>(a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w);
-}
-template <class F>
-__device__ __forceinline__ void st(uint4* p, const Fe<F>& v) {
-    u32 w[8];
-    fe_store(v, w);
-    p[0] = make_uint4(w[0], w[1], w[2], w[3]);
-    p[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
 
 // partial[block] = sum over the block's grid-stride share of a[i] * b[i]
 template <class F>
@@ -39,27 +27,27 @@ __global__ void __launch_bounds__(256) inner_product_kernel(const uint4* __restr
     __shared__ Fe<F> sh[256];
     Fe<F> acc = fe_zero<F>();
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        acc = fe_add(acc, fe_mul(ld<F>(a + 2 * i), ld<F>(b + 2 * i)));
+        acc = fe_add(acc, fe_mul(load_fe<F>(a + 2 * i), load_fe<F>(b + 2 * i)));
     sh[threadIdx.x] = acc;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
         if ((int)threadIdx.x < s) sh[threadIdx.x] = fe_add(sh[threadIdx.x], sh[threadIdx.x + s]);
         __syncthreads();
     }
-    if (threadIdx.x == 0) st<F>(partial + 2 * blockIdx.x, sh[0]);
+    if (threadIdx.x == 0) store_fe<F>(partial + 2 * blockIdx.x, sh[0]);
 }
 template <class F>
 __global__ void __launch_bounds__(256) sum_partials_kernel(const uint4* __restrict__ partial, u32 count, uint4* __restrict__ out) {
     __shared__ Fe<F> sh[256];
     Fe<F> acc = fe_zero<F>();
-    for (u32 i = threadIdx.x; i < count; i += 256) acc = fe_add(acc, ld<F>(partial + 2 * i));
+    for (u32 i = threadIdx.x; i < count; i += 256) acc = fe_add(acc, load_fe<F>(partial + 2 * i));
     sh[threadIdx.x] = acc;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
         if ((int)threadIdx.x < s) sh[threadIdx.x] = fe_add(sh[threadIdx.x], sh[threadIdx.x + s]);
         __syncthreads();
     }
-    if (threadIdx.x == 0) st<F>(out, sh[0]);
+    if (threadIdx.x == 0) store_fe<F>(out, sh[0]);
 }
 
 // evaluation of a batch of polynomials at one point: partial[poly][block] = sum over the block's share of a[poly][i] * pw[i]
@@ -69,28 +57,28 @@ __global__ void __launch_bounds__(256) eval_batch_kernel(const uint4* __restrict
     const uint4* a = polys + (size_t)blockIdx.y * n * 2;
     Fe<F> acc = fe_zero<F>();
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        acc = fe_add(acc, fe_mul(ld<F>(a + 2 * i), ld<F>(pw + 2 * i)));
+        acc = fe_add(acc, fe_mul(load_fe<F>(a + 2 * i), load_fe<F>(pw + 2 * i)));
     sh[threadIdx.x] = acc;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
         if ((int)threadIdx.x < s) sh[threadIdx.x] = fe_add(sh[threadIdx.x], sh[threadIdx.x + s]);
         __syncthreads();
     }
-    if (threadIdx.x == 0) st<F>(partial + 2 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x), sh[0]);
+    if (threadIdx.x == 0) store_fe<F>(partial + 2 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x), sh[0]);
 }
 template <class F>
 __global__ void __launch_bounds__(256) sum_partials_batch_kernel(const uint4* __restrict__ partial, u32 count, uint4* __restrict__ out) {
     __shared__ Fe<F> sh[256];
     const uint4* p = partial + 2 * (size_t)blockIdx.x * count;
     Fe<F> acc = fe_zero<F>();
-    for (u32 i = threadIdx.x; i < count; i += 256) acc = fe_add(acc, ld<F>(p + 2 * i));
+    for (u32 i = threadIdx.x; i < count; i += 256) acc = fe_add(acc, load_fe<F>(p + 2 * i));
     sh[threadIdx.x] = acc;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
         if ((int)threadIdx.x < s) sh[threadIdx.x] = fe_add(sh[threadIdx.x], sh[threadIdx.x + s]);
         __syncthreads();
     }
-    if (threadIdx.x == 0) st<F>(out + 2 * (size_t)blockIdx.x, sh[0]);
+    if (threadIdx.x == 0) store_fe<F>(out + 2 * (size_t)blockIdx.x, sh[0]);
 }
 
 // y[i] += c * x[i]
@@ -98,7 +86,7 @@ template <class F>
 __global__ void __launch_bounds__(256) axpy_kernel(uint4* __restrict__ y, const uint4* __restrict__ x, size_t n, const uint4* __restrict__ c) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    st<F>(y + 2 * i, fe_add(ld<F>(y + 2 * i), fe_mul(ld<F>(x + 2 * i), ld<F>(c))));
+    store_fe<F>(y + 2 * i, fe_add(load_fe<F>(y + 2 * i), fe_mul(load_fe<F>(x + 2 * i), load_fe<F>(c))));
 }
 
 // out[i] = x^i, pw[b] = x^(2^b)
@@ -108,8 +96,8 @@ __global__ void __launch_bounds__(256) powers_kernel(uint4* __restrict__ out, si
     if (i >= n) return;
     Fe<F> r = fe_one<F>();
     for (int b = 0; b < 32; ++b)
-        if ((i >> b) & 1u) r = fe_mul(r, ld<F>(pw + 2 * b));
-    st<F>(out + 2 * i, r);
+        if ((i >> b) & 1u) r = fe_mul(r, load_fe<F>(pw + 2 * b));
+    store_fe<F>(out + 2 * i, r);
 }
 
 // generator collapse: g_lo[i] = g_lo[i] + u * g_hi[i], normalised to affine
@@ -149,10 +137,10 @@ __global__ void __launch_bounds__(256) ipa_round_update_kernel(uint4* __restrict
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
     const Fe<F> u = ipa_const<F>(consts, 1);
-    if ((idx >> bit) & 1u) st<F>(wgt + 2 * idx, fe_mul(ld<F>(wgt + 2 * idx), u));
+    if ((idx >> bit) & 1u) store_fe<F>(wgt + 2 * idx, fe_mul(load_fe<F>(wgt + 2 * idx), u));
     if (idx < half) {
-        st<F>(p + 2 * idx, fe_add(ld<F>(p + 2 * idx), fe_mul(ld<F>(p + 2 * (half + idx)), ipa_const<F>(consts, 0))));
-        st<F>(b + 2 * idx, fe_add(ld<F>(b + 2 * idx), fe_mul(ld<F>(b + 2 * (half + idx)), u)));
+        store_fe<F>(p + 2 * idx, fe_add(load_fe<F>(p + 2 * idx), fe_mul(load_fe<F>(p + 2 * (half + idx)), ipa_const<F>(consts, 0))));
+        store_fe<F>(b + 2 * idx, fe_add(load_fe<F>(b + 2 * idx), fe_mul(load_fe<F>(b + 2 * (half + idx)), u)));
     }
 }
 
@@ -174,14 +162,14 @@ __global__ void __launch_bounds__(256) inner_product2_kernel(const uint4* __rest
     const uint4* b = blockIdx.y ? b1 : b0;
     Fe<F> acc = fe_zero<F>();
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        acc = fe_add(acc, fe_mul(ld<F>(a + 2 * i), ld<F>(b + 2 * i)));
+        acc = fe_add(acc, fe_mul(load_fe<F>(a + 2 * i), load_fe<F>(b + 2 * i)));
     sh[threadIdx.x] = acc;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
         if ((int)threadIdx.x < s) sh[threadIdx.x] = fe_add(sh[threadIdx.x], sh[threadIdx.x + s]);
         __syncthreads();
     }
-    if (threadIdx.x == 0) st<F>(partial + 2 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x), sh[0]);
+    if (threadIdx.x == 0) store_fe<F>(partial + 2 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x), sh[0]);
 }
 
 template <class F>
@@ -194,25 +182,25 @@ __global__ void __launch_bounds__(256) ipa_round_front_kernel(const uint4* __res
     if (idx >= n) return;
     const size_t hprev = half << 1;  // the previous round's half
     const Fe<F> uinv = ipa_const<F>(consts, 0), u = ipa_const<F>(consts, 1);
-    auto pn = [&](size_t x) { return first ? ld<F>(p_old + 2 * x) : fe_add(ld<F>(p_old + 2 * x), fe_mul(ld<F>(p_old + 2 * (hprev + x)), uinv)); };  // x < hprev
+    auto pn = [&](size_t x) { return first ? load_fe<F>(p_old + 2 * x) : fe_add(load_fe<F>(p_old + 2 * x), fe_mul(load_fe<F>(p_old + 2 * (hprev + x)), uinv)); };  // x < hprev
     Fe<F> w;
     if (wfresh) {  // round 0 reads no weights, round 1 writes them all
         w = (!first && ((idx >> (bit + 1)) & 1u)) ? u : fe_one<F>();
-        if (!first) st<F>(wgt + 2 * idx, w);
+        if (!first) store_fe<F>(wgt + 2 * idx, w);
     } else {
-        w = ld<F>(wgt + 2 * idx);
-        if (!first && ((idx >> (bit + 1)) & 1u)) { w = fe_mul(w, u); st<F>(wgt + 2 * idx, w); }
+        w = load_fe<F>(wgt + 2 * idx);
+        if (!first && ((idx >> (bit + 1)) & 1u)) { w = fe_mul(w, u); store_fe<F>(wgt + 2 * idx, w); }
     }
     const size_t i = idx & (half - 1);
     const bool hi = (idx >> bit) & 1u;
     Fe<F> v = fe_mul(w, pn(hi ? i : half + i));
     if (canon) v = fe_from_mont(v);
     const Fe<F> zero = fe_zero<F>();
-    st<F>(lrsc + 2 * idx, hi ? zero : v);
-    st<F>(lrsc + 2 * (stride + idx), hi ? v : zero);
+    store_fe<F>(lrsc + 2 * idx, hi ? zero : v);
+    store_fe<F>(lrsc + 2 * (stride + idx), hi ? v : zero);
     if (!first && idx < hprev) {  // the folded vectors, once
-        st<F>(p_new + 2 * idx, pn(idx));
-        st<F>(b_new + 2 * idx, fe_add(ld<F>(b_old + 2 * idx), fe_mul(ld<F>(b_old + 2 * (hprev + idx)), u)));
+        store_fe<F>(p_new + 2 * idx, pn(idx));
+        store_fe<F>(b_new + 2 * idx, fe_add(load_fe<F>(b_old + 2 * idx), fe_mul(load_fe<F>(b_old + 2 * (hprev + idx)), u)));
     }
 }
 // dst[i] = a[i] + x s[i] (s may be null: a plain copy) and the block sums of dst[i] b[i], one pass: the opening's s(X) -> s' and p + xi s -> p'
@@ -225,10 +213,10 @@ __global__ void __launch_bounds__(256) ipa_combine_eval_kernel(const uint4* __re
     const Fe<F> x = ipa_const<F>(consts, 0);
     Fe<F> acc = fe_zero<F>();
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        Fe<F> v = ld<F>(a + 2 * i);
-        if (sv) v = fe_add(v, fe_mul(ld<F>(sv + 2 * i), x));
-        st<F>(dst + 2 * i, v);
-        acc = fe_add(acc, fe_mul(v, ld<F>(b + 2 * i)));
+        Fe<F> v = load_fe<F>(a + 2 * i);
+        if (sv) v = fe_add(v, fe_mul(load_fe<F>(sv + 2 * i), x));
+        store_fe<F>(dst + 2 * i, v);
+        acc = fe_add(acc, fe_mul(v, load_fe<F>(b + 2 * i)));
     }
     sh[threadIdx.x] = acc;
     __syncthreads();
@@ -236,14 +224,14 @@ __global__ void __launch_bounds__(256) ipa_combine_eval_kernel(const uint4* __re
         if ((int)threadIdx.x < s) sh[threadIdx.x] = fe_add(sh[threadIdx.x], sh[threadIdx.x + s]);
         __syncthreads();
     }
-    if (threadIdx.x == 0) st<F>(partial + 2 * blockIdx.x, sh[0]);
+    if (threadIdx.x == 0) store_fe<F>(partial + 2 * blockIdx.x, sh[0]);
 }
 // one workgroup: vec[0] -= sum of the partials; with tail: vec[n] = consts[0] (the blind), vec[n + 1] = 0 (the scalar of u)
 template <class F>
 __global__ void __launch_bounds__(256) ipa_fix_constant_kernel(const uint4* __restrict__ partial, u32 count, uint4* __restrict__ vec, size_t n, int tail, const IpaConsts consts) {
     __shared__ Fe<F> sh[256];
     Fe<F> acc = fe_zero<F>();
-    for (u32 i = threadIdx.x; i < count; i += 256) acc = fe_add(acc, ld<F>(partial + 2 * i));
+    for (u32 i = threadIdx.x; i < count; i += 256) acc = fe_add(acc, load_fe<F>(partial + 2 * i));
     sh[threadIdx.x] = acc;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
@@ -251,8 +239,8 @@ __global__ void __launch_bounds__(256) ipa_fix_constant_kernel(const uint4* __re
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        st<F>(vec, fe_sub(ld<F>(vec), sh[0]));
-        if (tail) { st<F>(vec + 2 * n, ipa_const<F>(consts, 0)); st<F>(vec + 2 * (n + 1), fe_zero<F>()); }
+        store_fe<F>(vec, fe_sub(load_fe<F>(vec), sh[0]));
+        if (tail) { store_fe<F>(vec + 2 * n, ipa_const<F>(consts, 0)); store_fe<F>(vec + 2 * (n + 1), fe_zero<F>()); }
     }
 }
 
@@ -263,7 +251,7 @@ __global__ void __launch_bounds__(256) ipa_round_tails_kernel(const uint4* __res
     const u32 side = blockIdx.x;
     const uint4* p = partial + 2 * (size_t)side * count;
     Fe<F> acc = fe_zero<F>();
-    for (u32 i = threadIdx.x; i < count; i += 256) acc = fe_add(acc, ld<F>(p + 2 * i));
+    for (u32 i = threadIdx.x; i < count; i += 256) acc = fe_add(acc, load_fe<F>(p + 2 * i));
     sh[threadIdx.x] = acc;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
@@ -273,8 +261,8 @@ __global__ void __launch_bounds__(256) ipa_round_tails_kernel(const uint4* __res
     if (threadIdx.x == 0) {
         Fe<F> r = side ? ipa_const<F>(consts, 1) : ipa_const<F>(consts, 0), vz = fe_mul(sh[0], ipa_const<F>(consts, 2));
         if (canon) { r = fe_from_mont(r); vz = fe_from_mont(vz); }
-        st<F>(lrsc + 2 * (side * stride + n), r);
-        st<F>(lrsc + 2 * (side * stride + n + 1), vz);
+        store_fe<F>(lrsc + 2 * (side * stride + n), r);
+        store_fe<F>(lrsc + 2 * (side * stride + n + 1), vz);
     }
 }
 
@@ -627,7 +615,7 @@ extern "C" {
 
 int trh_poly_eval_batch_dev(int field, const void* polys_dev, size_t n, size_t batch, const uint64_t point[4], void* stream, uint64_t* out) {
     TRH_TRY(require_init());
-    if (field != TRH_FP && field != TRH_FQ) { set_error("unknown field id %d", field); return TRH_EINVAL; }
+    TRH_TRY(check_field(field));
     if (!out || !point || (n && batch && !polys_dev)) { set_error("poly_eval: null pointer"); return TRH_EINVAL; }
     if (!batch) return TRH_OK;
     if (!n) { memset(out, 0, batch * 32); return TRH_OK; }
@@ -635,25 +623,23 @@ int trh_poly_eval_batch_dev(int field, const void* polys_dev, size_t n, size_t b
     Range range("trh_poly_eval_batch_dev");
     Ctx& c = ctx();
     (void)c;
-    if (field == TRH_FP) return eval_batch_t<FpParams>(polys_dev, n, batch, point, (hipStream_t)stream, out);
-    return eval_batch_t<FqParams>(polys_dev, n, batch, point, (hipStream_t)stream, out);
+    return with_field(field, [&](auto f) { return eval_batch_t<decltype(f)>(polys_dev, n, batch, point, (hipStream_t)stream, out); });
 }
 
 int trh_field_inner_product_dev(int field, const void* a_dev, const void* b_dev, size_t n, void* stream, uint64_t out[4]) {
     TRH_TRY(require_init());
-    if (field != TRH_FP && field != TRH_FQ) { set_error("unknown field id %d", field); return TRH_EINVAL; }
+    TRH_TRY(check_field(field));
     if (!out || (n && (!a_dev || !b_dev))) { set_error("inner_product: null pointer"); return TRH_EINVAL; }
     TRH_ENTER(stream);
     Range range("trh_field_inner_product_dev");
     Ctx& c = ctx();
     (void)c;
-    if (field == TRH_FP) return inner_product_t<FpParams>(a_dev, b_dev, n, (hipStream_t)stream, out);
-    return inner_product_t<FqParams>(a_dev, b_dev, n, (hipStream_t)stream, out);
+    return with_field(field, [&](auto f) { return inner_product_t<decltype(f)>(a_dev, b_dev, n, (hipStream_t)stream, out); });
 }
 
 int trh_field_axpy_dev(int field, void* y_dev, const void* x_dev, size_t n, const uint64_t c_mont[4], void* stream) {
     TRH_TRY(require_init());
-    if (field != TRH_FP && field != TRH_FQ) { set_error("unknown field id %d", field); return TRH_EINVAL; }
+    TRH_TRY(check_field(field));
     if (!c_mont || (n && (!y_dev || !x_dev))) { set_error("axpy: null pointer"); return TRH_EINVAL; }
     if (!n) return TRH_OK;
     TRH_ENTER(stream);
@@ -662,35 +648,31 @@ int trh_field_axpy_dev(int field, void* y_dev, const void* x_dev, size_t n, cons
     (void)c;
     FeMem cm;
     memcpy(&cm, c_mont, 32);
-    if (field == TRH_FP) return axpy_t<FpParams>(y_dev, x_dev, n, cm, (hipStream_t)stream);
-    return axpy_t<FqParams>(y_dev, x_dev, n, cm, (hipStream_t)stream);
+    return with_field(field, [&](auto f) { return axpy_t<decltype(f)>(y_dev, x_dev, n, cm, (hipStream_t)stream); });
 }
 
 int trh_field_powers_dev(int field, void* out_dev, size_t n, const uint64_t x_mont[4], void* stream) {
     TRH_TRY(require_init());
-    if (field != TRH_FP && field != TRH_FQ) { set_error("unknown field id %d", field); return TRH_EINVAL; }
+    TRH_TRY(check_field(field));
     if (!x_mont || (n && !out_dev)) { set_error("powers: null pointer"); return TRH_EINVAL; }
     if (!n) return TRH_OK;
     TRH_ENTER(stream);
     Range range("trh_field_powers_dev");
     Ctx& c = ctx();
     (void)c;
-    if (field == TRH_FP) return powers_t<FpParams>(out_dev, n, x_mont, (hipStream_t)stream);
-    return powers_t<FqParams>(out_dev, n, x_mont, (hipStream_t)stream);
+    return with_field(field, [&](auto f) { return powers_t<decltype(f)>(out_dev, n, x_mont, (hipStream_t)stream); });
 }
 
 int trh_bases_fold_dev(int curve, void* g_lo_dev, const void* g_hi_dev, size_t half, const uint64_t u_mont[4], void* stream) {
     TRH_TRY(require_init());
-    if (curve != TRH_PALLAS && curve != TRH_VESTA) { set_error("unknown curve id %d", curve); return TRH_EINVAL; }
+    TRH_TRY(check_curve(curve));
     if (!u_mont || (half && (!g_lo_dev || !g_hi_dev))) { set_error("bases_fold: null pointer"); return TRH_EINVAL; }
     if (!half) return TRH_OK;
     TRH_ENTER(stream);
     Range range("trh_bases_fold_dev");
     Ctx& c = ctx();
     (void)c;
-    // pallas: scalar field Fq, base field Fp
-    if (curve == TRH_PALLAS) return bases_fold_t<FqParams, FpParams>(g_lo_dev, g_hi_dev, half, u_mont, (hipStream_t)stream);
-    return bases_fold_t<FpParams, FqParams>(g_lo_dev, g_hi_dev, half, u_mont, (hipStream_t)stream);
+    return with_curve(curve, [&](auto cv) { return bases_fold_t<typename decltype(cv)::Scalar, typename decltype(cv)::Base>(g_lo_dev, g_hi_dev, half, u_mont, (hipStream_t)stream); });
 }
 
 int trh_ipa_create_proof(trh_bases_t g_w, const uint64_t u_xy[8], uint32_t k, const void* p_poly_dev, const uint64_t p_blind[4], const uint64_t x3[4],
@@ -710,9 +692,9 @@ int trh_ipa_create_proof(trh_bases_t g_w, const uint64_t u_xy[8], uint32_t k, co
         TRH_HIP_TRY(hipMemcpy(last, (const char*)g_w->d_xy + (g_w->n - 1) * 64, 64, hipMemcpyDeviceToHost));
         if (memcmp(last, u_xy, 64) != 0) { set_error("ipa_create_proof: the last point of a g || w || u base set differs from u"); return TRH_EINVAL; }
     }
-    if (g_w->curve == TRH_PALLAS)
-        return ipa_create_proof_t<FqParams, FpParams>(TRH_PALLAS, g_w, u_xy, k, p_poly_dev, p_blind, x3, s_poly_dev, s_blind, transcript, rng, rng_ctx, (hipStream_t)stream, out_c, out_f);
-    return ipa_create_proof_t<FpParams, FqParams>(TRH_VESTA, g_w, u_xy, k, p_poly_dev, p_blind, x3, s_poly_dev, s_blind, transcript, rng, rng_ctx, (hipStream_t)stream, out_c, out_f);
+    return with_curve(g_w->curve, [&](auto cv) {
+        return ipa_create_proof_t<typename decltype(cv)::Scalar, typename decltype(cv)::Base>(g_w->curve, g_w, u_xy, k, p_poly_dev, p_blind, x3, s_poly_dev, s_blind, transcript, rng, rng_ctx, (hipStream_t)stream, out_c, out_f);
+    });
 }
 
 }  // extern "C"

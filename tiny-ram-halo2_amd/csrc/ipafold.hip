@@ -19,32 +19,13 @@
 #include <vector>
 
 #include "ctx.h"
+#include "devmem.h"
 #include "hostcombine.h"
 
 namespace trh {
 namespace {
 
 constexpr u32 FOLD_SIGN = 0x80000000u;
-
-template <class BF>
-__device__ __forceinline__ void fold_store_raw(XYZZzMem* dst, const XYZZz<BF>& v) {
-    uint4* p = (uint4*)dst;
-    const u32* w = (const u32*)&v;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) p[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
-}
-template <class BF>
-__device__ __forceinline__ XYZZz<BF> fold_load_raw(const XYZZzMem* src) {
-    const uint4* p = (const uint4*)src;
-    XYZZz<BF> v;
-    u32* w = (u32*)&v;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        uint4 q = p[k];
-        w[4 * k] = q.x; w[4 * k + 1] = q.y; w[4 * k + 2] = q.z; w[4 * k + 3] = q.w;
-    }
-    return v;
-}
 
 // plan = offsets[nbk + 1] then entries: level j << 16 | t | sign << 31 (host: fold_plan)
 // grid (m / 256, nbk): every lane of a workgroup walks the SAME list -- the control flow is uniform and the loads are contiguous over i
@@ -115,7 +96,7 @@ __global__ void __launch_bounds__(256) ipa_fold_accumulate_kernel(const uint4* _
         if (pos < hi) step(s0);
     }
     if (fresh) acc = xyzzz_identity<BF>();
-    fold_store_raw(out + ((size_t)b << log_m) + i, acc);
+    store_raw(out + ((size_t)b << log_m) + i, acc);
 }
 
 // 32 lanes per generator: lane = (sub-window s, slice q < 16).  Slice: running sums over its NB / 16 buckets, + (first id - 1) * (sum of the
@@ -132,7 +113,7 @@ __global__ void __launch_bounds__(256) ipa_fold_reduce_kernel(const XYZZzMem* __
     const u32 first = (s ? (1u << (w0 - 1)) : 0u) + q * sl;  // row of the slice's first bucket
     XYZZz<BF> run = xyzzz_identity<BF>(), acc = xyzzz_identity<BF>();
     for (int k = (int)sl - 1; k >= 0; --k) {
-        const XYZZz<BF> v = fold_load_raw<BF>(buckets + ((size_t)(first + k) << log_m) + i);
+        const XYZZz<BF> v = load_raw<BF>(buckets + ((size_t)(first + k) << log_m) + i);
         run = xyzzz_add(run, v);
         acc = xyzzz_add(acc, run);
     }
@@ -165,7 +146,7 @@ __global__ void __launch_bounds__(256) ipa_fold_reduce_kernel(const XYZZzMem* __
         if (lane32 != 0) return;
         acc = xyzzz_add(acc, o);
     }
-    fold_store_raw(sums + i, acc);
+    store_raw(sums + i, acc);
 }
 
 // a thread per generator: affine in the lazy domain -- 1 / zzz by Fermat with this domain's products (255 squarings + ~65 products: the moduli
@@ -174,7 +155,7 @@ template <class BF>
 __global__ void __launch_bounds__(64) ipa_fold_affine_kernel(const XYZZzMem* __restrict__ sums, size_t m, uint4* __restrict__ out_xy, uint4* __restrict__ out_z) {
     const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (i >= m) return;
-    const XYZZz<BF> acc = fold_load_raw<BF>(sums + i);
+    const XYZZz<BF> acc = load_raw<BF>(sums + i);
     Affine<BF> a;
     if (xyzzz_is_identity(acc)) { a.x = fe_zero<BF>(); a.y = fe_zero<BF>(); }  // (never, for independent generators)
     else {
@@ -310,8 +291,7 @@ int ipa_fold_reserve(const MsmFixedBase& fb, uint32_t k, uint32_t r) {
 // out_xy = m affine points (64-byte records), out_z = the same in the accumulation's 128-byte form.  Enqueued on s; the caller holds the context.
 int ipa_fold_generators(int curve, const MsmFixedBase& fb, size_t row, uint32_t k, uint32_t r, const u64* u_mont, void* out_xy, void* out_z, hipStream_t s) {
     if (!ipa_fold_supported(fb, k, r)) { set_error("ipa fold: unsupported shape (table window %d, k = %u, r = %u)", fb.c, k, r); return TRH_EINVAL; }
-    if (curve == TRH_PALLAS) return ipa_fold_t<FqParams, FpParams>(fb, row, k, r, u_mont, out_xy, out_z, s);
-    return ipa_fold_t<FpParams, FqParams>(fb, row, k, r, u_mont, out_xy, out_z, s);
+    return with_curve(curve, [&](auto cv) { return ipa_fold_t<typename decltype(cv)::Scalar, typename decltype(cv)::Base>(fb, row, k, r, u_mont, out_xy, out_z, s); });
 }
 
 }  // namespace trh

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "devmem.h"
 
 struct trh_ipa_msm {
     int curve;
@@ -42,18 +43,6 @@ struct trh_ipa_msm {
 namespace trh {
 namespace {
 
-template <class F>
-__device__ __forceinline__ Fe<F> ldv(const uint4* p) {
-    const uint4 a = p[0], b = p[1];
-    return fe_load<F>(a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w);
-}
-template <class F>
-__device__ __forceinline__ void stv(uint4* p, const Fe<F>& v) {
-    u32 w[8];
-    fe_store(v, w);
-    p[0] = make_uint4(w[0], w[1], w[2], w[3]);
-    p[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
 struct Const1 { uint4 w[2]; };  // one scalar as a kernel argument
 template <class F>
 __device__ __forceinline__ Fe<F> ldc(const Const1& c) { return fe_load<F>(c.w[0].x, c.w[0].y, c.w[0].z, c.w[0].w, c.w[1].x, c.w[1].y, c.w[1].z, c.w[1].w); }
@@ -70,10 +59,10 @@ __global__ void __launch_bounds__(256) verify_tables_kernel(const uint4* __restr
     const uint4* up = u + 2 * (size_t)p * k;
     const bool hi = e >= lo_n;
     const u32 t = hi ? e - lo_n : e, nb = hi ? hbits : lbits, shift = hi ? lbits : 0;
-    Fe<F> r = hi ? ldv<F>(coef + 2 * p) : fe_one<F>();
+    Fe<F> r = hi ? load_fe<F>(coef + 2 * p) : fe_one<F>();
     for (u32 b = 0; b < nb; ++b)
-        if ((t >> b) & 1u) r = fe_mul(r, ldv<F>(up + 2 * (k - 1 - (shift + b))));
-    stv<F>(tables + 2 * ((size_t)p * entries + e), r);
+        if ((t >> b) & 1u) r = fe_mul(r, load_fe<F>(up + 2 * (k - 1 - (shift + b))));
+    store_fe<F>(tables + 2 * ((size_t)p * entries + e), r);
 }
 
 // g[i] = alpha g[i] + sum_p hi_p[i >> L] lo_p[i & (2^L - 1)] over [blockIdx.x * span, + span).  LDS: the low tables of all proofs are
@@ -103,14 +92,14 @@ __global__ void __launch_bounds__(256) verify_apply_kernel(uint4* __restrict__ g
         Fe<F> acc = fe_zero<F>();
         for (u32 p = 0; p < count; ++p) {
             const uint4* tp = tables + 2 * (size_t)p * entries;
-            const Fe<F> l = LDS ? ldv<F>(lds_lo + 2 * ((size_t)p * lo_n + lo)) : ldv<F>(tp + 2 * lo);
-            acc = fe_add(acc, fe_mul(ldv<F>(tp + 2 * (lo_n + hi)), l));
+            const Fe<F> l = LDS ? load_fe<F>(lds_lo + 2 * ((size_t)p * lo_n + lo)) : load_fe<F>(tp + 2 * lo);
+            acc = fe_add(acc, fe_mul(load_fe<F>(tp + 2 * (lo_n + hi)), l));
         }
         if (!fresh) {
-            const Fe<F> old = ldv<F>(g + 2 * i);
+            const Fe<F> old = load_fe<F>(g + 2 * i);
             acc = fe_add(acc, unit_alpha ? old : fe_mul(old, ldc<F>(alpha)));
         }
-        stv<F>(g + 2 * i, acc);
+        store_fe<F>(g + 2 * i, acc);
     }
 }
 
@@ -119,19 +108,19 @@ template <class F>
 __global__ void __launch_bounds__(256) verify_scale_kernel(uint4* __restrict__ g, size_t n, const Const1 f) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    stv<F>(g + 2 * i, fe_mul(ldv<F>(g + 2 * i), ldc<F>(f)));
+    store_fe<F>(g + 2 * i, fe_mul(load_fe<F>(g + 2 * i), ldc<F>(f)));
 }
 // MSM::add_to_g_scalars / add_msm: g[i] += h[i]
 template <class F>
 __global__ void __launch_bounds__(256) verify_add_kernel(uint4* __restrict__ g, const uint4* __restrict__ h, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    stv<F>(g + 2 * i, fe_add(ldv<F>(g + 2 * i), ldv<F>(h + 2 * i)));
+    store_fe<F>(g + 2 * i, fe_add(load_fe<F>(g + 2 * i), load_fe<F>(h + 2 * i)));
 }
 // MSM::add_constant_term: g[0] += c
 template <class F>
 __global__ void verify_add_constant_kernel(uint4* __restrict__ g, const Const1 c) {
-    if (threadIdx.x == 0) stv<F>(g, fe_add(ldv<F>(g), ldc<F>(c)));
+    if (threadIdx.x == 0) store_fe<F>(g, fe_add(load_fe<F>(g), ldc<F>(c)));
 }
 
 // the low tables go to LDS up to this size: two workgroups of the apply kernel per CU (160 KiB of LDS each)
@@ -160,14 +149,14 @@ void host_add(uint64_t* acc, const uint64_t* b) {
     memcpy(acc, &r, 32);
 }
 void smul(int curve, const uint64_t* a, const uint64_t* b, uint64_t* out) {  // scalars of `curve`: pallas -> Fq, vesta -> Fp
-    if (curve == TRH_PALLAS) host_mul<FqParams>(a, b, out); else host_mul<FpParams>(a, b, out);
+    with_curve(curve, [&](auto cv) { host_mul<typename decltype(cv)::Scalar>(a, b, out); });
 }
 void sadd(int curve, uint64_t* acc, const uint64_t* b) {
-    if (curve == TRH_PALLAS) host_add<FqParams>(acc, b); else host_add<FpParams>(acc, b);
+    with_curve(curve, [&](auto cv) { host_add<typename decltype(cv)::Scalar>(acc, b); });
 }
 bool is_one_mont(int curve, const uint64_t* v) {
     FeMem one;
-    if (curve == TRH_PALLAS) fe_store(fe_one<FqParams>(), one); else fe_store(fe_one<FpParams>(), one);
+    with_curve(curve, [&](auto cv) { fe_store(fe_one<typename decltype(cv)::Scalar>(), one); });
     return memcmp(&one, v, 32) == 0;
 }
 
@@ -186,16 +175,14 @@ int add_g(trh_ipa_msm* m, const void* src, hipStream_t s) {
         m->has_g = true;
         return TRH_OK;
     }
-    if (m->curve == TRH_PALLAS) hipLaunchKernelGGL((verify_add_kernel<FqParams>), dim3(blocks_of(m->n)), dim3(256), 0, s, (uint4*)m->scalars.p, (const uint4*)src, m->n);
-    else hipLaunchKernelGGL((verify_add_kernel<FpParams>), dim3(blocks_of(m->n)), dim3(256), 0, s, (uint4*)m->scalars.p, (const uint4*)src, m->n);
+    with_curve(m->curve, [&](auto cv) { hipLaunchKernelGGL((verify_add_kernel<typename decltype(cv)::Scalar>), dim3(blocks_of(m->n)), dim3(256), 0, s, (uint4*)m->scalars.p, (const uint4*)src, m->n); });
     TRH_HIP_TRY(hipGetLastError());
     return TRH_OK;
 }
 
 int scale_g(trh_ipa_msm* m, const uint64_t* f, hipStream_t s) {
     if (!m->has_g) return TRH_OK;
-    if (m->curve == TRH_PALLAS) hipLaunchKernelGGL((verify_scale_kernel<FqParams>), dim3(blocks_of(m->n)), dim3(256), 0, s, (uint4*)m->scalars.p, m->n, const1(f));
-    else hipLaunchKernelGGL((verify_scale_kernel<FpParams>), dim3(blocks_of(m->n)), dim3(256), 0, s, (uint4*)m->scalars.p, m->n, const1(f));
+    with_curve(m->curve, [&](auto cv) { hipLaunchKernelGGL((verify_scale_kernel<typename decltype(cv)::Scalar>), dim3(blocks_of(m->n)), dim3(256), 0, s, (uint4*)m->scalars.p, m->n, const1(f)); });
     TRH_HIP_TRY(hipGetLastError());
     return TRH_OK;
 }
@@ -317,8 +304,7 @@ int trh_ipa_msm_add_constant_term(trh_ipa_msm_t m, const uint64_t c[4]) {
     Range range("trh_ipa_msm_add_constant_term");
     TRH_TRY(check_msm(m, "ipa_msm_add_constant_term"));
     TRH_TRY(ensure_g(m, m->stream));
-    if (m->curve == TRH_PALLAS) hipLaunchKernelGGL((verify_add_constant_kernel<FqParams>), dim3(1), dim3(64), 0, m->stream, (uint4*)m->scalars.p, const1(c));
-    else hipLaunchKernelGGL((verify_add_constant_kernel<FpParams>), dim3(1), dim3(64), 0, m->stream, (uint4*)m->scalars.p, const1(c));
+    with_curve(m->curve, [&](auto cv) { hipLaunchKernelGGL((verify_add_constant_kernel<typename decltype(cv)::Scalar>), dim3(1), dim3(64), 0, m->stream, (uint4*)m->scalars.p, const1(c)); });
     TRH_HIP_TRY(hipGetLastError());
     return TRH_OK;
 }
@@ -365,8 +351,7 @@ int trh_ipa_msm_use_challenges(trh_ipa_msm_t m, size_t count, const uint64_t* u,
         if (weights) smul(m->curve, weights + 4 * p, neg_c + 4 * p, coef + 4 * p);
         else memcpy(coef + 4 * p, neg_c + 4 * p, 32);
     }
-    if (m->curve == TRH_PALLAS) return use_challenges_t<FqParams>(m, count, hp.data(), alpha, s);
-    return use_challenges_t<FpParams>(m, count, hp.data(), alpha, s);
+    return with_curve(m->curve, [&](auto cv) { return use_challenges_t<typename decltype(cv)::Scalar>(m, count, hp.data(), alpha, s); });
 }
 
 int trh_ipa_msm_scale(trh_ipa_msm_t m, const uint64_t factor[4], void* stream) {

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "devmem.h"
 
 namespace trh {
 namespace {
@@ -31,12 +32,6 @@ constexpr int THREADS = 256;
 constexpr int ITEMS = TILE / THREADS;
 constexpr int RADIX_BITS = 4, RADIX = 1 << RADIX_BITS, PASSES = 64 / RADIX_BITS;
 constexpr int FAST_KEY_BITS = 48;  // varying bits the fast path sorts by (see select_limb_kernel)
-
-template <class F>
-__device__ __forceinline__ Fe<F> ldf(const uint4* p) {
-    uint4 a = p[0], b = p[1];
-    return fe_load<F>(a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w);
-}
 
 // column c of the batch: c < batch the input of lookup c, else the table of lookup c - batch
 __device__ __forceinline__ const uint4* column_ptr(const uint4* in, const uint4* tab, size_t stride, u32 batch, u32 c) {
@@ -51,7 +46,7 @@ __global__ void __launch_bounds__(256) canon_planes_kernel(const uint4* __restri
     const u32 c = blockIdx.y;
     if (i >= n) return;
     u32 w[8];
-    fe_store(fe_from_mont(ldf<F>(column_ptr(in, tab, stride, batch, c) + 2 * i)), w);
+    fe_store(fe_from_mont(load_fe<F>(column_ptr(in, tab, stride, batch, c) + 2 * i)), w);
     u64* pl = planes + (size_t)c * 4 * n;
     for (int k = 0; k < 4; ++k) pl[(size_t)k * n + i] = (u64)w[2 * k] | ((u64)w[2 * k + 1] << 32);
     perm[(size_t)c * n + i] = (u32)i;
@@ -555,15 +550,14 @@ extern "C" {
 int trh_lookup_permute_batch_dev(int field, const void* inputs_dev, const void* tables_dev, size_t usable_rows, size_t row_stride, size_t batch, void* out_inputs_dev,
                                  void* out_tables_dev, void* stream) {
     TRH_TRY(require_init());
-    if (field != TRH_FP && field != TRH_FQ) { set_error("unknown field id %d", field); return TRH_EINVAL; }
+    TRH_TRY(check_field(field));
     if (usable_rows && batch && (!inputs_dev || !tables_dev || !out_inputs_dev || !out_tables_dev)) { set_error("lookup_permute: null pointer"); return TRH_EINVAL; }
     if (out_inputs_dev == inputs_dev || out_tables_dev == tables_dev || out_inputs_dev == out_tables_dev) { set_error("lookup_permute: outputs must not alias the inputs"); return TRH_EINVAL; }
     if (usable_rows >= ((size_t)1 << 31) || row_stride < usable_rows) { set_error("lookup_permute: bad row count / stride"); return TRH_EINVAL; }
     if (!usable_rows || !batch) return TRH_OK;
     TRH_ENTER(stream);
     Range range("trh_lookup_permute_batch_dev");
-    if (field == TRH_FP) return lookup_permute_all_t<FpParams>(inputs_dev, tables_dev, usable_rows, row_stride, batch, out_inputs_dev, out_tables_dev, (hipStream_t)stream);
-    return lookup_permute_all_t<FqParams>(inputs_dev, tables_dev, usable_rows, row_stride, batch, out_inputs_dev, out_tables_dev, (hipStream_t)stream);
+    return with_field(field, [&](auto f) { return lookup_permute_all_t<decltype(f)>(inputs_dev, tables_dev, usable_rows, row_stride, batch, out_inputs_dev, out_tables_dev, (hipStream_t)stream); });
 }
 
 int trh_lookup_permute_dev(int field, const void* input_dev, const void* table_dev, size_t usable_rows, void* out_input_dev, void* out_table_dev, void* stream) {

@@ -23,6 +23,7 @@
 #include <string.h>
 
 #include "ctx.h"
+#include "devmem.h"
 #include "curve_q4.h"
 #include "hostcombine.h"
 #include "hosthelper.h"
@@ -486,43 +487,6 @@ __global__ void __launch_bounds__(RANGE_BLOCK) msm_bucket_ranges_kernel(u32* __r
 }
 
 // ---------------------------------------------------------------------------------------
-// 4. accumulate
-// ---------------------------------------------------------------------------------------
-template <class BF>
-__device__ __forceinline__ Affine<BF> load_affine(const uint4* __restrict__ bases, u32 idx) {
-    const uint4* p = bases + (size_t)idx * 4;
-    uint4 a = p[0], b = p[1], c = p[2], d = p[3];
-    Affine<BF> r;
-    r.x = fe_load<BF>(a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w);
-    r.y = fe_load<BF>(c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w);
-    return r;
-}
-template <class BF>
-__device__ __forceinline__ void store_fe4(uint4* p, const Fe<BF>& v) {
-    u32 w[8];
-    fe_store(v, w);
-    p[0] = make_uint4(w[0], w[1], w[2], w[3]);
-    p[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
-template <class BF>
-__device__ __forceinline__ Fe<BF> load_fe4(const uint4* p) {
-    uint4 a = p[0], b = p[1];
-    return fe_load<BF>(a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w);
-}
-template <class BF>
-__device__ __forceinline__ void store_xyzz(XYZZMem* dst, const XYZZ<BF>& v) {
-    uint4* p = (uint4*)dst;
-    store_fe4(p, v.x); store_fe4(p + 2, v.y); store_fe4(p + 4, v.zz); store_fe4(p + 6, v.zzz);
-}
-template <class BF>
-__device__ __forceinline__ XYZZ<BF> load_xyzz(const XYZZMem* src) {
-    const uint4* p = (const uint4*)src;
-    XYZZ<BF> v;
-    v.x = load_fe4<BF>(p); v.y = load_fe4<BF>(p + 2); v.zz = load_fe4<BF>(p + 4); v.zzz = load_fe4<BF>(p + 6);
-    return v;
-}
-
-// ---------------------------------------------------------------------------------------
 // 4. balanced accumulation in the lazy domain.
 //   convert   bases (Montgomery R = 2^256) -> 128-byte records of ready limbs in the signed lazy domain (R'' = 2^261; ctx.h ZREC),
 //             once per base set (owned handles keep them) or per MSM
@@ -553,26 +517,6 @@ __global__ void __launch_bounds__(256) msm_convert_bases_kernel(const uint4* __r
     uint4 a = p[0], b = p[1], c = p[2], d = p[3];
     // 0 -> 0: the identity stays (0, 0)
     store_zrec(out + i * (ZREC / 16), fy_from_fe(fe_load<BF>(a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w)), fy_from_fe(fe_load<BF>(c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w)));
-}
-
-template <class BF>
-__device__ __forceinline__ void store_raw(XYZZzMem* dst, const XYZZz<BF>& v) {
-    uint4* p = (uint4*)dst;
-    const u32* w = (const u32*)&v;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) p[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
-}
-template <class BF>
-__device__ __forceinline__ XYZZz<BF> load_raw(const XYZZzMem* src) {
-    const uint4* p = (const uint4*)src;
-    XYZZz<BF> v;
-    u32* w = (u32*)&v;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        uint4 q = p[k];
-        w[4 * k] = q.x; w[4 * k + 1] = q.y; w[4 * k + 2] = q.z; w[4 * k + 3] = q.w;
-    }
-    return v;
 }
 
 template <class BF>
@@ -780,7 +724,7 @@ __global__ void __launch_bounds__(256) msm_combine_kernel(const u32* __restrict_
     }
     if constexpr (G > 1) {
         for (int off = G / 2; off > 0; off >>= 1) {
-            XYZZz<BF> o;
+            XYZZz<BF> o;  // shfl_down_point(acc, off, G) written out: through the call the compiler allocates this kernel's registers differently
 #pragma unroll
             for (int i = 0; i < NLIMBS; ++i) {
                 o.x.l[i] = __shfl_down(acc.x.l[i], off, G); o.y.l[i] = __shfl_down(acc.y.l[i], off, G);
@@ -973,7 +917,7 @@ __global__ void __launch_bounds__(256) msm_window_sum_q4_kernel(const XYZZzMem* 
     if (Qi == 0) {
         const bool id = q4_is_identity(v);
         const Fe<BF> c = id ? fe_zero<BF>() : fy_to_fe(v);
-        store_fe4((uint4*)&window_sums[j] + 2 * q, c);
+        store_fe((uint4*)&window_sums[j] + 2 * q, c);
     }
 }
 
@@ -1017,8 +961,8 @@ __global__ void __launch_bounds__(256) bases_generate_kernel(u64 s0, u64 d, u64 
     }
     Affine<BF> a = xyzz_to_affine(acc);
     uint4* p = out + i * 4;
-    store_fe4(p, a.x);
-    store_fe4(p + 2, a.y);
+    store_fe(p, a.x);
+    store_fe(p + 2, a.y);
 }
 
 // fixed-base table: out[j * n + i] = 2^(c j) * P_i in the lazy affine form (identity stays all-zero)
@@ -1336,17 +1280,6 @@ __global__ void __launch_bounds__(256) msm_sparse_remap_kernel(u32* __restrict__
 constexpr u32 SMALL_NBK = 1u << (SMALL_C - 1);  // 16
 struct SmallBias { u32 w[9]; };
 
-template <class BF>
-__device__ __forceinline__ XYZZz<BF> shfl_down_point(const XYZZz<BF>& v, int off, int width) {
-    XYZZz<BF> o;
-#pragma unroll
-    for (int l = 0; l < NLIMBS; ++l) {
-        o.x.l[l] = __shfl_down(v.x.l[l], off, width); o.y.l[l] = __shfl_down(v.y.l[l], off, width);
-        o.zz.l[l] = __shfl_down(v.zz.l[l], off, width); o.zzz.l[l] = __shfl_down(v.zzz.l[l], off, width);
-    }
-    return o;
-}
-
 template <class SF, class BF, bool Q4>
 __global__ void __launch_bounds__(256) msm_small_kernel(const uint4* __restrict__ bases_z, const uint4* __restrict__ scalars, u32 n, int mont, size_t sstride,
                                                         const uint4* __restrict__ tails, const SmallBias H, XYZZMem* __restrict__ window_sums) {
@@ -1460,7 +1393,7 @@ __global__ void __launch_bounds__(256) msm_small_kernel(const uint4* __restrict_
             const bool id = q4_is_identity(v);
             uint4* dst = (uint4*)&window_sums[(size_t)z * W + j] + 2 * q;
             if (id) { dst[0] = make_uint4(0, 0, 0, 0); dst[1] = make_uint4(0, 0, 0, 0); }
-            else store_fe4(dst, fy_to_fe(v));
+            else store_fe(dst, fy_to_fe(v));
         }
     }
 }
@@ -2082,39 +2015,32 @@ int msm_build_table(int curve, const void* bases_dev, size_t n, int c, void* tab
     if (!n) return TRH_OK;
     const int W = num_windows(c);
     const unsigned gb = (unsigned)((n + 255) / 256);
-    if (curve == TRH_PALLAS) hipLaunchKernelGGL((msm_table_kernel<FpParams>), dim3(gb), dim3(256), 0, s, (const uint4*)bases_dev, (uint4*)table_dev, n, c, W);
-    else hipLaunchKernelGGL((msm_table_kernel<FqParams>), dim3(gb), dim3(256), 0, s, (const uint4*)bases_dev, (uint4*)table_dev, n, c, W);
+    with_curve(curve, [&](auto cv) { hipLaunchKernelGGL((msm_table_kernel<typename decltype(cv)::Base>), dim3(gb), dim3(256), 0, s, (const uint4*)bases_dev, (uint4*)table_dev, n, c, W); });
     TRH_HIP_TRY(hipGetLastError());
     return TRH_OK;
 }
 int msm_enqueue(int curve, const void* bases_dev, const void* bases_z, const void* scalars_dev, size_t n, size_t batch, size_t stride, int mont, hipStream_t s, const MsmFixedBase* fb,
                 const void* tails_dev, MsmFlags flags) {
     const MsmCall a{bases_dev, bases_z, scalars_dev, tails_dev, n, batch, stride, mont, s, fb, flags};
-    // pallas: base Fp, scalar Fq; vesta: base Fq, scalar Fp
-    if (curve == TRH_PALLAS) return msm_enqueue_t<FqParams, FpParams>(a);
-    return msm_enqueue_t<FpParams, FqParams>(a);
+    return with_curve(curve, [&](auto cv) { return msm_enqueue_t<typename decltype(cv)::Scalar, typename decltype(cv)::Base>(a); });
 }
 int msm_convert_bases(int curve, const void* in_dev, void* out_dev, size_t n, hipStream_t s) {
     if (!n) return TRH_OK;
     const unsigned gb = (unsigned)((n + 255) / 256);
-    if (curve == TRH_PALLAS) hipLaunchKernelGGL((msm_convert_bases_kernel<FpParams>), dim3(gb), dim3(256), 0, s, (const uint4*)in_dev, (uint4*)out_dev, n);
-    else hipLaunchKernelGGL((msm_convert_bases_kernel<FqParams>), dim3(gb), dim3(256), 0, s, (const uint4*)in_dev, (uint4*)out_dev, n);
+    with_curve(curve, [&](auto cv) { hipLaunchKernelGGL((msm_convert_bases_kernel<typename decltype(cv)::Base>), dim3(gb), dim3(256), 0, s, (const uint4*)in_dev, (uint4*)out_dev, n); });
     TRH_HIP_TRY(hipGetLastError());
     return TRH_OK;
 }
 int msm_finish(int curve, hipStream_t s, u64* out_xyz, size_t batch) {
-    if (curve == TRH_PALLAS) return msm_finish_t<FpParams>(s, out_xyz, batch);
-    return msm_finish_t<FqParams>(s, out_xyz, batch);
+    return with_curve(curve, [&](auto cv) { return msm_finish_t<typename decltype(cv)::Base>(s, out_xyz, batch); });
 }
 int point_sum_host(int curve, const u64* pts, size_t count, u64* out) {
-    if (curve == TRH_PALLAS) return point_sum_host_t<FpParams>(pts, count, out);
-    return point_sum_host_t<FqParams>(pts, count, out);
+    return with_curve(curve, [&](auto cv) { return point_sum_host_t<typename decltype(cv)::Base>(pts, count, out); });
 }
 int bases_generate_device(int curve, u64 s0, u64 d, u64 first, size_t n, void* out_dev, hipStream_t s) {
     if (!n) return TRH_OK;
     const unsigned gb = (unsigned)((n + 255) / 256);
-    if (curve == TRH_PALLAS) hipLaunchKernelGGL((bases_generate_kernel<FpParams>), dim3(gb), dim3(256), 0, s, s0, d, first, n, (uint4*)out_dev);
-    else hipLaunchKernelGGL((bases_generate_kernel<FqParams>), dim3(gb), dim3(256), 0, s, s0, d, first, n, (uint4*)out_dev);
+    with_curve(curve, [&](auto cv) { hipLaunchKernelGGL((bases_generate_kernel<typename decltype(cv)::Base>), dim3(gb), dim3(256), 0, s, s0, d, first, n, (uint4*)out_dev); });
     TRH_HIP_TRY(hipGetLastError());
     return TRH_OK;
 }

@@ -20,6 +20,7 @@
 #include <string.h>
 
 #include "ctx.h"
+#include "devmem.h"
 #include "hostplan.h"
 
 namespace trh {
@@ -35,18 +36,6 @@ struct alignas(16) Half {  // 16 bytes of a field element
     u32 w[4];
 };
 
-template <class F>
-__device__ __forceinline__ Fe<F> load_fe(const uint4* __restrict__ p) {
-    uint4 a = p[0], b = p[1];
-    return fe_load<F>(a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w);
-}
-template <class F>
-__device__ __forceinline__ void store_fe(uint4* __restrict__ p, const Fe<F>& v) {
-    u32 w[8];
-    fe_store(v, w);
-    p[0] = make_uint4(w[0], w[1], w[2], w[3]);
-    p[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
 // LDS holds each element in memory format as two 16-byte halves in separate planes: consecutive
 // lanes touch consecutive 16-byte slots, which ds_read_b128 / ds_write_b128 serve conflict-free
 template <class F>
@@ -269,11 +258,6 @@ __global__ void __launch_bounds__((1 << TLOG) >> LG) ntt_passg_kernel(const uint
 // Bounds (units of m): inputs |v| < 1.13 (canonical words, a product); round 0: < 2 after the first trivial stage, < 4 after the
 // second; every later stage adds a product in (-0.24, 1.24): |v| < 4 + 1.24 (s - 2) <= 12.7 for s <= 9, inside the 16 of the domain;
 // lazy limbs are at most N + L1 = 1.5 * 2^30 in magnitude, and 9 * 1.5 * 2^30 * 2^29 + the reduction terms stays below 2^63.
-template <class F>
-__device__ __forceinline__ Fy<F> load_fy(const uint4* __restrict__ p) {
-    uint4 a = p[0], b = p[1];
-    return fy_load<F>(a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w);
-}
 template <class F>
 __device__ __forceinline__ Fy<F> lds_load_limbs_y(const uint4* pa, const uint4* pb, const u32* pc, int idx) {
     const uint4 a = pa[idx], b = pb[idx];
@@ -827,15 +811,14 @@ int ntt_device(int field, void* a_dev, uint32_t log_n, const u64 omega[4], size_
 #undef TRH_PASSY_ATTR
         ctx().attr_done |= ATTR_NTT;
     }
-    if (field == TRH_FP) return ntt_device_t<FpParams>(a_dev, log_n, omega, batch, s, fu, scale);
-    return ntt_device_t<FqParams>(a_dev, log_n, omega, batch, s, fu, scale);
+    return with_field(field, [&](auto f) { return ntt_device_t<decltype(f)>(a_dev, log_n, omega, batch, s, fu, scale); });
 }
 
 int ntt_prepare(int field, uint32_t log_n, const u64 omega[4], const u64* scale, size_t batch, uint32_t blocks, hipStream_t s) {
     if (log_n == 0 || log_n > 27 || batch == 0) return TRH_OK;
     Ctx& c = ctx();
     TwiddleEntry* t = find_tables(field, (int)log_n, omega, scale);
-    if (!t) TRH_TRY(field == TRH_FP ? build_tables<FpParams>((int)log_n, omega, scale, s, &t) : build_tables<FqParams>((int)log_n, omega, scale, s, &t));
+    if (!t) TRH_TRY(with_field(field, [&](auto f) { return build_tables<decltype(f)>((int)log_n, omega, scale, s, &t); }));
     int sizes[8], P = 0, tlog = TILE_LOG;
     plan_passes((int)log_n, sizes, &P, &tlog);
     const size_t N = (size_t)1 << log_n;
@@ -859,8 +842,7 @@ int field_scale_periodic(int field, void* a_dev, size_t rows, size_t row_len, si
     const size_t n = rows * active_len;
     if (!n) return TRH_OK;
     const unsigned gb = (unsigned)((n + 255) / 256);
-    if (field == TRH_FP) hipLaunchKernelGGL((field_scale_periodic_kernel<FpParams>), dim3(gb), dim3(256), 0, s, (uint4*)a_dev, rows, row_len, active_len, (const uint4*)factors_dev, period);
-    else hipLaunchKernelGGL((field_scale_periodic_kernel<FqParams>), dim3(gb), dim3(256), 0, s, (uint4*)a_dev, rows, row_len, active_len, (const uint4*)factors_dev, period);
+    with_field(field, [&](auto f) { hipLaunchKernelGGL((field_scale_periodic_kernel<decltype(f)>), dim3(gb), dim3(256), 0, s, (uint4*)a_dev, rows, row_len, active_len, (const uint4*)factors_dev, period); });
     TRH_HIP_TRY(hipGetLastError());
     return TRH_OK;
 }
@@ -878,8 +860,7 @@ int ntt_block_table_build(int field, void* table_dev, uint32_t blocks, uint32_t 
     TRH_HIP_TRY(hipStreamSynchronize(s));  // h is a stack buffer
     const size_t M = (size_t)blocks << log_n;
     const unsigned gb = (unsigned)((M + 255) / 256);
-    if (field == TRH_FP) hipLaunchKernelGGL((ntt_block_table_kernel<FpParams>), dim3(gb), dim3(256), 0, s, (uint4*)table_dev, blocks, (int)log_n, (const uint4*)slot);
-    else hipLaunchKernelGGL((ntt_block_table_kernel<FqParams>), dim3(gb), dim3(256), 0, s, (uint4*)table_dev, blocks, (int)log_n, (const uint4*)slot);
+    with_field(field, [&](auto f) { hipLaunchKernelGGL((ntt_block_table_kernel<decltype(f)>), dim3(gb), dim3(256), 0, s, (uint4*)table_dev, blocks, (int)log_n, (const uint4*)slot); });
     TRH_HIP_TRY(hipGetLastError());
     return TRH_OK;
 }
@@ -888,8 +869,7 @@ int ntt_block_scale(int field, const void* in_dev, void* out_dev, size_t transfo
     const size_t total = transforms << log_n;
     if (!total) return TRH_OK;
     const unsigned gb = (unsigned)((total + 255) / 256);
-    if (field == TRH_FP) hipLaunchKernelGGL((ntt_block_scale_kernel<FpParams>), dim3(gb), dim3(256), 0, s, (const uint4*)in_dev, (uint4*)out_dev, transforms, blocks, (int)log_n, (const uint4*)table_dev, in_per_block ? 1 : 0);
-    else hipLaunchKernelGGL((ntt_block_scale_kernel<FqParams>), dim3(gb), dim3(256), 0, s, (const uint4*)in_dev, (uint4*)out_dev, transforms, blocks, (int)log_n, (const uint4*)table_dev, in_per_block ? 1 : 0);
+    with_field(field, [&](auto f) { hipLaunchKernelGGL((ntt_block_scale_kernel<decltype(f)>), dim3(gb), dim3(256), 0, s, (const uint4*)in_dev, (uint4*)out_dev, transforms, blocks, (int)log_n, (const uint4*)table_dev, in_per_block ? 1 : 0); });
     TRH_HIP_TRY(hipGetLastError());
     return TRH_OK;
 }

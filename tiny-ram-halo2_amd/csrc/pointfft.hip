@@ -13,9 +13,6 @@
 namespace trh {
 namespace {
 
-template <class F>
-__device__ __forceinline__ XYZZ<F> ld_xyzz(const XYZZMem* p) { return xyzz_load<F>(*p); }
-
 // work[bitrev(i)] = points[i] as XYZZ
 template <class BF>
 __global__ void __launch_bounds__(256) pfft_load_kernel(const AffineMem* __restrict__ pts, XYZZMem* __restrict__ work, u32 log_n) {
@@ -56,8 +53,8 @@ __global__ void __launch_bounds__(256) pfft_stage_kernel(XYZZMem* __restrict__ w
     if (bf >= (1u << (log_n - 1))) return;
     const u32 half = 1u << st, pos = bf & (half - 1u);
     const u32 i0 = ((bf >> st) << (st + 1)) | pos, i1 = i0 + half;
-    const XYZZ<BF> a = ld_xyzz<BF>(&work[i0]);
-    XYZZ<BF> t = ld_xyzz<BF>(&work[i1]);
+    const XYZZ<BF> a = xyzz_load<BF>(work[i0]);
+    XYZZ<BF> t = xyzz_load<BF>(work[i1]);
     if (pos) t = scalar_mul<BF>(t, tw[pos << (log_n - 1 - st)].w);
     xyzz_store(xyzz_add(a, t), work[i0]);
     xyzz_store(xyzz_add(a, xyzz_neg(t)), work[i1]);
@@ -67,7 +64,7 @@ template <class BF>
 __global__ void __launch_bounds__(256) pfft_finish_kernel(const XYZZMem* __restrict__ work, AffineMem* __restrict__ pts, u32 n, const FeMem* __restrict__ scale) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    XYZZ<BF> p = ld_xyzz<BF>(&work[i]);
+    XYZZ<BF> p = xyzz_load<BF>(work[i]);
     if (scale) p = scalar_mul<BF>(p, scale->w);
     aff_store(xyzz_to_affine(p), pts[i]);
 }
@@ -109,14 +106,12 @@ using namespace trh;
 
 extern "C" int trh_point_fft_dev(int curve, void* points_dev, uint32_t log_n, const uint64_t omega[4], const uint64_t* scale_or_null, void* stream) {
     TRH_TRY(require_init());
-    if (curve != TRH_PALLAS && curve != TRH_VESTA) { set_error("unknown curve id %d", curve); return TRH_EINVAL; }
+    TRH_TRY(check_curve(curve));
     if (!points_dev || !omega) { set_error("point_fft: null pointer"); return TRH_EINVAL; }
     if (log_n > 24) { set_error("point_fft: log_n %u > 24 unsupported", log_n); return TRH_EINVAL; }
     TRH_ENTER(stream);
     Range range("trh_point_fft_dev");
     Ctx& c = ctx();
     (void)c;
-    // pallas: scalar field Fq, base field Fp
-    if (curve == TRH_PALLAS) return point_fft_t<FqParams, FpParams>(points_dev, log_n, omega, scale_or_null, (hipStream_t)stream);
-    return point_fft_t<FpParams, FqParams>(points_dev, log_n, omega, scale_or_null, (hipStream_t)stream);
+    return with_curve(curve, [&](auto cv) { return point_fft_t<typename decltype(cv)::Scalar, typename decltype(cv)::Base>(points_dev, log_n, omega, scale_or_null, (hipStream_t)stream); });
 }

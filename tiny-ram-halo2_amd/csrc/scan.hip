@@ -8,22 +8,10 @@
 #include <string.h>
 
 #include "ctx.h"
+#include "devmem.h"
 
 namespace trh {
 namespace {
-
-template <class F>
-__device__ __forceinline__ Fe<F> ldf(const uint4* p) {
-    uint4 a = p[0], b = p[1];
-    return fe_load<F>(a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w);
-}
-template <class F>
-__device__ __forceinline__ void stf(uint4* p, const Fe<F>& v) {
-    u32 w[8];
-    fe_store(v, w);
-    p[0] = make_uint4(w[0], w[1], w[2], w[3]);
-    p[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
 
 constexpr int INV_CHUNK = 64;  // elements per thread: one field inversion (~380 multiplies) per chunk
 
@@ -39,18 +27,18 @@ __global__ void __launch_bounds__(256) batch_invert_kernel(uint4* __restrict__ a
     Fe<F> acc = fe_one<F>();
     for (int i = 0; i < cnt; ++i) {
         const size_t e = base + (size_t)i * 256;
-        stf<F>(scratch + 2 * e, acc);  // product of the non-zero elements before this one
-        const Fe<F> v = ldf<F>(a + 2 * e);
+        store_fe<F>(scratch + 2 * e, acc);  // product of the non-zero elements before this one
+        const Fe<F> v = load_fe<F>(a + 2 * e);
         if (!fe_is_zero(v)) acc = fe_mul(acc, v);
     }
     Fe<F> inv = fe_inv(acc);
     for (int i = cnt; i-- > 0;) {
         const size_t e = base + (size_t)i * 256;
-        const Fe<F> v = ldf<F>(a + 2 * e);
+        const Fe<F> v = load_fe<F>(a + 2 * e);
         if (fe_is_zero(v)) continue;
-        Fe<F> r = fe_mul(inv, ldf<F>(scratch + 2 * e));
-        if (num) r = fe_mul(r, ldf<F>(num + 2 * e));
-        stf<F>(a + 2 * e, r);
+        Fe<F> r = fe_mul(inv, load_fe<F>(scratch + 2 * e));
+        if (num) r = fe_mul(r, load_fe<F>(num + 2 * e));
+        store_fe<F>(a + 2 * e, r);
         inv = fe_mul(inv, v);
     }
 }
@@ -71,11 +59,11 @@ __global__ void __launch_bounds__(256) product_terms_kernel(const DevTerm* __res
     Fe<F> acc = fe_one<F>();
     for (u32 t = t0; t < t1; ++t) {  // uniform: the descriptors are scalar loads
         const DevTerm& d = terms[t];
-        Fe<F> v = fe_add(ldf<F>(d.x + 2 * i), fe_load<F>(d.g));
-        if (d.y) v = fe_add(v, fe_mul(ldf<F>(d.y + 2 * i), fe_load<F>(d.c)));
+        Fe<F> v = fe_add(load_fe<F>(d.x + 2 * i), fe_load<F>(d.g));
+        if (d.y) v = fe_add(v, fe_mul(load_fe<F>(d.y + 2 * i), fe_load<F>(d.c)));
         acc = t == t0 ? v : fe_mul(acc, v);
     }
-    stf<F>(out + 2 * ((size_t)r * n + i), acc);
+    store_fe<F>(out + 2 * ((size_t)r * n + i), acc);
 }
 
 constexpr int SCAN_PER_THREAD = 16;
@@ -119,10 +107,10 @@ __global__ void __launch_bounds__(256) scan_block_totals_kernel(const uint4* __r
     const size_t lo = (size_t)blockIdx.x * SCAN_BLOCK + (size_t)threadIdx.x * SCAN_PER_THREAD;
     Fe<F> p = OP::id();
     for (int k = 0; k < SCAN_PER_THREAD; ++k)
-        if (lo + k < n) p = OP::op(p, ldf<F>(a + 2 * (lo + k)));
+        if (lo + k < n) p = OP::op(p, load_fe<F>(a + 2 * (lo + k)));
     Fe<F> total;
     block_exclusive_scan<F, OP>(sh, p, total);
-    if (threadIdx.x == 0) stf<F>(totals + 2 * blockIdx.x, total);
+    if (threadIdx.x == 0) store_fe<F>(totals + 2 * blockIdx.x, total);
 }
 // phase 2 (one workgroup): exclusive scan of the block totals, in place
 template <class F, class OP>
@@ -133,13 +121,13 @@ __global__ void __launch_bounds__(256) scan_totals_kernel(uint4* __restrict__ to
     const u32 lo = threadIdx.x * per;
     Fe<F> p = OP::id();
     for (u32 k = 0; k < per; ++k)
-        if (lo + k < count) p = OP::op(p, ldf<F>(totals + 2 * (lo + k)));
+        if (lo + k < count) p = OP::op(p, load_fe<F>(totals + 2 * (lo + k)));
     Fe<F> total;
     Fe<F> run = block_exclusive_scan<F, OP>(sh, p, total);
     for (u32 k = 0; k < per; ++k) {
         if (lo + k >= count) break;
-        const Fe<F> v = ldf<F>(totals + 2 * (lo + k));
-        stf<F>(totals + 2 * (lo + k), run);
+        const Fe<F> v = load_fe<F>(totals + 2 * (lo + k));
+        store_fe<F>(totals + 2 * (lo + k), run);
         run = OP::op(run, v);
     }
 }
@@ -153,14 +141,14 @@ __global__ void __launch_bounds__(256) scan_apply_kernel(const uint4* __restrict
     Fe<F> p = OP::id();
 #pragma unroll
     for (int k = 0; k < SCAN_PER_THREAD; ++k) {
-        vals[k] = lo + k < n ? ldf<F>(a + 2 * (lo + k)) : OP::id();
+        vals[k] = lo + k < n ? load_fe<F>(a + 2 * (lo + k)) : OP::id();
         p = OP::op(p, vals[k]);
     }
     Fe<F> total;
-    Fe<F> run = OP::op(block_exclusive_scan<F, OP>(sh, p, total), ldf<F>(totals + 2 * blockIdx.x));
+    Fe<F> run = OP::op(block_exclusive_scan<F, OP>(sh, p, total), load_fe<F>(totals + 2 * blockIdx.x));
 #pragma unroll
     for (int k = 0; k < SCAN_PER_THREAD; ++k) {
-        if (lo + k < n) stf<F>(out + 2 * (lo + k), run);
+        if (lo + k < n) store_fe<F>(out + 2 * (lo + k), run);
         run = OP::op(run, vals[k]);
     }
 }
@@ -188,22 +176,22 @@ __global__ void __launch_bounds__(256) lincomb_kernel(const uint4* __restrict__ 
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Fe<F> acc = fe_zero<F>();
-    for (u32 b = 0; b < batch; ++b) acc = fe_add(acc, fe_mul(ldf<F>(polys + 2 * ((size_t)b * n + i)), ldf<F>(coeffs + 2 * b)));
-    stf<F>(out + 2 * i, acc);
+    for (u32 b = 0; b < batch; ++b) acc = fe_add(acc, fe_mul(load_fe<F>(polys + 2 * ((size_t)b * n + i)), load_fe<F>(coeffs + 2 * b)));
+    store_fe<F>(out + 2 * i, acc);
 }
 // kate_division, step 1: t[m] = a[m] * z^m (pz = the powers of z)
 template <class F>
 __global__ void __launch_bounds__(256) mul_pointwise_kernel(const uint4* __restrict__ a, const uint4* __restrict__ b, uint4* __restrict__ out, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) stf<F>(out + 2 * i, fe_mul(ldf<F>(a + 2 * i), ldf<F>(b + 2 * i)));
+    if (i < n) store_fe<F>(out + 2 * i, fe_mul(load_fe<F>(a + 2 * i), load_fe<F>(b + 2 * i)));
 }
 // step 3: q[i - 1] = (total - P[i]) * zinv^i for i = 1..n-1, P = exclusive prefix sums of t, total = P[n-1] + t[n-1]
 template <class F>
 __global__ void __launch_bounds__(256) kate_finish_kernel(const uint4* __restrict__ t, const uint4* __restrict__ P, const uint4* __restrict__ pzinv, uint4* __restrict__ q, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x + 1;
     if (i >= n) return;
-    const Fe<F> total = fe_add(ldf<F>(P + 2 * (n - 1)), ldf<F>(t + 2 * (n - 1)));
-    stf<F>(q + 2 * (i - 1), fe_mul(fe_sub(total, ldf<F>(P + 2 * i)), ldf<F>(pzinv + 2 * i)));
+    const Fe<F> total = fe_add(load_fe<F>(P + 2 * (n - 1)), load_fe<F>(t + 2 * (n - 1)));
+    store_fe<F>(q + 2 * (i - 1), fe_mul(fe_sub(total, load_fe<F>(P + 2 * i)), load_fe<F>(pzinv + 2 * i)));
 }
 
 template <class F>
@@ -225,33 +213,27 @@ extern "C" {
 
 int trh_field_batch_invert_dev(int field, void* a_dev, size_t n, void* stream) {
     TRH_TRY(require_init());
-    if (field != TRH_FP && field != TRH_FQ) { set_error("unknown field id %d", field); return TRH_EINVAL; }
+    TRH_TRY(check_field(field));
     if (n && !a_dev) { set_error("batch_invert: null pointer"); return TRH_EINVAL; }
     if (!n) return TRH_OK;
     TRH_ENTER(stream);
     Range range("trh_field_batch_invert_dev");
-    Ctx& c = ctx();
-    (void)c;
-    if (field == TRH_FP) return batch_invert_t<FpParams>(a_dev, nullptr, n, (hipStream_t)stream);
-    return batch_invert_t<FqParams>(a_dev, nullptr, n, (hipStream_t)stream);
+    return with_field(field, [&](auto f) { return batch_invert_t<decltype(f)>(a_dev, nullptr, n, (hipStream_t)stream); });
 }
 
 int trh_field_batch_invert_mul_dev(int field, void* a_dev, const void* num_dev, size_t n, void* stream) {
     TRH_TRY(require_init());
-    if (field != TRH_FP && field != TRH_FQ) { set_error("unknown field id %d", field); return TRH_EINVAL; }
+    TRH_TRY(check_field(field));
     if (n && (!a_dev || !num_dev)) { set_error("batch_invert_mul: null pointer"); return TRH_EINVAL; }
     if (!n) return TRH_OK;
     TRH_ENTER(stream);
     Range range("trh_field_batch_invert_mul_dev");
-    Ctx& c = ctx();
-    (void)c;
-    if (field == TRH_FP) return batch_invert_t<FpParams>(a_dev, num_dev, n, (hipStream_t)stream);
-    return batch_invert_t<FqParams>(a_dev, num_dev, n, (hipStream_t)stream);
+    return with_field(field, [&](auto f) { return batch_invert_t<decltype(f)>(a_dev, num_dev, n, (hipStream_t)stream); });
 }
 
 int trh_product_terms_dev(int field, const trh_product_term_t* terms, const uint32_t* row_start, uint32_t rows, size_t n, void* out_dev, void* stream) {
     TRH_TRY(require_init());
-    if (field != TRH_FP && field != TRH_FQ) { set_error("unknown field id %d", field); return TRH_EINVAL; }
+    TRH_TRY(check_field(field));
     if (!rows || !n) return TRH_OK;
     if (!terms || !row_start || !out_dev) { set_error("product_terms: null pointer"); return TRH_EINVAL; }
     if (rows > 32768) { set_error("product_terms: more than 32768 rows"); return TRH_EINVAL; }
@@ -272,8 +254,7 @@ int trh_product_terms_dev(int field, const trh_product_term_t* terms, const uint
     TRH_HIP_TRY(hipMemcpyAsync((char*)c.scan.p + term_bytes, row_start, start_bytes, hipMemcpyHostToDevice, s));
     TRH_HIP_TRY(hipStreamSynchronize(s));  // the caller's descriptor arrays may be reused
     const dim3 grid((unsigned)((n + 255) / 256), rows);
-    if (field == TRH_FP) hipLaunchKernelGGL((product_terms_kernel<FpParams>), grid, dim3(256), 0, s, (const DevTerm*)c.scan.p, (const u32*)((char*)c.scan.p + term_bytes), n, (uint4*)out_dev);
-    else hipLaunchKernelGGL((product_terms_kernel<FqParams>), grid, dim3(256), 0, s, (const DevTerm*)c.scan.p, (const u32*)((char*)c.scan.p + term_bytes), n, (uint4*)out_dev);
+    with_field(field, [&](auto f) { hipLaunchKernelGGL((product_terms_kernel<decltype(f)>), grid, dim3(256), 0, s, (const DevTerm*)c.scan.p, (const u32*)((char*)c.scan.p + term_bytes), n, (uint4*)out_dev); });
     TRH_HIP_TRY(hipGetLastError());
     TRH_HIP_TRY(hipStreamSynchronize(s));  // c.scan is shared scratch
     return TRH_OK;
@@ -281,35 +262,30 @@ int trh_product_terms_dev(int field, const trh_product_term_t* terms, const uint
 
 int trh_field_prefix_product_dev(int field, const void* a_dev, void* out_dev, size_t n, void* stream) {
     TRH_TRY(require_init());
-    if (field != TRH_FP && field != TRH_FQ) { set_error("unknown field id %d", field); return TRH_EINVAL; }
+    TRH_TRY(check_field(field));
     if (n && (!a_dev || !out_dev)) { set_error("prefix_product: null pointer"); return TRH_EINVAL; }
     if (a_dev == out_dev) { set_error("prefix_product: in-place operation is not supported"); return TRH_EINVAL; }
     if (!n) return TRH_OK;
     TRH_ENTER(stream);
     Range range("trh_field_prefix_product_dev");
-    Ctx& c = ctx();
-    (void)c;
-    if (field == TRH_FP) return prefix_scan_t<FpParams, OpMul<FpParams>>(a_dev, out_dev, n, (hipStream_t)stream);
-    return prefix_scan_t<FqParams, OpMul<FqParams>>(a_dev, out_dev, n, (hipStream_t)stream);
+    return with_field(field, [&](auto f) { return prefix_scan_t<decltype(f), OpMul<decltype(f)>>(a_dev, out_dev, n, (hipStream_t)stream); });
 }
 
 int trh_poly_lincomb_dev(int field, const void* polys_dev, size_t n, size_t batch, const uint64_t* coeffs_host, void* out_dev, void* stream) {
     TRH_TRY(require_init());
-    if (field != TRH_FP && field != TRH_FQ) { set_error("unknown field id %d", field); return TRH_EINVAL; }
+    TRH_TRY(check_field(field));
     if (n && (!out_dev || (batch && (!polys_dev || !coeffs_host)))) { set_error("poly_lincomb: null pointer"); return TRH_EINVAL; }
     if (batch > ((size_t)1 << 20)) { set_error("poly_lincomb: batch too large"); return TRH_EINVAL; }
     if (!n) return TRH_OK;
     TRH_ENTER(stream);
     Range range("trh_poly_lincomb_dev");
     Ctx& c = ctx();
-    (void)c;
     hipStream_t s = (hipStream_t)stream;
     TRH_TRY(c.scan.ensure((batch ? batch : 1) * 32));
     if (batch) TRH_HIP_TRY(hipMemcpyAsync(c.scan.p, coeffs_host, batch * 32, hipMemcpyHostToDevice, s));
     TRH_HIP_TRY(hipStreamSynchronize(s));  // the caller's coefficient buffer may be reused
     const unsigned gb = (unsigned)((n + 255) / 256);
-    if (field == TRH_FP) hipLaunchKernelGGL((lincomb_kernel<FpParams>), dim3(gb), dim3(256), 0, s, (const uint4*)polys_dev, n, (u32)batch, c.scan.as<uint4>(), (uint4*)out_dev);
-    else hipLaunchKernelGGL((lincomb_kernel<FqParams>), dim3(gb), dim3(256), 0, s, (const uint4*)polys_dev, n, (u32)batch, c.scan.as<uint4>(), (uint4*)out_dev);
+    with_field(field, [&](auto f) { hipLaunchKernelGGL((lincomb_kernel<decltype(f)>), dim3(gb), dim3(256), 0, s, (const uint4*)polys_dev, n, (u32)batch, c.scan.as<uint4>(), (uint4*)out_dev); });
     TRH_HIP_TRY(hipGetLastError());
     TRH_HIP_TRY(hipStreamSynchronize(s));  // c.scan is shared scratch
     return TRH_OK;
@@ -319,56 +295,46 @@ int trh_poly_lincomb_dev(int field, const void* polys_dev, size_t n, size_t batc
  * (n elements each, device; trh_field_powers_dev), scratch: 2 n elements of device memory */
 int trh_poly_kate_division_dev(int field, const void* a_dev, size_t n, const void* pz_dev, const void* pzinv_dev, void* scratch_dev, void* q_dev, void* stream) {
     TRH_TRY(require_init());
-    if (field != TRH_FP && field != TRH_FQ) { set_error("unknown field id %d", field); return TRH_EINVAL; }
+    TRH_TRY(check_field(field));
     if (n < 2) return TRH_OK;  // a constant has an empty quotient
     if (!a_dev || !pz_dev || !pzinv_dev || !scratch_dev || !q_dev) { set_error("kate_division: null pointer"); return TRH_EINVAL; }
     TRH_ENTER(stream);
     Range range("trh_poly_kate_division_dev");
-    Ctx& c = ctx();
-    (void)c;
     hipStream_t s = (hipStream_t)stream;
     uint4* t = (uint4*)scratch_dev;
     uint4* P = t + 2 * n;
     const unsigned gb = (unsigned)((n + 255) / 256);
-    if (field == TRH_FP) {
-        hipLaunchKernelGGL((mul_pointwise_kernel<FpParams>), dim3(gb), dim3(256), 0, s, (const uint4*)a_dev, (const uint4*)pz_dev, t, n);
-        TRH_TRY((prefix_scan_t<FpParams, OpAdd<FpParams>>(t, P, n, s)));
-        hipLaunchKernelGGL((kate_finish_kernel<FpParams>), dim3(gb), dim3(256), 0, s, t, P, (const uint4*)pzinv_dev, (uint4*)q_dev, n);
-    } else {
-        hipLaunchKernelGGL((mul_pointwise_kernel<FqParams>), dim3(gb), dim3(256), 0, s, (const uint4*)a_dev, (const uint4*)pz_dev, t, n);
-        TRH_TRY((prefix_scan_t<FqParams, OpAdd<FqParams>>(t, P, n, s)));
-        hipLaunchKernelGGL((kate_finish_kernel<FqParams>), dim3(gb), dim3(256), 0, s, t, P, (const uint4*)pzinv_dev, (uint4*)q_dev, n);
-    }
+    TRH_TRY(with_field(field, [&](auto f) -> int {
+        using F = decltype(f);
+        hipLaunchKernelGGL((mul_pointwise_kernel<F>), dim3(gb), dim3(256), 0, s, (const uint4*)a_dev, (const uint4*)pz_dev, t, n);
+        TRH_TRY((prefix_scan_t<F, OpAdd<F>>(t, P, n, s)));
+        hipLaunchKernelGGL((kate_finish_kernel<F>), dim3(gb), dim3(256), 0, s, t, P, (const uint4*)pzinv_dev, (uint4*)q_dev, n);
+        return TRH_OK;
+    }));
     TRH_HIP_TRY(hipGetLastError());
     return TRH_OK;
 }
 
 int trh_field_prefix_product_rows_dev(int field, const void* a_dev, void* out_dev, size_t n, size_t rows, void* stream) {
     TRH_TRY(require_init());
-    if (field != TRH_FP && field != TRH_FQ) { set_error("unknown field id %d", field); return TRH_EINVAL; }
+    TRH_TRY(check_field(field));
     if (n && rows && (!a_dev || !out_dev)) { set_error("prefix_product_rows: null pointer"); return TRH_EINVAL; }
     if (a_dev == out_dev) { set_error("prefix_product_rows: in-place operation is not supported"); return TRH_EINVAL; }
     if (!n || !rows) return TRH_OK;
     TRH_ENTER(stream);
     Range range("trh_field_prefix_product_rows_dev");
-    Ctx& c = ctx();
-    (void)c;
-    if (field == TRH_FP) return prefix_scan_t<FpParams, OpMul<FpParams>>(a_dev, out_dev, n, (hipStream_t)stream, rows);
-    return prefix_scan_t<FqParams, OpMul<FqParams>>(a_dev, out_dev, n, (hipStream_t)stream, rows);
+    return with_field(field, [&](auto f) { return prefix_scan_t<decltype(f), OpMul<decltype(f)>>(a_dev, out_dev, n, (hipStream_t)stream, rows); });
 }
 
 int trh_field_prefix_sum_dev(int field, const void* a_dev, void* out_dev, size_t n, void* stream) {
     TRH_TRY(require_init());
-    if (field != TRH_FP && field != TRH_FQ) { set_error("unknown field id %d", field); return TRH_EINVAL; }
+    TRH_TRY(check_field(field));
     if (n && (!a_dev || !out_dev)) { set_error("prefix_sum: null pointer"); return TRH_EINVAL; }
     if (a_dev == out_dev) { set_error("prefix_sum: in-place operation is not supported"); return TRH_EINVAL; }
     if (!n) return TRH_OK;
     TRH_ENTER(stream);
     Range range("trh_field_prefix_sum_dev");
-    Ctx& c = ctx();
-    (void)c;
-    if (field == TRH_FP) return prefix_scan_t<FpParams, OpAdd<FpParams>>(a_dev, out_dev, n, (hipStream_t)stream);
-    return prefix_scan_t<FqParams, OpAdd<FqParams>>(a_dev, out_dev, n, (hipStream_t)stream);
+    return with_field(field, [&](auto f) { return prefix_scan_t<decltype(f), OpAdd<decltype(f)>>(a_dev, out_dev, n, (hipStream_t)stream); });
 }
 
 }  // extern "C"
