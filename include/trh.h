@@ -31,7 +31,7 @@
  * thread its own context: trh_ctx_create + trh_ctx_set_current (thread-local binding; several contexts
  * per GPU are fine).  Handles (trh_bases_t, trh_domain_t, trh_expr_t) are device memory: usable from
  * every context of the device they were created on.  Callbacks (trh_ipa_create_proof's transcript /
- * rng) run with the context locked: they may call host-side helpers (trh_point_sum, trh_last_error)
+ * rng) run with the context locked: they may call host-side helpers (trh_point_sum, trh_rng_next_scalar, trh_last_error)
  * but must not start device work on the same context.
  * Multi-GPU: trh_init_multi() binds a device group; base sets of at least trh_set_shard_min() points
  * created afterwards are range-sharded over the group and trh_msm / trh_msm_dev / trh_best_multiexp_*
@@ -457,6 +457,38 @@ int trh_bases_download_compressed(trh_bases_t b, size_t offset, size_t n, uint8_
 /* host-side, no device needed (like trh_point_sum): a transcript's write_point / read_point of single commitments */
 int trh_point_to_bytes(int curve, const uint64_t xyz[12], uint8_t out[32]);    /* Jacobian in, any Z (Z = 0: the identity) */
 int trh_point_from_bytes(int curve, const uint8_t in[32], uint64_t out_xy[8]); /* TRH_EINVAL on an invalid encoding (out_xy zeroed) */
+
+/* ---- the prover's random scalars, drawn on the device from a ChaCha20 seed: `C::Scalar::random(&mut rng)` for whole vectors ----------
+ * create_proof draws the vanishing argument's random polynomial (2^k scalars), the opening's s(X) (2^k) and the blinding rows at the end of
+ * every advice / permuted / product column one scalar at a time on the host.  Here the host draws 32 bytes from its own rng ONCE, and the
+ * stream they seed is expanded where the values are used.  Element i of the stream (seed, stream_id):
+ *   ChaCha20 block number i (RFC 8439 section 2.3 block function, 20 rounds, the original layout: 64-bit block counter in state words 12 - 13,
+ *   64-bit stream id in words 14 - 15, low words first), its 64 bytes read as eight little-endian u64 limbs[0 .. 8), then
+ *   (limbs[0 .. 4) + 2^256 limbs[4 .. 8)) mod m as 4 x u64 Montgomery words, fully reduced.
+ * That is -- as recalled, not pinned by the reference -- what rand_chacha's `ChaCha20Rng::from_seed(seed)` (set_stream(stream_id)) yields through
+ * pasta_curves' `Fp::random` / `Fq::random`.  One element is exactly one block; positions are block numbers.
+ * The handle is HOST memory, like the Rust rng object: it belongs to no context or device and may be used with any.  Host draws and device
+ * fills share its one position (guarded by a lock of the handle's own), so they interleave like calls on one rng: a call advances the
+ * position by the elements it produced (n, rows * count, or 1) and a call that fails leaves it where it was.  position + elements > 2^64
+ * is TRH_EINVAL (rand_chacha would wrap and repeat the stream); after a draw that ended exactly on the last block the position is 2^64:
+ * trh_rng_position then fails and trh_rng_seek is the way back.  n == 0 / count == 0 / rows == 0 succeed and do nothing.
+ * The fill entries are asynchronous on `stream` and ordered behind the context's previous call, like the other *_dev entries; device
+ * elements must be 16-byte aligned.  The seed appears in no error message and in no trace output.
+ * Every entry takes the handle first and the field id second (TRH_FP / TRH_FQ; an unknown id is refused as everywhere else).               */
+typedef struct trh_rng* trh_rng_t;
+int trh_rng_create(const uint8_t seed[32], uint64_t stream_id, trh_rng_t* out);   /* no device needed */
+void trh_rng_destroy(trh_rng_t r);                                                 /* wipes the key */
+int trh_rng_seek(trh_rng_t r, uint64_t block);
+int trh_rng_position(trh_rng_t r, uint64_t* block);
+/* host-side, one block, no device needed: the blinds of commitments, and trh_ipa_create_proof's rng callback -- that callback runs with the
+ * context locked, which is allowed because this entry starts no device work and takes only the handle's own lock */
+int trh_rng_next_scalar(trh_rng_t r, int field, uint64_t out_mont[4]);
+/* out[i] = element position + i, i < n (the random polynomial, s(X)) */
+int trh_rng_fill_dev(trh_rng_t r, int field, void* out_dev, size_t n, void* stream);
+/* `rows` columns of row_len elements stored back to back: cell (r, first + c), c < count, = element position + r * count + c (row-major over
+ * the cells written); every other cell is left untouched -- the blinding rows of a batch of resident columns, without a staging buffer.
+ * first + count > row_len is TRH_EINVAL.                                                                                                   */
+int trh_rng_fill_rows_dev(trh_rng_t r, int field, void* cols_dev, size_t rows, size_t row_len, size_t first, size_t count, void* stream);
 
 /* ---- element-wise field / group ops on device memory (parity tests of the device arithmetic;
  *      op: 0 add, 1 sub, 2 mul, 3 sqr, 4 neg, 5 inv, 6 to_mont, 7 from_mont) ------------------ */

@@ -11,6 +11,7 @@
 //   trh::Expression + compile_gates         plonk::Expression<F> and the y-folded evaluation of the gate polynomials
 //   trh::ipa_create_proof                   poly::commitment::create_proof (IPA opening)
 //   trh::IpaMsm                             poly::commitment::msm::MSM + Guard::use_challenges (the verifier's accumulator)
+//   trh::Rng                                `C::Scalar::random(rng)` for whole vectors: a ChaCha20 seed expanded on the device
 //
 // Reference call sites of all of these: /root/reference/src/test_utils.rs:21-49, 89-104 (through keygen_* and
 // create_proof of the halo2_proofs crate pinned at /root/reference/Cargo.lock:619-621).
@@ -495,6 +496,44 @@ public:
     size_t n_outputs;
 private:
     trh_expr_t e_ = nullptr;
+};
+
+// ---- the prover's random scalars from a ChaCha20 seed (trh_rng_*): `C::Scalar::random(&mut rng)` for whole vectors ------------------
+// The host draws 32 bytes from create_proof's rng once; element i of the stream they seed is ChaCha20 block i through from_u512 (trh.h).
+// fill / fill_rows expand it in device memory, next_scalar on the host; all three share the one position.  Host memory: usable with any context.
+class Rng {
+public:
+    explicit Rng(const std::array<uint8_t, 32>& seed, uint64_t stream_id = 0) { check(trh_rng_create(seed.data(), stream_id, &r_), "rng_create"); }
+    Rng(const Rng&) = delete;
+    Rng& operator=(const Rng&) = delete;
+    Rng(Rng&& o) noexcept : r_(o.r_) { o.r_ = nullptr; }
+    Rng& operator=(Rng&& o) noexcept { std::swap(r_, o.r_); return *this; }
+    ~Rng() { if (r_) trh_rng_destroy(r_); }
+    trh_rng_t handle() const { return r_; }
+    void seek(uint64_t block) { check(trh_rng_seek(r_, block), "rng_seek"); }
+    uint64_t position() const { uint64_t b = 0; check(trh_rng_position(r_, &b), "rng_position"); return b; }
+    Limbs next_scalar(Field f) { Limbs v; check(trh_rng_next_scalar(r_, (int)f, v.data()), "rng_next_scalar"); return v; }
+    // out_dev: n elements (the random polynomial, s(X))
+    void fill(Field f, void* out_dev, size_t n, void* stream = nullptr) { check(trh_rng_fill_dev(r_, (int)f, out_dev, n, stream), "rng_fill"); }
+    // cells [first, first + count) of `rows` columns of row_len elements stored back to back (blinding rows); the other cells are untouched
+    void fill_rows(Field f, void* cols_dev, size_t rows, size_t row_len, size_t first, size_t count, void* stream = nullptr) {
+        check(trh_rng_fill_rows_dev(r_, (int)f, cols_dev, rows, row_len, first, count, stream), "rng_fill_rows");
+    }
+private:
+    trh_rng_t r_ = nullptr;
+};
+
+// An Rng as the `trh_rng_scalar_fn` / rng_ctx pair of ipa_create_proof: pass RngScalarFn::call and the object's address.  The callback runs
+// with the context locked; trh_rng_next_scalar is host-only and takes only the handle's own lock, so that is allowed (trh.h).  A C callback
+// cannot fail: a refused draw (the end of the stream) writes zero and sets `failed`, which the caller checks after the opening.
+struct RngScalarFn {
+    Rng& rng;
+    Field field;
+    bool failed = false;
+    static void call(void* self, uint64_t out_mont[4]) {
+        RngScalarFn* s = (RngScalarFn*)self;
+        if (trh_rng_next_scalar(s->rng.handle(), (int)s->field, out_mont) != TRH_OK) { s->failed = true; for (int i = 0; i < 4; ++i) out_mont[i] = 0; }
+    }
 };
 
 // ---- poly::commitment::create_proof (IPA opening) -------------------------------------------------------------------

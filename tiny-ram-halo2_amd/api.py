@@ -191,6 +191,13 @@ _SIGNATURES = {
     "trh_bases_download_compressed": ([_vp, ctypes.c_size_t, ctypes.c_size_t, _vp], ctypes.c_int),
     "trh_point_to_bytes": ([ctypes.c_int, _u64p, _vp], ctypes.c_int),
     "trh_point_from_bytes": ([ctypes.c_int, _vp, _u64p], ctypes.c_int),
+    "trh_rng_create": ([_vp, ctypes.c_uint64, ctypes.POINTER(_vp)], ctypes.c_int),
+    "trh_rng_destroy": ([_vp], None),
+    "trh_rng_seek": ([_vp, ctypes.c_uint64], ctypes.c_int),
+    "trh_rng_position": ([_vp, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+    "trh_rng_next_scalar": ([_vp, ctypes.c_int, _u64p], ctypes.c_int),
+    "trh_rng_fill_dev": ([_vp, ctypes.c_int, _vp, ctypes.c_size_t, _vp], ctypes.c_int),
+    "trh_rng_fill_rows_dev": ([_vp, ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, _vp], ctypes.c_int),
     "trh_set_timing": ([ctypes.c_int], ctypes.c_int),
     "trh_last_timing": ([ctypes.POINTER(Timing)], ctypes.c_int),
 }
@@ -560,6 +567,55 @@ def point_from_bytes(curve: str, data: bytes) -> np.ndarray:
     out = np.zeros(8, dtype=np.uint64)
     _check(lib().trh_point_from_bytes(CURVE_ID[curve], ctypes.c_char_p(bytes(data)), _p(out)))
     return out
+
+
+# ---------------------------------------------------------------------------------------
+# the prover's random scalars from a ChaCha20 seed: csrc/chacha.h, csrc/random.hip
+# ---------------------------------------------------------------------------------------
+class Rng:
+    """trh_rng_t: the stream of field elements a 32-byte seed expands to (element i = ChaCha20 block i through from_u512; include/trh.h),
+    with ONE position shared by the host draws and the device fills.  The handle is host memory: no device is needed to make one or to
+    draw from it on the host, and it may be used with any context."""
+
+    def __init__(self, seed: bytes, stream_id: int = 0):
+        seed = bytes(seed)
+        assert len(seed) == 32
+        self.handle = _vp()
+        _check(lib().trh_rng_create(ctypes.c_char_p(seed), stream_id, ctypes.byref(self.handle)))
+
+    def seek(self, block: int) -> None:
+        _check(lib().trh_rng_seek(self.handle, block))
+
+    def position(self) -> int:
+        v = ctypes.c_uint64(0)
+        _check(lib().trh_rng_position(self.handle, ctypes.byref(v)))
+        return int(v.value)
+
+    def next_scalar(self, field: str) -> np.ndarray:
+        """one element on the host -> (4,) Montgomery limbs (a commitment's blind, the opening's round blinds)"""
+        out = np.zeros(4, dtype=np.uint64)
+        _check(lib().trh_rng_next_scalar(self.handle, FIELD_ID[field], _p(out)))
+        return out
+
+    def fill(self, field: str, out_dev, n: int, stream=None) -> None:
+        """out[i] = the next n elements, written on the device (asynchronous on `stream`)"""
+        _check(lib().trh_rng_fill_dev(self.handle, FIELD_ID[field], _devptr(out_dev), n, stream))
+
+    def fill_rows(self, field: str, cols_dev, rows: int, row_len: int, first: int, count: int, stream=None) -> None:
+        """cells [first, first + count) of each of `rows` columns of row_len elements (back to back) = the next rows * count elements in
+        row-major order; every other cell is left as it is (the blinding rows of resident columns)"""
+        _check(lib().trh_rng_fill_rows_dev(self.handle, FIELD_ID[field], _devptr(cols_dev), rows, row_len, first, count, stream))
+
+    def destroy(self):
+        if self.handle:
+            lib().trh_rng_destroy(self.handle)
+            self.handle = _vp()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
 
 
 def set_timing(on: bool):

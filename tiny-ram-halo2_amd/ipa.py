@@ -27,9 +27,29 @@ def _canon(field: str, limbs) -> int:
     return v * pow(1 << 256, -1, m) % m
 
 
+class RngScalarFn:
+    """An api.Rng as the `trh_rng_scalar_fn` callback of trh_ipa_create_proof: every call is one trh_rng_next_scalar in the scalar field
+    of `curve`, written straight into the library's buffer.  The callback runs with the context locked; trh_rng_next_scalar is host-only
+    and takes nothing but the handle's own lock, so that is allowed (include/trh.h).  A C callback cannot fail: a refused draw (the end of
+    the stream) leaves the scalar zero and is kept in `error`, which create_proof_native raises after the call."""
+
+    def __init__(self, rng: api.Rng, curve: str):
+        self.rng, self.error = rng, None
+        lib, fid = api.lib(), api.FIELD_ID[api.SCALAR_FIELD[curve]]
+
+        def draw(ctx, out):
+            if lib.trh_rng_next_scalar(rng.handle, fid, out) != 0:
+                self.error = self.error or lib.trh_last_error().decode()
+                for i in range(4):
+                    out[i] = 0
+
+        self.fn = api.RNG_FN(draw)
+
+
 def create_proof_native(params, rng, transcript, p_poly, p_blind: int, x3: int, s_poly, s_blind: int):
     """The same opening through the single C entry point `trh_ipa_create_proof` (csrc/ipa.hip): the round loop
-    and all host-side scalar arithmetic run in C++, the transcript and randomness are callbacks."""
+    and all host-side scalar arithmetic run in C++, the transcript and randomness are callbacks.  rng: a callable returning canonical ints, or
+    an RngScalarFn (the library's own stream); s_poly: host limbs (uploaded here) or a device tensor (one filled by api.Rng.fill, say)."""
     import ctypes
 
     import torch
@@ -47,16 +67,18 @@ def create_proof_native(params, rng, transcript, p_poly, p_blind: int, x3: int, 
     wp = api.WRITE_POINT_FN(lambda ctx, p: transcript.write_point(limbs_of(p, 12)))
     ws = api.WRITE_SCALAR_FN(lambda ctx, p: transcript.write_scalar(limbs_of(p, 4)))
     sq = api.SQUEEZE_FN(lambda ctx, out: put(out, _mont(sf, transcript.squeeze_challenge_scalar())))
-    rn = api.RNG_FN(lambda ctx, out: put(out, _mont(sf, rng())))
+    rn = rng.fn if isinstance(rng, RngScalarFn) else api.RNG_FN(lambda ctx, out: put(out, _mont(sf, rng())))
     tr = api.Transcript(None, wp, ws, sq)
     # (np.require copies only when s_poly is not already contiguous and writable: an unconditional .copy() of the 8 MiB was 1 ms of every k = 18 opening)
-    s_dev = torch.from_numpy(np.require(s_poly, dtype=np.uint64, requirements=["C", "W"]).view(np.int64)).to(p_poly.device)
+    s_dev = s_poly if isinstance(s_poly, torch.Tensor) else torch.from_numpy(np.require(s_poly, dtype=np.uint64, requirements=["C", "W"]).view(np.int64)).to(p_poly.device)
     out_c, out_f = np.zeros(4, np.uint64), np.zeros(4, np.uint64)
     u = np.ascontiguousarray(params.u, dtype=np.uint64).reshape(8)
     bases = params.ipa_bases() if hasattr(params, "ipa_bases") else params._g
     api._check(api.lib().trh_ipa_create_proof(bases.handle, api._p(u), k, api._devptr(p_poly), api._p(_mont(sf, p_blind)), api._p(_mont(sf, x3)),
                                               api._devptr(s_dev), api._p(_mont(sf, s_blind)), ctypes.byref(tr), rn, None, _stream(p_poly),
                                               api._p(out_c), api._p(out_f)))
+    if isinstance(rng, RngScalarFn) and rng.error:
+        raise api.TrhError(rng.error)
     return _canon(sf, out_c), _canon(sf, out_f)
 
 
