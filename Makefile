@@ -9,7 +9,7 @@ HIPFLAGS ?= -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -Wall -Wno-unused-functi
 OBJS := $(CSRC)/capi.o $(CSRC)/msm.o $(CSRC)/ntt.o $(CSRC)/ipa.o $(CSRC)/ipafold.o $(CSRC)/ipaverify.o $(CSRC)/pointfft.o $(CSRC)/domain.o $(CSRC)/scan.o $(CSRC)/expr.o $(CSRC)/lookup.o $(CSRC)/hostio.o $(CSRC)/selftest.o $(CSRC)/encoding.o $(CSRC)/random.o
 HDRS := $(CSRC)/field.h $(CSRC)/fieldsqrt.h $(CSRC)/chacha.h $(CSRC)/curve.h $(CSRC)/curve_q4.h $(CSRC)/devmem.h $(CSRC)/dispatch.h $(CSRC)/ctx.h $(CSRC)/hostcombine.h $(CSRC)/hosthelper.h $(CSRC)/hostplan.h $(CSRC)/copypool.h $(CSRC)/devpool.h $(CSRC)/selftest_kat.h include/trh.h
 
-all: $(PKG)/libtrh.so oracle examples/replay tests/native/multi_ctx_test tests/native/libtrh_q4broken.so tests/native/lazy29_dev_test tests/native/params_io_test tests/native/rng_fill_test
+all: $(PKG)/libtrh.so oracle examples/replay tests/native/multi_ctx_test tests/native/libtrh_q4broken.so tests/native/lazy29_dev_test tests/native/lazy29_alias_test tests/native/lazy29_segment_test tests/native/params_io_test tests/native/rng_fill_test
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -50,11 +50,19 @@ tests/native/rng_fill_test: tests/native/rng_fill_test.cpp include/trh.hpp inclu
 tests/native/lazy29_dev_test: tests/native/lazy29_dev_test.hip tests/native/lazy29_cases.h $(CSRC)/field.h $(CSRC)/fieldsqrt.h $(CSRC)/curve.h
 	$(HIPCC) $(HIPFLAGS) $< -o $@
 
+# the product forms of the lazy domain with the result written over an operand and with shared operands; run by tests/test_gpu_lazy29_alias.py
+tests/native/lazy29_alias_test: tests/native/lazy29_alias_test.hip tests/native/lazy29_cases.h $(CSRC)/field.h $(CSRC)/fieldsqrt.h $(CSRC)/curve.h
+	$(HIPCC) $(HIPFLAGS) $< -o $@
+
+# one segment of the accumulation (64 lanes x 128 mixed additions), every step against the host branch; run by tests/test_gpu_lazy29_segment.py
+tests/native/lazy29_segment_test: tests/native/lazy29_segment_test.hip $(CSRC)/field.h $(CSRC)/fieldsqrt.h $(CSRC)/curve.h
+	$(HIPCC) $(HIPFLAGS) $< -o $@
+
 oracle:
 	$(MAKE) -s -C oracle libtrh_oracle.so
 
 clean:
-	rm -f $(OBJS) $(CSRC)/*.q4b.o $(PKG)/libtrh.so tests/native/libtrh_q4broken.so examples/replay tests/native/multi_ctx_test tests/native/lazy29_dev_test tests/native/params_io_test tests/native/rng_fill_test
+	rm -f $(OBJS) $(CSRC)/*.q4b.o $(PKG)/libtrh.so tests/native/libtrh_q4broken.so examples/replay tests/native/multi_ctx_test tests/native/lazy29_dev_test tests/native/lazy29_alias_test tests/native/lazy29_segment_test tests/native/params_io_test tests/native/rng_fill_test
 	$(MAKE) -s -C oracle clean
 
 .PHONY: all oracle clean

@@ -260,7 +260,7 @@ int trh_expr_create(int field, const trh_expr_insn_t* insns, size_t n_insn, cons
             }
             case TRH_EXPR_NEG: case TRH_EXPR_SQR:
                 if (depth < 1) return bad("unary operator on an empty stack");
-                if (u.op == TRH_EXPR_SQR) {  // fy_squares doubles the limbs of its operand: below 256 m, and the result below 512 m
+                if (u.op == TRH_EXPR_SQR) {  // fy_sqr doubles the limbs of its operand: below 256 m, and the result below 512 m
                     if (bound.back() > MAX_SQR) reduce_top();
                     bound.back() = after_mul(bound.back(), bound.back());
                 }

@@ -375,335 +375,176 @@ TRH_HD i32 opaque_two22(bool negative = false) {
     return v;
 }
 
-// acc (+)= a * b on signed 32-bit operands as ONE v_mad_i64_i32.  Left to itself the compiler multiplies an operand it knows to be
-// non-negative with v_mad_u64_u32 and repairs the sign of the other one with a second multiply-add on the high word plus two moves
-// (seen in the NTT pass: 675 v_mov and 30 % more multiply-adds than the source has products).
-TRH_HD i64 fy_prod(i32 a, i32 b) {
+// The product and its Montgomery reduction, BY COLUMNS.  Column k of T = a b (+ c d) holds the products a_i b_(k-i), the reduction terms
+// of the quotient digits already known (q_(k-1) (-P1), q_(k-2) (-P2), q_(k-3) (-P3), q_(k-4) (-P4), q_(k-8) (-+2^22)), for k >= 9 the
+// subtrahends, and the carry of column k - 1.  All of them are summed in ONE chain of v_mad_i64_i32 whose first multiply-add takes the
+// carry as its addend: the carry costs no instruction of its own.  (By rows -- rounds 4 to 6 -- every column was complete before its
+// carry-in was known, which made the carry a 64-bit add per column: 147 v_lshl_add_u64 per mixed addition.)  A column is then closed by
+// two instructions: v_and_b32 (the quotient digit q_k, or the result limb for k >= 9) and v_ashrrev_i64 (the next carry, in place: one
+// 64-bit accumulator is live instead of 18).  The sums are the same exact integers as by rows, with the same q_k: every result is the
+// same limb for limb.
+//
+// What the instruction selection needs (learned in rounds 4 - 6, unchanged):
+//   * signed v_mad_i64_i32 written out: left to itself the compiler multiplies an operand it knows to be non-negative with
+//     v_mad_u64_u32 and repairs the sign of the other one with a second multiply-add on the high word plus two moves;
+//   * the carry-out operand is vcc (an allocated SGPR pair makes the compiler put an s_nop behind every instruction);
+//   * one asm block per column: the hazard recogniser puts one s_nop behind each asm statement, whatever its length;
+//   * an asm statement takes at most 30 operands, so a column of more than 14 terms (fy_mul2) is two blocks chained through the
+//     accumulator.
+//
+// fy_chain: c = (ZERO ? 0 : c) + sum_(i < N) x[i] y[i] - (SUB >= 1 ? s1 : 0) - (SUB == 2 ? 2 s2 : 0).  The host computes in the same order.
 #if defined(__HIP_DEVICE_COMPILE__)
-    i64 d;  // the carry-out operand goes to vcc (an allocated SGPR pair makes the compiler put an s_nop behind every statement)
-    asm("v_mad_i64_i32 %0, vcc, %1, %2, 0" : "=v"(d) : "v"(a), "v"(b) : "vcc");
-    return d;
-#else
-    return (i64)a * b;
-#endif
-}
-TRH_HD void fy_mac(i64& acc, i32 a, i32 b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_mad_i64_i32 %0, vcc, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b) : "vcc");
-#else
-    acc += (i64)a * b;
-#endif
-}
-// One ROW of the schoolbook product, c[k] (+)= a * b[k] for k = 0 .. 8, as one block of nine independent multiply-adds.  Single
-// statements would each be followed by an s_nop (the compiler's hazard recogniser is conservative around inline assembly on
-// gfx950: 1338 of them in an NTT pass); a block pays one.  INIT 0: all nine accumulate; 1: the last column starts from zero (rows
-// 1 .. 8 of a product: column i + 8 is first reached there); 2: all nine start from zero (row 0).
-template <int INIT> TRH_HD void fy_row(i64 (&acc)[18], int base, i32 a, const i32 (&b)[NLIMBS]) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    i64 &c0 = acc[base], &c1 = acc[base + 1], &c2 = acc[base + 2], &c3 = acc[base + 3], &c4 = acc[base + 4], &c5 = acc[base + 5], &c6 = acc[base + 6], &c7 = acc[base + 7],
-        &c8 = acc[base + 8];
-    if constexpr (INIT == 2) {
-        asm("v_mad_i64_i32 %0, vcc, %9, %10, 0\n\tv_mad_i64_i32 %1, vcc, %9, %11, 0\n\tv_mad_i64_i32 %2, vcc, %9, %12, 0\n\t"
-            "v_mad_i64_i32 %3, vcc, %9, %13, 0\n\tv_mad_i64_i32 %4, vcc, %9, %14, 0\n\tv_mad_i64_i32 %5, vcc, %9, %15, 0\n\t"
-            "v_mad_i64_i32 %6, vcc, %9, %16, 0\n\tv_mad_i64_i32 %7, vcc, %9, %17, 0\n\tv_mad_i64_i32 %8, vcc, %9, %18, 0"
-            : "=&v"(c0), "=&v"(c1), "=&v"(c2), "=&v"(c3), "=&v"(c4), "=&v"(c5), "=&v"(c6), "=&v"(c7), "=&v"(c8)
-            : "v"(a), "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]), "v"(b[4]), "v"(b[5]), "v"(b[6]), "v"(b[7]), "v"(b[8])
-            : "vcc");
-    } else if constexpr (INIT == 1) {
-        asm("v_mad_i64_i32 %0, vcc, %9, %10, %0\n\tv_mad_i64_i32 %1, vcc, %9, %11, %1\n\tv_mad_i64_i32 %2, vcc, %9, %12, %2\n\t"
-            "v_mad_i64_i32 %3, vcc, %9, %13, %3\n\tv_mad_i64_i32 %4, vcc, %9, %14, %4\n\tv_mad_i64_i32 %5, vcc, %9, %15, %5\n\t"
-            "v_mad_i64_i32 %6, vcc, %9, %16, %6\n\tv_mad_i64_i32 %7, vcc, %9, %17, %7\n\tv_mad_i64_i32 %8, vcc, %9, %18, 0"
-            : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3), "+v"(c4), "+v"(c5), "+v"(c6), "+v"(c7), "=&v"(c8)
-            : "v"(a), "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]), "v"(b[4]), "v"(b[5]), "v"(b[6]), "v"(b[7]), "v"(b[8])
-            : "vcc");
-    } else {
-        asm("v_mad_i64_i32 %0, vcc, %9, %10, %0\n\tv_mad_i64_i32 %1, vcc, %9, %11, %1\n\tv_mad_i64_i32 %2, vcc, %9, %12, %2\n\t"
-            "v_mad_i64_i32 %3, vcc, %9, %13, %3\n\tv_mad_i64_i32 %4, vcc, %9, %14, %4\n\tv_mad_i64_i32 %5, vcc, %9, %15, %5\n\t"
-            "v_mad_i64_i32 %6, vcc, %9, %16, %6\n\tv_mad_i64_i32 %7, vcc, %9, %17, %7\n\tv_mad_i64_i32 %8, vcc, %9, %18, %8"
-            : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3), "+v"(c4), "+v"(c5), "+v"(c6), "+v"(c7), "+v"(c8)
-            : "v"(a), "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]), "v"(b[4]), "v"(b[5]), "v"(b[6]), "v"(b[7]), "v"(b[8])
-            : "vcc");
+#define TRH_FY_M(i) "v_mad_i64_i32 %[c], vcc, %[x" #i "], %[y" #i "], %[c]\n\t"
+#define TRH_FY_Z "v_mad_i64_i32 %[c], vcc, %[x0], %[y0], 0\n\t"
+#define TRH_FY_S1 "v_mad_i64_i32 %[c], vcc, %[s1], -1, %[c]\n\t"
+#define TRH_FY_S2 "v_mad_i64_i32 %[c], vcc, %[s2], -2, %[c]\n\t"
+#define TRH_FY_V(i) [x##i] "v"(x[i]), [y##i] "v"(y[i])
+#define TRH_FY_B1
+#define TRH_FY_I1 TRH_FY_V(0)
+#define TRH_FY_B2 TRH_FY_B1 TRH_FY_M(1)
+#define TRH_FY_I2 TRH_FY_I1, TRH_FY_V(1)
+#define TRH_FY_B3 TRH_FY_B2 TRH_FY_M(2)
+#define TRH_FY_I3 TRH_FY_I2, TRH_FY_V(2)
+#define TRH_FY_B4 TRH_FY_B3 TRH_FY_M(3)
+#define TRH_FY_I4 TRH_FY_I3, TRH_FY_V(3)
+#define TRH_FY_B5 TRH_FY_B4 TRH_FY_M(4)
+#define TRH_FY_I5 TRH_FY_I4, TRH_FY_V(4)
+#define TRH_FY_B6 TRH_FY_B5 TRH_FY_M(5)
+#define TRH_FY_I6 TRH_FY_I5, TRH_FY_V(5)
+#define TRH_FY_B7 TRH_FY_B6 TRH_FY_M(6)
+#define TRH_FY_I7 TRH_FY_I6, TRH_FY_V(6)
+#define TRH_FY_B8 TRH_FY_B7 TRH_FY_M(7)
+#define TRH_FY_I8 TRH_FY_I7, TRH_FY_V(7)
+#define TRH_FY_B9 TRH_FY_B8 TRH_FY_M(8)
+#define TRH_FY_I9 TRH_FY_I8, TRH_FY_V(8)
+#define TRH_FY_B10 TRH_FY_B9 TRH_FY_M(9)
+#define TRH_FY_I10 TRH_FY_I9, TRH_FY_V(9)
+#define TRH_FY_B11 TRH_FY_B10 TRH_FY_M(10)
+#define TRH_FY_I11 TRH_FY_I10, TRH_FY_V(10)
+#define TRH_FY_B12 TRH_FY_B11 TRH_FY_M(11)
+#define TRH_FY_I12 TRH_FY_I11, TRH_FY_V(11)
+#define TRH_FY_B13 TRH_FY_B12 TRH_FY_M(12)
+#define TRH_FY_I13 TRH_FY_I12, TRH_FY_V(12)
+#define TRH_FY_B14 TRH_FY_B13 TRH_FY_M(13)
+#define TRH_FY_I14 TRH_FY_I13, TRH_FY_V(13)
+#define TRH_FY_CASE(n)                                                                                                                     \
+    else if constexpr (N == n) {                                                                                                           \
+        if constexpr (ZERO) asm(TRH_FY_Z TRH_FY_B##n : [c] "=&v"(c) : TRH_FY_I##n : "vcc");                                                \
+        else if constexpr (SUB == 0) asm(TRH_FY_M(0) TRH_FY_B##n : [c] "+v"(c) : TRH_FY_I##n : "vcc");                                     \
+        else if constexpr (SUB == 1) asm(TRH_FY_M(0) TRH_FY_B##n TRH_FY_S1 : [c] "+v"(c) : TRH_FY_I##n, [s1] "v"(s1) : "vcc");             \
+        else asm(TRH_FY_M(0) TRH_FY_B##n TRH_FY_S1 TRH_FY_S2 : [c] "+v"(c) : TRH_FY_I##n, [s1] "v"(s1), [s2] "v"(s2) : "vcc");             \
     }
-#else
-    for (int k = 0; k < NLIMBS; ++k) {
-        const i64 p = (i64)a * b[k];
-        if (INIT == 2 || (INIT == 1 && k == NLIMBS - 1)) acc[base + k] = p; else acc[base + k] += p;
-    }
 #endif
-}
-// c[9 + k] += m * s[k]: a subtrahend (m = -1, -2) enters the result columns as one more row of multiply-adds -- one instruction
-// per limb, where sign-extending s[k] and a 64-bit subtraction in the final carry chain took three
-template <int M> TRH_HD void fy_row_hi(i64 (&acc)[18], const i32 (&b)[NLIMBS]) {
-    static_assert(M == -1 || M == -2, "inline constants of the instruction");
+template <int N, int SUB, bool ZERO> TRH_HD void fy_chain(i64& c, const i32* x, const i32* y, i32 s1, i32 s2) {
+    static_assert(N >= 0 && N <= 14 && SUB >= 0 && SUB <= 2 && 1 + 2 * N + SUB <= 30 && !(ZERO && (SUB != 0 || N == 0)), "one asm statement");
 #if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (M == -1) {
-        asm("v_mad_i64_i32 %0, vcc, %9, -1, %0\n\t"
-            "v_mad_i64_i32 %1, vcc, %10, -1, %1\n\t"
-            "v_mad_i64_i32 %2, vcc, %11, -1, %2\n\t"
-            "v_mad_i64_i32 %3, vcc, %12, -1, %3\n\t"
-            "v_mad_i64_i32 %4, vcc, %13, -1, %4\n\t"
-            "v_mad_i64_i32 %5, vcc, %14, -1, %5\n\t"
-            "v_mad_i64_i32 %6, vcc, %15, -1, %6\n\t"
-            "v_mad_i64_i32 %7, vcc, %16, -1, %7\n\t"
-            "v_mad_i64_i32 %8, vcc, %17, -1, %8"
-            : "+v"(acc[9]), "+v"(acc[10]), "+v"(acc[11]), "+v"(acc[12]), "+v"(acc[13]), "+v"(acc[14]), "+v"(acc[15]), "+v"(acc[16]), "+v"(acc[17])
-            : "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]), "v"(b[4]), "v"(b[5]), "v"(b[6]), "v"(b[7]), "v"(b[8])
-            : "vcc");
-    } else {
-        asm("v_mad_i64_i32 %0, vcc, %9, -2, %0\n\t"
-            "v_mad_i64_i32 %1, vcc, %10, -2, %1\n\t"
-            "v_mad_i64_i32 %2, vcc, %11, -2, %2\n\t"
-            "v_mad_i64_i32 %3, vcc, %12, -2, %3\n\t"
-            "v_mad_i64_i32 %4, vcc, %13, -2, %4\n\t"
-            "v_mad_i64_i32 %5, vcc, %14, -2, %5\n\t"
-            "v_mad_i64_i32 %6, vcc, %15, -2, %6\n\t"
-            "v_mad_i64_i32 %7, vcc, %16, -2, %7\n\t"
-            "v_mad_i64_i32 %8, vcc, %17, -2, %8"
-            : "+v"(acc[9]), "+v"(acc[10]), "+v"(acc[11]), "+v"(acc[12]), "+v"(acc[13]), "+v"(acc[14]), "+v"(acc[15]), "+v"(acc[16]), "+v"(acc[17])
-            : "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]), "v"(b[4]), "v"(b[5]), "v"(b[6]), "v"(b[7]), "v"(b[8])
-            : "vcc");
+    if constexpr (N == 0) {
+        if constexpr (SUB == 1) asm(TRH_FY_S1 : [c] "+v"(c) : [s1] "v"(s1) : "vcc");
+        else if constexpr (SUB == 2) asm(TRH_FY_S1 TRH_FY_S2 : [c] "+v"(c) : [s1] "v"(s1), [s2] "v"(s2) : "vcc");
     }
+    TRH_FY_CASE(1) TRH_FY_CASE(2) TRH_FY_CASE(3) TRH_FY_CASE(4) TRH_FY_CASE(5) TRH_FY_CASE(6) TRH_FY_CASE(7) TRH_FY_CASE(8) TRH_FY_CASE(9) TRH_FY_CASE(10) TRH_FY_CASE(11) TRH_FY_CASE(12) TRH_FY_CASE(13) TRH_FY_CASE(14)
 #else
-    for (int k = 0; k < NLIMBS; ++k) acc[9 + k] += (i64)M * b[k];
+    if (ZERO) c = 0;
+    for (int i = 0; i < N; ++i) c += (i64)x[i] * y[i];
+    if (SUB >= 1) c += (i64)s1 * -1;
+    if (SUB == 2) c += (i64)s2 * -2;
 #endif
 }
-// one reduction round: the five columns q touches
-TRH_HD void fy_round(i64& c1, i64& c2, i64& c3, i64& c4, i64& c8, i32 q, i32 p1, i32 p2, i32 p3, i32 p4, i32 p8) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("v_mad_i64_i32 %0, vcc, %5, %6, %0\n\tv_mad_i64_i32 %1, vcc, %5, %7, %1\n\tv_mad_i64_i32 %2, vcc, %5, %8, %2\n\t"
-        "v_mad_i64_i32 %3, vcc, %5, %9, %3\n\tv_mad_i64_i32 %4, vcc, %5, %10, %4"
-        : "+v"(c1), "+v"(c2), "+v"(c3), "+v"(c4), "+v"(c8)
-        : "v"(q), "v"(p1), "v"(p2), "v"(p3), "v"(p4), "v"(p8)
-        : "vcc");
-#else
-    c1 += (i64)q * p1; c2 += (i64)q * p2; c3 += (i64)q * p3; c4 += (i64)q * p4; c8 += (i64)q * p8;
-#endif
-}
-// the 9 x 9 products of a * b into the 17 columns they touch (column 17 only ever holds carries of the reduction: zeroed here)
-template <class F> TRH_HD void fy_products(i64 (&acc)[18], const Fy<F>& a, const Fy<F>& b) {
-    fy_row<2>(acc, 0, a.l[0], b.l);
+// number of terms of column k: products of a 9 x 9 schoolbook product, of a square in its doubled-limb form, reduction terms
+constexpr int fy_nprod(int k) { return k <= 8 ? k + 1 : k <= 16 ? 17 - k : 0; }
+constexpr int fy_nsqr(int k) { return k > 16 ? 0 : fy_nprod(k) / 2 + (k % 2 == 0 ? 1 : 0); }
+constexpr int fy_isq(int i) { return i >= 0 && i <= 8 ? 1 : 0; }  // is q_i a quotient digit?
+constexpr int fy_nround(int k) { return fy_isq(k - 1) + fy_isq(k - 2) + fy_isq(k - 3) + fy_isq(k - 4) + fy_isq(k - 8); }
+
+// Column K and, through the recursion, every column after it.  SQR: a^2 (a2 = 2 a: row i of a square is a_i (a_i, 2 a_(i+1), ..., 2 a_8),
+// the doubled limbs below 2^30 in magnitude as a is normalised); TWO: a b + c d; SUB: minus s1 (and 2 s2) in the result columns;
+// pm = (-+P1, -+P2, -+P3, -+P4, -+2^22).
+// A round removes r = column mod 2^29 by adding -r m (m = 1 mod 2^29): the low limb of -r m cancels r, so the carry into the next
+// column is simply floor(column / 2^29) and the other limbs of m enter as r * (-m_k).  The result lies in (-v / 2^261 - m, v / 2^261]:
+// fine for the signed domain.  NONNEG picks the mirror image (q = -r mod 2^29, + q m, carry = ceil = (column + q) / 2^29): result in
+// [v / 2^261, v / 2^261 + m), i.e. non-negative for v >= 0 -- needed where the result is stored as eight words (fy_store) -- at one
+// 64-bit add and one negation more per round.
+template <class F, int K, bool SQR, bool TWO, int SUB, bool NONNEG>
+TRH_HD void fy_columns(i64& acc, i32 (&q)[NLIMBS], Fy<F>& r, const i32 (&a)[NLIMBS], const i32 (&b)[NLIMBS], const i32 (&c)[NLIMBS], const i32 (&d)[NLIMBS],
+                       const i32 (&a2)[NLIMBS], const i32 (&pm)[5], const i32* s1, const i32* s2) {
+    constexpr int NP = SQR ? fy_nsqr(K) : (TWO ? 2 : 1) * fy_nprod(K);
+    constexpr int NT = NP + fy_nround(K);
+    constexpr int NS = K >= 9 ? SUB : 0;
+    constexpr int LO = K > 8 ? K - 8 : 0, HI = K > 8 ? 8 : K;
+    i32 x[NT > 0 ? NT : 1], y[NT > 0 ? NT : 1];
+    int n = 0;
+    if constexpr (K <= 16) {
+        if constexpr (SQR) {
+            if constexpr (K % 2 == 0) { x[n] = a[K / 2]; y[n] = a[K / 2]; ++n; }
 #pragma unroll
-    for (int i = 1; i < NLIMBS; ++i) fy_row<1>(acc, i, a.l[i], b.l);
-    acc[17] = 0;
-}
-template <class F> TRH_HD void fy_products_add(i64 (&acc)[18], const Fy<F>& a, const Fy<F>& b) {
+            for (int i = LO; 2 * i < K; ++i) { x[n] = a[i]; y[n] = a2[K - i]; ++n; }
+        } else {
 #pragma unroll
-    for (int i = 0; i < NLIMBS; ++i) fy_row<0>(acc, i, a.l[i], b.l);
+            for (int i = LO; i <= HI; ++i) { x[n] = a[i]; y[n] = b[K - i]; ++n; }
+            if constexpr (TWO) {
+#pragma unroll
+                for (int i = LO; i <= HI; ++i) { x[n] = c[i]; y[n] = d[K - i]; ++n; }
+            }
+        }
+    }
+    if constexpr (fy_isq(K - 8)) { x[n] = q[K - 8]; y[n] = pm[4]; ++n; }
+    if constexpr (fy_isq(K - 4)) { x[n] = q[K - 4]; y[n] = pm[3]; ++n; }
+    if constexpr (fy_isq(K - 3)) { x[n] = q[K - 3]; y[n] = pm[2]; ++n; }
+    if constexpr (fy_isq(K - 2)) { x[n] = q[K - 2]; y[n] = pm[1]; ++n; }
+    if constexpr (fy_isq(K - 1)) { x[n] = q[K - 1]; y[n] = pm[0]; ++n; }  // the youngest digit last
+    const i32 t1 = NS >= 1 ? s1[K - 9 < 0 ? 0 : K - 9] : 0, t2 = NS == 2 ? s2[K - 9 < 0 ? 0 : K - 9] : 0;
+    if constexpr (K == 0) fy_chain<NT, 0, true>(acc, x, y, 0, 0);
+    else if constexpr (1 + 2 * NT + NS <= 30) fy_chain<NT, NS, false>(acc, x, y, t1, t2);
+    else {
+        fy_chain<NT / 2, 0, false>(acc, x, y, 0, 0);
+        fy_chain<NT - NT / 2, NS, false>(acc, x + NT / 2, y + NT / 2, t1, t2);
+    }
+    if constexpr (K <= 8) {
+        if constexpr (NONNEG) {
+            q[K] = (i32)((0u - (u32)acc) & (u32)YMASK);
+            acc += q[K];  // a multiple of 2^29
+        } else {
+            q[K] = (i32)((u32)acc & (u32)YMASK);
+        }
+        acc >>= YBITS;
+    } else if constexpr (K < 17) {
+        r.l[K - 9] = (i32)((u32)acc & (u32)YMASK);
+        acc >>= YBITS;
+    } else {
+        r.l[8] = (i32)acc;  // signed top limb: |value| < 2^260
+    }
+    if constexpr (K < 17) fy_columns<F, K + 1, SQR, TWO, SUB, NONNEG>(acc, q, r, a, b, c, d, a2, pm, s1, s2);
 }
-// c[k] (+)= a * b[k] for k < L as one block (the rows of a square: L = 9 .. 1).  ALL: every column starts from zero (row 0); otherwise the
-// first L - 1 accumulate and the last one -- the first entry of its column -- starts from zero
-template <int L, bool ALL> TRH_HD void fy_short_row(i64* c, i32 a, const i32* b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    if constexpr (L == 9 && ALL) {
-        asm("v_mad_i64_i32 %[c0], vcc, %[a], %[b0], 0\n\t"
-            "v_mad_i64_i32 %[c1], vcc, %[a], %[b1], 0\n\t"
-            "v_mad_i64_i32 %[c2], vcc, %[a], %[b2], 0\n\t"
-            "v_mad_i64_i32 %[c3], vcc, %[a], %[b3], 0\n\t"
-            "v_mad_i64_i32 %[c4], vcc, %[a], %[b4], 0\n\t"
-            "v_mad_i64_i32 %[c5], vcc, %[a], %[b5], 0\n\t"
-            "v_mad_i64_i32 %[c6], vcc, %[a], %[b6], 0\n\t"
-            "v_mad_i64_i32 %[c7], vcc, %[a], %[b7], 0\n\t"
-            "v_mad_i64_i32 %[c8], vcc, %[a], %[b8], 0"
-            : [c0] "=&v"(c[0]), [c1] "=&v"(c[1]), [c2] "=&v"(c[2]), [c3] "=&v"(c[3]), [c4] "=&v"(c[4]), [c5] "=&v"(c[5]), [c6] "=&v"(c[6]), [c7] "=&v"(c[7]), [c8] "=&v"(c[8])
-            : [a] "v"(a), [b0] "v"(b[0]), [b1] "v"(b[1]), [b2] "v"(b[2]), [b3] "v"(b[3]), [b4] "v"(b[4]), [b5] "v"(b[5]), [b6] "v"(b[6]), [b7] "v"(b[7]), [b8] "v"(b[8])
-            : "vcc");
-    }
-    else if constexpr (L == 9 && !ALL) {
-        asm("v_mad_i64_i32 %[c0], vcc, %[a], %[b0], %[c0]\n\t"
-            "v_mad_i64_i32 %[c1], vcc, %[a], %[b1], %[c1]\n\t"
-            "v_mad_i64_i32 %[c2], vcc, %[a], %[b2], %[c2]\n\t"
-            "v_mad_i64_i32 %[c3], vcc, %[a], %[b3], %[c3]\n\t"
-            "v_mad_i64_i32 %[c4], vcc, %[a], %[b4], %[c4]\n\t"
-            "v_mad_i64_i32 %[c5], vcc, %[a], %[b5], %[c5]\n\t"
-            "v_mad_i64_i32 %[c6], vcc, %[a], %[b6], %[c6]\n\t"
-            "v_mad_i64_i32 %[c7], vcc, %[a], %[b7], %[c7]\n\t"
-            "v_mad_i64_i32 %[c8], vcc, %[a], %[b8], 0"
-            : [c0] "+v"(c[0]), [c1] "+v"(c[1]), [c2] "+v"(c[2]), [c3] "+v"(c[3]), [c4] "+v"(c[4]), [c5] "+v"(c[5]), [c6] "+v"(c[6]), [c7] "+v"(c[7]), [c8] "=&v"(c[8])
-            : [a] "v"(a), [b0] "v"(b[0]), [b1] "v"(b[1]), [b2] "v"(b[2]), [b3] "v"(b[3]), [b4] "v"(b[4]), [b5] "v"(b[5]), [b6] "v"(b[6]), [b7] "v"(b[7]), [b8] "v"(b[8])
-            : "vcc");
-    }
-    else if constexpr (L == 8 && !ALL) {
-        asm("v_mad_i64_i32 %[c0], vcc, %[a], %[b0], %[c0]\n\t"
-            "v_mad_i64_i32 %[c1], vcc, %[a], %[b1], %[c1]\n\t"
-            "v_mad_i64_i32 %[c2], vcc, %[a], %[b2], %[c2]\n\t"
-            "v_mad_i64_i32 %[c3], vcc, %[a], %[b3], %[c3]\n\t"
-            "v_mad_i64_i32 %[c4], vcc, %[a], %[b4], %[c4]\n\t"
-            "v_mad_i64_i32 %[c5], vcc, %[a], %[b5], %[c5]\n\t"
-            "v_mad_i64_i32 %[c6], vcc, %[a], %[b6], %[c6]\n\t"
-            "v_mad_i64_i32 %[c7], vcc, %[a], %[b7], 0"
-            : [c0] "+v"(c[0]), [c1] "+v"(c[1]), [c2] "+v"(c[2]), [c3] "+v"(c[3]), [c4] "+v"(c[4]), [c5] "+v"(c[5]), [c6] "+v"(c[6]), [c7] "=&v"(c[7])
-            : [a] "v"(a), [b0] "v"(b[0]), [b1] "v"(b[1]), [b2] "v"(b[2]), [b3] "v"(b[3]), [b4] "v"(b[4]), [b5] "v"(b[5]), [b6] "v"(b[6]), [b7] "v"(b[7])
-            : "vcc");
-    }
-    else if constexpr (L == 7 && !ALL) {
-        asm("v_mad_i64_i32 %[c0], vcc, %[a], %[b0], %[c0]\n\t"
-            "v_mad_i64_i32 %[c1], vcc, %[a], %[b1], %[c1]\n\t"
-            "v_mad_i64_i32 %[c2], vcc, %[a], %[b2], %[c2]\n\t"
-            "v_mad_i64_i32 %[c3], vcc, %[a], %[b3], %[c3]\n\t"
-            "v_mad_i64_i32 %[c4], vcc, %[a], %[b4], %[c4]\n\t"
-            "v_mad_i64_i32 %[c5], vcc, %[a], %[b5], %[c5]\n\t"
-            "v_mad_i64_i32 %[c6], vcc, %[a], %[b6], 0"
-            : [c0] "+v"(c[0]), [c1] "+v"(c[1]), [c2] "+v"(c[2]), [c3] "+v"(c[3]), [c4] "+v"(c[4]), [c5] "+v"(c[5]), [c6] "=&v"(c[6])
-            : [a] "v"(a), [b0] "v"(b[0]), [b1] "v"(b[1]), [b2] "v"(b[2]), [b3] "v"(b[3]), [b4] "v"(b[4]), [b5] "v"(b[5]), [b6] "v"(b[6])
-            : "vcc");
-    }
-    else if constexpr (L == 6 && !ALL) {
-        asm("v_mad_i64_i32 %[c0], vcc, %[a], %[b0], %[c0]\n\t"
-            "v_mad_i64_i32 %[c1], vcc, %[a], %[b1], %[c1]\n\t"
-            "v_mad_i64_i32 %[c2], vcc, %[a], %[b2], %[c2]\n\t"
-            "v_mad_i64_i32 %[c3], vcc, %[a], %[b3], %[c3]\n\t"
-            "v_mad_i64_i32 %[c4], vcc, %[a], %[b4], %[c4]\n\t"
-            "v_mad_i64_i32 %[c5], vcc, %[a], %[b5], 0"
-            : [c0] "+v"(c[0]), [c1] "+v"(c[1]), [c2] "+v"(c[2]), [c3] "+v"(c[3]), [c4] "+v"(c[4]), [c5] "=&v"(c[5])
-            : [a] "v"(a), [b0] "v"(b[0]), [b1] "v"(b[1]), [b2] "v"(b[2]), [b3] "v"(b[3]), [b4] "v"(b[4]), [b5] "v"(b[5])
-            : "vcc");
-    }
-    else if constexpr (L == 5 && !ALL) {
-        asm("v_mad_i64_i32 %[c0], vcc, %[a], %[b0], %[c0]\n\t"
-            "v_mad_i64_i32 %[c1], vcc, %[a], %[b1], %[c1]\n\t"
-            "v_mad_i64_i32 %[c2], vcc, %[a], %[b2], %[c2]\n\t"
-            "v_mad_i64_i32 %[c3], vcc, %[a], %[b3], %[c3]\n\t"
-            "v_mad_i64_i32 %[c4], vcc, %[a], %[b4], 0"
-            : [c0] "+v"(c[0]), [c1] "+v"(c[1]), [c2] "+v"(c[2]), [c3] "+v"(c[3]), [c4] "=&v"(c[4])
-            : [a] "v"(a), [b0] "v"(b[0]), [b1] "v"(b[1]), [b2] "v"(b[2]), [b3] "v"(b[3]), [b4] "v"(b[4])
-            : "vcc");
-    }
-    else if constexpr (L == 4 && !ALL) {
-        asm("v_mad_i64_i32 %[c0], vcc, %[a], %[b0], %[c0]\n\t"
-            "v_mad_i64_i32 %[c1], vcc, %[a], %[b1], %[c1]\n\t"
-            "v_mad_i64_i32 %[c2], vcc, %[a], %[b2], %[c2]\n\t"
-            "v_mad_i64_i32 %[c3], vcc, %[a], %[b3], 0"
-            : [c0] "+v"(c[0]), [c1] "+v"(c[1]), [c2] "+v"(c[2]), [c3] "=&v"(c[3])
-            : [a] "v"(a), [b0] "v"(b[0]), [b1] "v"(b[1]), [b2] "v"(b[2]), [b3] "v"(b[3])
-            : "vcc");
-    }
-    else if constexpr (L == 3 && !ALL) {
-        asm("v_mad_i64_i32 %[c0], vcc, %[a], %[b0], %[c0]\n\t"
-            "v_mad_i64_i32 %[c1], vcc, %[a], %[b1], %[c1]\n\t"
-            "v_mad_i64_i32 %[c2], vcc, %[a], %[b2], 0"
-            : [c0] "+v"(c[0]), [c1] "+v"(c[1]), [c2] "=&v"(c[2])
-            : [a] "v"(a), [b0] "v"(b[0]), [b1] "v"(b[1]), [b2] "v"(b[2])
-            : "vcc");
-    }
-    else if constexpr (L == 2 && !ALL) {
-        asm("v_mad_i64_i32 %[c0], vcc, %[a], %[b0], %[c0]\n\t"
-            "v_mad_i64_i32 %[c1], vcc, %[a], %[b1], 0"
-            : [c0] "+v"(c[0]), [c1] "=&v"(c[1])
-            : [a] "v"(a), [b0] "v"(b[0]), [b1] "v"(b[1])
-            : "vcc");
-    }
-    else if constexpr (L == 1 && !ALL) {
-        asm("v_mad_i64_i32 %[c0], vcc, %[a], %[b0], 0"
-            : [c0] "=&v"(c[0])
-            : [a] "v"(a), [b0] "v"(b[0])
-            : "vcc");
-    }
-#else
-    for (int k = 0; k < L; ++k) {
-        const i64 p = (i64)a * b[k];
-        if (ALL || k == L - 1) c[k] = p; else c[k] += p;
-    }
-#endif
-}
-// a^2: row i is a_i * (a_i, 2 a_{i+1}, ..., 2 a_8) into columns 2 i .. i + 8
-template <class F> TRH_HD void fy_squares(i64 (&acc)[18], const Fy<F>& a) {
-    i32 d[NLIMBS][NLIMBS];  // d[i] = (a_i, 2 a_{i+1}, ...): the doubled limbs are shared (< 2^30 in magnitude: a is normalised)
+// (a b [+ c d] | a^2) / 2^261 (mod m) - s1 - 2 s2, normalised: nine uniform 29-bit rounds on signed columns.  The subtrahends ride in the
+// result columns (the difference that follows a product would otherwise be a carry chain of its own): SUB 0 none, 1 s1, 2 s1 and 2 s2.
+template <class F, bool SQR, bool TWO, int SUB, bool NONNEG>
+TRH_HD Fy<F> fy_mulred(const Fy<F>& a, const Fy<F>& b, const Fy<F>& c, const Fy<F>& d, const Fy<F>* s1, const Fy<F>* s2) {
+    constexpr i32 P1 = YModLimb<F, 1>::v, P2 = YModLimb<F, 2>::v, P3 = YModLimb<F, 3>::v, P4 = YModLimb<F, 4>::v;
+    const i32 pm[5] = {NONNEG ? P1 : -P1, NONNEG ? P2 : -P2, NONNEG ? P3 : -P3, NONNEG ? P4 : -P4, opaque_two22(!NONNEG)};
     i32 a2[NLIMBS];
 #pragma unroll
-    for (int j = 0; j < NLIMBS; ++j) a2[j] = a.l[j] * 2;
-#pragma unroll
-    for (int i = 0; i < NLIMBS; ++i) {
-        d[i][0] = a.l[i];
-#pragma unroll
-        for (int j = i + 1; j < NLIMBS; ++j) d[i][j - i] = a2[j];
-    }
-    fy_short_row<9, true>(&acc[0], a.l[0], d[0]);
-    fy_short_row<8, false>(&acc[2], a.l[1], d[1]);
-    fy_short_row<7, false>(&acc[4], a.l[2], d[2]);
-    fy_short_row<6, false>(&acc[6], a.l[3], d[3]);
-    fy_short_row<5, false>(&acc[8], a.l[4], d[4]);
-    fy_short_row<4, false>(&acc[10], a.l[5], d[5]);
-    fy_short_row<3, false>(&acc[12], a.l[6], d[6]);
-    fy_short_row<2, false>(&acc[14], a.l[7], d[7]);
-    fy_short_row<1, false>(&acc[16], a.l[8], d[8]);
-    acc[17] = 0;
-}
-
-// nine uniform 29-bit rounds on signed columns; result = value / 2^261 (mod m) - s1 - 2 s2, normalised.  The subtrahends ride in the
-// final carry chain (the difference that follows a product would otherwise be a second chain): SUB 0 none, 1 s1, 2 s1 and 2 s2.
-// A round removes r = column mod 2^29 by adding -r m (m = 1 mod 2^29): the low limb of -r m cancels r, so the carry into the next
-// column is simply floor(column / 2^29) and the other limbs of m enter as r * (-m_k) -- three instructions (and, shift, add) next to the
-// five multiply-adds.  The result lies in (-v / 2^261 - m, v / 2^261]: fine for the signed domain.  NONNEG picks the mirror image
-// (q = -r mod 2^29, + q m, carry = ceil): result in [v / 2^261, v / 2^261 + m), i.e. non-negative for v >= 0 -- needed where the
-// result is stored as eight words (fy_store) -- at five instructions per round.
-template <class F, int SUB, bool NONNEG = false> TRH_HD Fy<F> fy_reduce_sub(i64 (&acc)[18], const Fy<F>* s1, const Fy<F>* s2) {
-    constexpr i32 P1 = YModLimb<F, 1>::v, P2 = YModLimb<F, 2>::v, P3 = YModLimb<F, 3>::v, P4 = YModLimb<F, 4>::v;
-    const i32 two22 = opaque_two22(!NONNEG);  // +-2^22
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        if (NONNEG) {
-            const i32 q = (i32)((0u - (u32)acc[i]) & (u32)YMASK);
-            // column i + q is a multiple of 2^29: its quotient is ceil(acc[i] / 2^29) (arithmetic shift = floor)
-            acc[i + 1] += (acc[i] + YMASK) >> YBITS;
-            fy_round(acc[i + 1], acc[i + 2], acc[i + 3], acc[i + 4], acc[i + 8], q, P1, P2, P3, P4, two22);
-        } else {
-            const i32 r = (i32)((u32)acc[i] & (u32)YMASK);
-            acc[i + 1] += acc[i] >> YBITS;
-            fy_round(acc[i + 1], acc[i + 2], acc[i + 3], acc[i + 4], acc[i + 8], r, -P1, -P2, -P3, -P4, two22);
-        }
-    }
-    if (SUB >= 1) fy_row_hi<-1>(acc, s1->l);
-    if (SUB == 2) fy_row_hi<-2>(acc, s2->l);
+    for (int j = 0; j < NLIMBS; ++j) a2[j] = SQR ? a.l[j] * 2 : 0;
+    i32 q[NLIMBS];
+    i64 acc;
     Fy<F> r;
-    i64 c = 0;
-#pragma unroll
-    for (int k = 0; k < NLIMBS; ++k) {
-        c += acc[9 + k];
-        if (k < NLIMBS - 1) {
-            r.l[k] = (i32)((u32)c & (u32)YMASK);
-            c >>= YBITS;
-        }
-    }
-    r.l[8] = (i32)c;  // signed top limb: |value| < 2^260
+    fy_columns<F, 0, SQR, TWO, SUB, NONNEG>(acc, q, r, a.l, b.l, c.l, d.l, a2, pm, SUB >= 1 ? s1->l : nullptr, SUB == 2 ? s2->l : nullptr);
     return r;
 }
-template <class F> TRH_HD Fy<F> fy_reduce(i64 (&acc)[18]) { return fy_reduce_sub<F, 0>(acc, nullptr, nullptr); }
 // a normalised or lazy, b normalised (or the other way round): |a_i b_j| < 2^59
-template <class F> TRH_HD Fy<F> fy_mul(const Fy<F>& a, const Fy<F>& b) {
-    i64 acc[18];
-    fy_products(acc, a, b);
-    return fy_reduce<F>(acc);
-}
+template <class F> TRH_HD Fy<F> fy_mul(const Fy<F>& a, const Fy<F>& b) { return fy_mulred<F, false, false, 0, false>(a, b, a, b, nullptr, nullptr); }
 // the same with a non-negative result for non-negative operands (below a b / 2^261 + m): for values that are stored as words
-template <class F> TRH_HD Fy<F> fy_mul_nonneg(const Fy<F>& a, const Fy<F>& b) {
-    i64 acc[18];
-    fy_products(acc, a, b);
-    return fy_reduce_sub<F, 0, true>(acc, nullptr, nullptr);
-}
+template <class F> TRH_HD Fy<F> fy_mul_nonneg(const Fy<F>& a, const Fy<F>& b) { return fy_mulred<F, false, false, 0, true>(a, b, a, b, nullptr, nullptr); }
 // a normalised
-template <class F> TRH_HD Fy<F> fy_sqr(const Fy<F>& a) {
-    i64 acc[18];
-    fy_squares(acc, a);
-    return fy_reduce<F>(acc);
-}
+template <class F> TRH_HD Fy<F> fy_sqr(const Fy<F>& a) { return fy_mulred<F, true, false, 0, false>(a, a, a, a, nullptr, nullptr); }
 // a b + c d with ONE reduction.  Column bound: (a or b lazy, the other normalised) + (c, d normalised) <= 9 * 2^59 + 9 * 2^58 < 2^62.8
 template <class F> TRH_HD Fy<F> fy_mul2(const Fy<F>& a, const Fy<F>& b, const Fy<F>& c, const Fy<F>& d) {
-    i64 acc[18];
-    fy_products(acc, a, b);
-    fy_products_add(acc, c, d);
-    return fy_reduce<F>(acc);
+    return fy_mulred<F, false, true, 0, false>(a, b, c, d, nullptr, nullptr);
 }
-// a b - s (U2 - X, S2 - Y of the mixed addition): the subtraction rides in the product's carry chain
-template <class F> TRH_HD Fy<F> fy_mul_sub(const Fy<F>& a, const Fy<F>& b, const Fy<F>& s) {
-    i64 acc[18];
-    fy_products(acc, a, b);
-    return fy_reduce_sub<F, 1>(acc, &s, nullptr);
-}
+// a b - s (U2 - X, S2 - Y of the mixed addition): the subtraction rides in the product's result columns
+template <class F> TRH_HD Fy<F> fy_mul_sub(const Fy<F>& a, const Fy<F>& b, const Fy<F>& s) { return fy_mulred<F, false, false, 1, false>(a, b, a, b, &s, nullptr); }
 // a^2 - s1 - 2 s2 (x3 = R^2 - PPP - 2 Q)
 template <class F> TRH_HD Fy<F> fy_sqr_sub_sub2(const Fy<F>& a, const Fy<F>& s1, const Fy<F>& s2) {
-    i64 acc[18];
-    fy_squares(acc, a);
-    return fy_reduce_sub<F, 2>(acc, &s1, &s2);
+    return fy_mulred<F, true, false, 2, false>(a, a, a, a, &s1, &s2);
 }
 // carry propagation: any limbs (|l[k]| < 2^31 - 2^3) -> normalised
 template <class F> TRH_HD Fy<F> fy_norm(const Fy<F>& a) {

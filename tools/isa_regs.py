@@ -17,7 +17,9 @@ def short(name):
     return name.split("(")[0][-60:]
 
 
-def main():
+def collect(count_instructions=True):
+    """{kernel<Field>: {"vgpr", "sgpr", "scratch", "lds", "isa_instructions"}} of the objects `make` left in csrc/ (read only); without
+    count_instructions the code objects are not disassembled and isa_instructions is 0"""
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
         for obj in sorted(glob.glob(os.path.join(ROOT, "tiny-ram-halo2_amd", "csrc", "*.o"))):
@@ -28,7 +30,7 @@ def main():
                 notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True).stdout
                 # static instruction count per kernel: lines of the disassembly between the kernel's label and the next one
                 counts, cur_fn = {}, None
-                for line in subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", co], capture_output=True, text=True).stdout.splitlines():
+                for line in subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", co], capture_output=True, text=True).stdout.splitlines() if count_instructions else []:
                     m = re.match(r"^[0-9a-f]+ <(\S+)>:$", line)
                     if m:
                         cur_fn = m.group(1)
@@ -54,10 +56,15 @@ def main():
                         if prev is None or ent["vgpr"] > prev["vgpr"]:
                             out[cur["short"]] = ent  # template instances that share a short name: the largest
                         cur = {}
+    return out
+
+
+def main():
+    out = collect()
     path = os.path.join(ROOT, "profiles", "isa_registers.json")
     json.dump(dict(sorted(out.items())), open(path, "w"), indent=1)
     print(f"{len(out)} kernels -> {path}")
-    for k in ("msm_accumulate_seg_kernel<Fp>", "ntt_passy_kernel", "msm_reduce_kernel<Fp>"):
+    for k in ("msm_accumulate_seg_kernel<Fp>", "msm_combine_kernel<Fp>", "msm_reduce_kernel<Fp>", "ntt_passy_kernel<Fp>"):
         print(k, out.get(k))
 
 

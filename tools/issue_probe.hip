@@ -7,6 +7,11 @@
 //   mix_dep    the reduction-round shape: and -> shift-add -> 5 mads that use the and's result, round after round
 //   mix_<op>   8 mads + 4 <op> for the other instruction classes of the kernel's carry handling: v_and_b32, v_ashrrev_i64 (64-bit shift),
 //              v_lshl_add_u64 (64-bit add), v_mov_b32
+//   chain_d<D> 12 v_mad_i64_i32 per iteration on D = 1, 2, 3 accumulators in turn: each multiply-add waits for the one D before it (the
+//              dependent issue latency a product accumulated BY COLUMNS lives on; `mad` above is distance 8)
+//   column     the column shape of a product accumulated by columns: 7 dependent multiply-adds starting from the carry, one asm
+//              block, then v_and_b32 (the quotient digit, a multiplier of the next column) and v_ashrrev_i64 (the next carry)
+//   column_x2  two independent multiplications interleaved column by column in one block
 // Reports, per row, the AVERAGE SIMD cycles per wave instruction and -- what the issue model needs (round 3 read the
 // average of the 8 + 4 mix as the cost of the add) -- the MARGINAL cost of the non-mad instruction:
 //     (cycles of the mixed loop - mads x cycles per mad in the pure-mad loop at the same occupancy) / others
@@ -97,7 +102,7 @@ __global__ void __launch_bounds__(256) k_mix_indep(u64* out, i32 a, i32 b) {
     out[blockIdx.x * blockDim.x + threadIdx.x] = r;
     if ((threadIdx.x & 63) == 0) g_cycles[blockIdx.x * 4 + (threadIdx.x >> 6)] = clock64() - t_begin;
 }
-// the shape of fy_reduce_sub's rounds: r = col & MASK; next += col >> 29; five multiply-adds with r
+// the shape of the BY-ROWS reduction rounds of rounds 4 - 6: r = col & MASK; next += col >> 29; five multiply-adds with r
 __global__ void __launch_bounds__(256) k_mix_dep(u64* out, i32 a, i32 b) {
     const u64 t_begin = clock64();
     i64 c[10];
@@ -118,6 +123,58 @@ __global__ void __launch_bounds__(256) k_mix_dep(u64* out, i32 a, i32 b) {
     u64 r = 0;
     for (int k = 0; k < 10; ++k) r ^= (u64)c[k];
     out[blockIdx.x * blockDim.x + threadIdx.x] = r;
+    if ((threadIdx.x & 63) == 0) g_cycles[blockIdx.x * 4 + (threadIdx.x >> 6)] = clock64() - t_begin;
+}
+template <int D>
+__global__ void __launch_bounds__(256) k_chain(u64* out, i32 a, i32 b) {
+    const u64 t_begin = clock64();
+    i64 x[D];
+    for (int k = 0; k < D; ++k) x[k] = threadIdx.x + k;
+    i32 aa = a + threadIdx.x, bb = b + threadIdx.x;
+    for (int i = 0; i < ITERS; ++i) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) mac(x[k % D], aa, bb);
+    }
+    u64 r = 0;
+    for (int k = 0; k < D; ++k) r ^= (u64)x[k];
+    out[blockIdx.x * blockDim.x + threadIdx.x] = r;
+    if ((threadIdx.x & 63) == 0) g_cycles[blockIdx.x * 4 + (threadIdx.x >> 6)] = clock64() - t_begin;
+}
+// one column: acc = carry + 7 products, q = acc & MASK, carry = acc >> 29 (in place); q is a multiplier of the next column
+#define COL7(c, q, p) \
+    asm volatile("v_mad_i64_i32 %0, vcc, %2, %3, %0\n\tv_mad_i64_i32 %0, vcc, %2, %4, %0\n\tv_mad_i64_i32 %0, vcc, %2, %5, %0\n\t"   \
+                 "v_mad_i64_i32 %0, vcc, %2, %6, %0\n\tv_mad_i64_i32 %0, vcc, %7, %3, %0\n\tv_mad_i64_i32 %0, vcc, %7, %4, %0\n\t"   \
+                 "v_mad_i64_i32 %0, vcc, %7, %5, %0"                                                                                    \
+                 : "+v"(c), "=&v"(q) : "v"(p), "v"(p1), "v"(p2), "v"(p3), "v"(p4), "v"(aa) : "vcc");                                   \
+    q = (i32)((u32)c & 0x1fffffffu); c >>= 29
+__global__ void __launch_bounds__(256) k_column(u64* out, i32 a, i32 b) {
+    const u64 t_begin = clock64();
+    i64 c = ((i64)threadIdx.x << 33) + 1;
+    i32 p1 = a + 1, p2 = a + 2, p3 = a + 3, p4 = a + 4, aa = b + threadIdx.x, q = aa, q2;
+    for (int i = 0; i < ITERS / 8; ++i) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { COL7(c, q2, q); COL7(c, q, q2); }
+    }
+    out[blockIdx.x * blockDim.x + threadIdx.x] = (u64)c ^ (u32)q;
+    if ((threadIdx.x & 63) == 0) g_cycles[blockIdx.x * 4 + (threadIdx.x >> 6)] = clock64() - t_begin;
+}
+#define COL7X2(c, q, p, d, r, s) \
+    asm volatile("v_mad_i64_i32 %0, vcc, %4, %6, %0\n\tv_mad_i64_i32 %2, vcc, %5, %6, %2\n\tv_mad_i64_i32 %0, vcc, %4, %7, %0\n\t"     \
+                 "v_mad_i64_i32 %2, vcc, %5, %7, %2\n\tv_mad_i64_i32 %0, vcc, %4, %8, %0\n\tv_mad_i64_i32 %2, vcc, %5, %8, %2\n\t"     \
+                 "v_mad_i64_i32 %0, vcc, %4, %9, %0\n\tv_mad_i64_i32 %2, vcc, %5, %9, %2\n\tv_mad_i64_i32 %0, vcc, %10, %6, %0\n\t"    \
+                 "v_mad_i64_i32 %2, vcc, %10, %6, %2\n\tv_mad_i64_i32 %0, vcc, %10, %7, %0\n\tv_mad_i64_i32 %2, vcc, %10, %7, %2\n\t"  \
+                 "v_mad_i64_i32 %0, vcc, %10, %8, %0\n\tv_mad_i64_i32 %2, vcc, %10, %8, %2"                                           \
+                 : "+v"(c), "=&v"(q), "+v"(d), "=&v"(r) : "v"(p), "v"(s), "v"(p1), "v"(p2), "v"(p3), "v"(p4), "v"(aa) : "vcc");       \
+    q = (i32)((u32)c & 0x1fffffffu); r = (i32)((u32)d & 0x1fffffffu); c >>= 29; d >>= 29
+__global__ void __launch_bounds__(256) k_column_x2(u64* out, i32 a, i32 b) {
+    const u64 t_begin = clock64();
+    i64 c = ((i64)threadIdx.x << 33) + 1, d = c + 5;
+    i32 p1 = a + 1, p2 = a + 2, p3 = a + 3, p4 = a + 4, aa = b + threadIdx.x, q = aa, q2, r = aa + 1, r2;
+    for (int i = 0; i < ITERS / 16; ++i) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { COL7X2(c, q2, q, d, r2, r); COL7X2(c, q, q2, d, r, r2); }
+    }
+    out[blockIdx.x * blockDim.x + threadIdx.x] = (u64)c ^ (u32)q ^ (u64)d ^ (u32)r;
     if ((threadIdx.x & 63) == 0) g_cycles[blockIdx.x * 4 + (threadIdx.x >> 6)] = clock64() - t_begin;
 }
 __global__ void k_clock(u64* out) {
@@ -161,13 +218,15 @@ int main() {
     printf("avg = SIMD cycles per wave instruction over ALL instructions of the loop; marginal = cycles the non-mad instruction adds to a stream of mads\n"
            "  = (loop cycles - mads x cycles per mad of the pure-mad row at the same occupancy) / others; `norm` rescales so that the mad row is 4.00\n");
     const int cus = prop.multiProcessorCount;
-    constexpr int NR = 8;
+    constexpr int NR = 13;
     for (int wps : {2, 3, 4, 8}) {
         const int blocks = cus * wps;  // 256-thread workgroups = 4 waves = one per SIMD
         struct { const char* name; double mads, others; double ms; } rows[NR] = {
             {"mad", 8.0 * ITERS, 0, 0}, {"add", 0, 8.0 * ITERS, 0}, {"mix_indep 8 mad + 4 v_add_u32", 8.0 * ITERS, 4.0 * ITERS, 0}, {"mix_dep 5 mad + 3 alu per round", 5.0 * ITERS, 3.0 * ITERS, 0},
             {"mix 8 mad + 4 v_and_b32", 8.0 * ITERS, 4.0 * ITERS, 0}, {"mix 8 mad + 4 v_mov_b32", 8.0 * ITERS, 4.0 * ITERS, 0},
-            {"mix 8 mad + 4 v_ashrrev_i64", 8.0 * ITERS, 4.0 * ITERS, 0}, {"mix 8 mad + 4 v_lshl_add_u64", 8.0 * ITERS, 4.0 * ITERS, 0}};
+            {"mix 8 mad + 4 v_ashrrev_i64", 8.0 * ITERS, 4.0 * ITERS, 0}, {"mix 8 mad + 4 v_lshl_add_u64", 8.0 * ITERS, 4.0 * ITERS, 0},
+            {"chain_d1 12 mad, distance 1", 12.0 * ITERS, 0, 0}, {"chain_d2 12 mad, distance 2", 12.0 * ITERS, 0, 0}, {"chain_d3 12 mad, distance 3", 12.0 * ITERS, 0, 0},
+            {"column 7 mad + and + ashr", 7.0 * ITERS, 2.0 * ITERS, 0}, {"column_x2 2 x (7 mad + and + ashr)", 7.0 * ITERS, 2.0 * ITERS, 0}};
         double cyc[NR];
         rows[0].ms = run([](int b, u64* o) { hipLaunchKernelGGL(k_mad, dim3(b), dim3(256), 0, 0, o, 3, 5); }, blocks, d_out, &cyc[0]);
         rows[1].ms = run([](int b, u64* o) { hipLaunchKernelGGL(k_add, dim3(b), dim3(256), 0, 0, o, 3, 5); }, blocks, d_out, &cyc[1]);
@@ -177,13 +236,18 @@ int main() {
         rows[5].ms = run([](int b, u64* o) { hipLaunchKernelGGL(k_mix_op<OpMov>, dim3(b), dim3(256), 0, 0, o, 3, 5); }, blocks, d_out, &cyc[5]);
         rows[6].ms = run([](int b, u64* o) { hipLaunchKernelGGL(k_mix_op<OpShr64>, dim3(b), dim3(256), 0, 0, o, 3, 5); }, blocks, d_out, &cyc[6]);
         rows[7].ms = run([](int b, u64* o) { hipLaunchKernelGGL(k_mix_op<OpAdd64>, dim3(b), dim3(256), 0, 0, o, 3, 5); }, blocks, d_out, &cyc[7]);
+        rows[8].ms = run([](int b, u64* o) { hipLaunchKernelGGL(k_chain<1>, dim3(b), dim3(256), 0, 0, o, 3, 5); }, blocks, d_out, &cyc[8]);
+        rows[9].ms = run([](int b, u64* o) { hipLaunchKernelGGL(k_chain<2>, dim3(b), dim3(256), 0, 0, o, 3, 5); }, blocks, d_out, &cyc[9]);
+        rows[10].ms = run([](int b, u64* o) { hipLaunchKernelGGL(k_chain<3>, dim3(b), dim3(256), 0, 0, o, 3, 5); }, blocks, d_out, &cyc[10]);
+        rows[11].ms = run([](int b, u64* o) { hipLaunchKernelGGL(k_column, dim3(b), dim3(256), 0, 0, o, 3, 5); }, blocks, d_out, &cyc[11]);
+        rows[12].ms = run([](int b, u64* o) { hipLaunchKernelGGL(k_column_x2, dim3(b), dim3(256), 0, 0, o, 3, 5); }, blocks, d_out, &cyc[12]);
         // every SIMD holds wps waves for the whole kernel: SIMD cycles per wave instruction = wave lifetime / (instructions per wave x wps)
         const double mad_cyc = cyc[0] / (rows[0].mads * wps);      // cycles per mad, pure-mad loop
         const double mad_ms = rows[0].ms / (rows[0].mads * wps);   // the same in wall time
         for (int i = 0; i < NR; ++i) {
             auto& r = rows[i];
             const double per_inst = cyc[i] / ((r.mads + r.others) * wps);
-            printf("waves/SIMD %d  %-32s %8.3f ms  avg %5.2f (norm %5.2f) cycles/inst, clock %.2f GHz", wps, r.name, r.ms, per_inst, per_inst * 4.0 / mad_cyc, cyc[i] / (r.ms * 1e-3) / 1e9);
+            printf("waves/SIMD %d  %-36s %8.3f ms  avg %5.2f (norm %5.2f) cycles/inst, clock %.2f GHz", wps, r.name, r.ms, per_inst, per_inst * 4.0 / mad_cyc, cyc[i] / (r.ms * 1e-3) / 1e9);
             if (r.others > 0) {
                 const double marg_cyc = (cyc[i] / wps - r.mads * mad_cyc) / r.others;
                 const double marg_ms = (r.ms / wps - r.mads * mad_ms) / r.others;
