@@ -299,6 +299,15 @@ int trh_ipa_create_proof(trh_bases_t g_w, const uint64_t u_xy[8], uint32_t k, co
                          const uint64_t s_blind[4], const trh_transcript_t* transcript,
                          trh_rng_scalar_fn rng, void* rng_ctx, void* stream,
                          uint64_t out_c[4], uint64_t out_f[4]);
+/* The generator collapse of that opening on its own (csrc/ipafold.hip), for tests and for callers that keep their own round loop:
+ * G''[i] = sum over t < 2^r of s_t G[i + t 2^(k-r)], i < 2^(k-r), s_t = the product of u_j over the set bits (r - 1 - j) of t -- what r
+ * rounds of parallel_generator_collapse leave of the first 2^k points of `bases`.  bases: a set on one device of at least 2^k points
+ * with a fixed-base table attached (trh_bases_precompute); the table's rows are as long as the set, so a g || w || u set collapses as
+ * in the opening.  Supported shapes: table windows of 10 .. 18 bits, 2 <= r <= 10, k >= r + 8; anything else is TRH_EINVAL.
+ * u_mont: r x 4 Montgomery words in round order, host memory.  out_xy_dev: 2^(k-r) 64-byte affine points (identity: all zero);
+ * out_rec_dev: the same points as 128-byte records of the MSM's accumulation (x, y, -y in the signed 29-bit limbs; identity: all zero).
+ * Returns with the stream synchronised.                                                                                            */
+int trh_ipa_collapse_generators_dev(trh_bases_t bases, uint32_t k, uint32_t r, const uint64_t* u_mont, void* out_xy_dev, void* out_rec_dev, void* stream);
 
 /* ---- IPA verifier accumulator: poly::commitment::msm::MSM and verifier::Guard::use_challenges (halo2_proofs 0.2.0
  *      poly/commitment/{msm.rs, verifier.rs}; reached from plonk::verify_proof / BatchVerifier::finalize after the proofs are made,

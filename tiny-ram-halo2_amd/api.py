@@ -124,6 +124,7 @@ _SIGNATURES = {
     "trh_domain_extended_to_coeff": ([_vp, _vp, ctypes.c_size_t, _vp], ctypes.c_int),
     "trh_domain_divide_by_vanishing_poly": ([_vp, _vp, ctypes.c_size_t, _vp], ctypes.c_int),
     "trh_ipa_create_proof": ([_vp, _u64p, ctypes.c_uint32, _vp, _u64p, _u64p, _vp, _u64p, ctypes.POINTER(Transcript), RNG_FN, _vp, _vp, _u64p, _u64p], ctypes.c_int),
+    "trh_ipa_collapse_generators_dev": ([_vp, ctypes.c_uint32, ctypes.c_uint32, _u64p, _vp, _vp, _vp], ctypes.c_int),
     "trh_ipa_msm_create": ([_vp, ctypes.c_uint32, _u64p, ctypes.POINTER(_vp)], ctypes.c_int),
     "trh_ipa_msm_destroy": ([_vp], None),
     "trh_ipa_msm_append_term": ([_vp, _u64p, _u64p], ctypes.c_int),
@@ -686,6 +687,21 @@ class Bases:
     def reserve(self, n: int, batch: int = 1) -> None:
         """trh_bases_reserve: sizes the calling context's MSM scratch for batches of `batch` MSMs over the first n bases, without running one"""
         _check(lib().trh_bases_reserve(self.handle, n, batch))
+
+    def collapse_generators(self, k: int, u, stream=None):
+        """trh_ipa_collapse_generators_dev: the first 2^k points after the r = len(u) collapses of an IPA opening, from this set's
+        fixed-base table.  u: (r, 4) Montgomery challenges in round order.  Returns (xy, rec) on the host: (2^(k-r), 8) uint64 affine
+        points and (2^(k-r), 32) uint32 records of the MSM's accumulation"""
+        uu = _c(u, 4)
+        r = uu.shape[0]
+        m = 1 << max(int(k) - r, 0)
+        d_xy, d_rec = DeviceBuffer(m * 64), DeviceBuffer(m * 128)
+        try:
+            _check(lib().trh_ipa_collapse_generators_dev(self.handle, k, r, _p(uu), d_xy.ptr, d_rec.ptr, stream))
+            return d_xy.to_host(np.uint64, (m, 8)), d_rec.to_host(np.uint32, (m, 32))
+        finally:
+            d_xy.free()
+            d_rec.free()
 
     def download(self, offset: int = 0, n: int | None = None) -> np.ndarray:
         n = len(self) - offset if n is None else n

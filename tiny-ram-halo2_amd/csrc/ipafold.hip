@@ -20,14 +20,13 @@
 
 #include "ctx.h"
 #include "devmem.h"
+#include "foldplan.h"
 #include "hostcombine.h"
 
 namespace trh {
 namespace {
 
-constexpr u32 FOLD_SIGN = 0x80000000u;
-
-// plan = offsets[nbk + 1] then entries: level j << 16 | t | sign << 31 (host: fold_plan)
+// plan = offsets[nbk + 1] then entries: level j << 16 | t | sign << 31 (host: foldplan.h fold_plan)
 // grid (m / 256, nbk): every lane of a workgroup walks the SAME list -- the control flow is uniform and the loads are contiguous over i
 template <class BF>
 __global__ void __launch_bounds__(256) ipa_fold_accumulate_kernel(const uint4* __restrict__ table, size_t row /* points per table level */, u32 log_m,
@@ -183,44 +182,6 @@ __global__ void __launch_bounds__(64) ipa_fold_affine_kernel(const XYZZzMem* __r
     z[7] = make_uint4(0u, 0u, 0u, 0u);
 }
 
-// the bucket lists of the 2^r shared scalars (canonical 4 x 64-bit words each): offsets[nbk + 1], then the entries bucket by bucket
-int fold_plan(const std::vector<hostcombine::H>& sc, int c, int W, u32 w0, u32 w1, std::vector<u32>& plan, u32& nbk) {
-    const u32 nb0 = 1u << (w0 - 1), nb1 = 1u << (w1 - 1);
-    nbk = nb0 + nb1;
-    std::vector<u32> bucket, entry;
-    bucket.reserve(sc.size() * W * 2); entry.reserve(sc.size() * W * 2);
-    std::vector<u32> count(nbk + 1, 0);
-    auto bits = [](const hostcombine::H& v, u32 o, u32 w) -> u32 {
-        if (o >= 256) return 0;
-        uint64_t x = v.l[o >> 6] >> (o & 63);
-        if ((o & 63) + w > 64 && (o >> 6) + 1 < 4) x |= v.l[(o >> 6) + 1] << (64 - (o & 63));
-        return (u32)(x & ((1ull << w) - 1));
-    };
-    for (size_t t = 0; t < sc.size(); ++t) {
-        u32 carry = 0;
-        for (int j = 0; j < W; ++j)
-            for (u32 s = 0; s < 2; ++s) {
-                const u32 w = s ? w1 : w0;
-                int d = (int)(bits(sc[t], (u32)(c * j) + (s ? w0 : 0), w) + carry);
-                if (d > (1 << (w - 1))) { d -= 1 << w; carry = 1; } else carry = 0;
-                if (!d) continue;
-                const u32 mag = (u32)(d < 0 ? -d : d);
-                const u32 b = (s ? nb0 : 0) + mag - 1;
-                bucket.push_back(b);
-                entry.push_back(((u32)j << 16) | (u32)t | (d < 0 ? FOLD_SIGN : 0u));
-                ++count[b];
-            }
-        if (carry) { set_error("ipa fold: a fold scalar does not fit the table's %d windows of %d bits", W, c); return TRH_EINVAL; }
-    }
-    plan.assign(nbk + 1 + entry.size(), 0);
-    u32 run = 0;
-    for (u32 b = 0; b < nbk; ++b) { plan[b] = run; run += count[b]; }
-    plan[nbk] = run;
-    std::vector<u32> cur(plan.begin(), plan.begin() + nbk);
-    for (size_t e = 0; e < entry.size(); ++e) plan[nbk + 1 + cur[bucket[e]]++] = entry[e];
-    return TRH_OK;
-}
-
 // buckets (+ the m sums between the reduction and the inversion), the bucket lists and their pinned source
 int fold_buffers(Ctx& c, const MsmFixedBase& fb, uint32_t k, uint32_t r, size_t plan_words, hipStream_t s) {
     const size_t m = (size_t)1 << (k - r);
@@ -257,7 +218,10 @@ int ipa_fold_t(const MsmFixedBase& fb, size_t row, uint32_t k, uint32_t r, const
     for (H& v : sc) v = hostcombine::mul<SF>(v, one_plain);  // out of the Montgomery form: canonical words
     std::vector<u32> plan;
     u32 nbk = 0;
-    TRH_TRY(fold_plan(sc, fb.c, fb.W, w0, w1, plan, nbk));
+    if (foldplan::fold_plan(sc, fb.c, fb.W, w0, w1, plan, nbk) != foldplan::FOLD_PLAN_OK) {
+        set_error("ipa fold: a fold scalar does not fit the table's %d windows of %d bits", fb.W, fb.c);
+        return TRH_EINVAL;
+    }
     DevBuf& buckets = c.ipa[9];
     DevBuf& dplan = c.ipa[10];
     TRH_TRY(fold_buffers(c, fb, k, r, plan.size(), s));
@@ -295,3 +259,24 @@ int ipa_fold_generators(int curve, const MsmFixedBase& fb, size_t row, uint32_t 
 }
 
 }  // namespace trh
+
+using namespace trh;
+
+extern "C" {
+
+int trh_ipa_collapse_generators_dev(trh_bases_t bases, uint32_t k, uint32_t r, const uint64_t* u_mont, void* out_xy_dev, void* out_rec_dev, void* stream) {
+    TRH_TRY(require_init());
+    if (!bases || !u_mont || !out_xy_dev || !out_rec_dev) { set_error("ipa_collapse_generators: null pointer"); return TRH_EINVAL; }
+    if (!bases->shards.empty()) { set_error("ipa_collapse_generators: needs a base set on one device"); return TRH_EINVAL; }
+    if (k > 26 || bases->n < ((size_t)1 << k)) { set_error("ipa_collapse_generators: k = %u over a set of %zu points (at least 2^k are needed)", k, bases->n); return TRH_EINVAL; }
+    if (!bases->d_table) { set_error("ipa_collapse_generators: the set has no fixed-base table (trh_bases_precompute)"); return TRH_EINVAL; }
+    TRH_ENTER(stream);
+    Range range("trh_ipa_collapse_generators_dev");
+    if (bases->owner && bases->owner->device != ctx().device) { set_error("ipa_collapse_generators: the base set lives on another device than the calling context"); return TRH_EINVAL; }
+    TRH_TRY(ipa_fold_generators(bases->curve, bases->fb, bases->n, k, r, (const u64*)u_mont, out_xy_dev, out_rec_dev, (hipStream_t)stream));
+    // the bucket lists go up from ONE pinned buffer, which the next collapse overwrites: like an opening, the call ends with the stream drained
+    TRH_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return TRH_OK;
+}
+
+}  // extern "C"
