@@ -499,6 +499,35 @@ int trh_rng_fill_dev(trh_rng_t r, int field, void* out_dev, size_t n, void* stre
  * first + count > row_len is TRH_EINVAL.                                                                                                   */
 int trh_rng_fill_rows_dev(trh_rng_t r, int field, void* cols_dev, size_t rows, size_t row_len, size_t first, size_t count, void* stream);
 
+/* ---- permutation keygen: plonk/permutation/keygen.rs `Assembly` { copy, build_vk, build_pk } (halo2_proofs 0.2.0, reached from keygen_vk /
+ *      keygen_pk) and the permutation part of MockProver::verify ---------------------------------------------------------------------------
+ * The assembly records the circuit's copy constraints over n_columns equality-enabled columns of n = 2^k rows and keeps the permutation they
+ * induce.  A cell is one u32, cell = column * n + row, so n_columns * n <= 2^32 (and n_columns >= 1, k <= 27).  trh_perm_copy is
+ * `Assembly::copy`: the cycles of the two cells are merged, the smaller into the larger, and the mapping of the two cells is swapped; copying
+ * a cell to itself or repeating a copy changes nothing; a cell outside the columns is TRH_EINVAL and changes nothing.  The ORDER of the
+ * copies decides the mapping (and through it the sigma commitments of the verifying key), as upstream -- restated as recalled, csrc/permkeygen.h.
+ * trh_perm_sigma_dev writes the sigma columns build_vk commits and build_pk transforms: for `count` columns from first_column,
+ *     sigma[c][r] = delta^(m / n) * omega^(m % n),  m = mapping[c * n + r]
+ * (omega: the 2^k-th root of unity of EvaluationDomain, delta = 5^(2^32), pasta_curves DELTA), count x n elements back to back in device
+ * memory, asynchronous on `stream` except for the upload of the mapping: the handle keeps one device copy per context, made by the first
+ * device call after a copy (that call synchronises `stream` once) and reused until the next copy.
+ * trh_perm_check_dev counts the cells whose value differs from the value of the cell they map to -- columns_dev: n_columns device pointers
+ * (host array), n elements each, canonical stored forms, compared word by word; *n_bad = 0 means the copy constraints hold;
+ * *first_bad_cell = the smallest such cell, n_columns * n when there is none.  It synchronises the stream.
+ * The handle is HOST memory, like trh_rng_t: create, copy, mapping and destroy need no device.  Every entry takes the handle first; the device
+ * entries take the field id second (an unknown id is refused as everywhere else).                                                        */
+typedef struct trh_perm_s* trh_perm_t;
+int trh_perm_create(uint32_t n_columns, uint32_t k, trh_perm_t* out);   /* no device needed */
+void trh_perm_destroy(trh_perm_t p);
+int trh_perm_copy(trh_perm_t p, uint32_t left_column, uint32_t left_row, uint32_t right_column, uint32_t right_row);
+/* quads: count x (left_column, left_row, right_column, right_row), applied in order; stops at the first refused one (trh_last_error() names
+ * its index; the copies before it stay made) */
+int trh_perm_copy_batch(trh_perm_t p, const uint32_t* quads, size_t count);
+/* the mapping of `count` columns from first_column: out_cells[(c - first_column) * n + r] = the cell that cell (c, r) maps to */
+int trh_perm_mapping(trh_perm_t p, uint32_t first_column, uint32_t count, uint32_t* out_cells);
+int trh_perm_sigma_dev(trh_perm_t p, int field, uint32_t first_column, uint32_t count, void* out_dev, void* stream);
+int trh_perm_check_dev(trh_perm_t p, int field, const void* const* columns_dev, uint64_t* n_bad, uint64_t* first_bad_cell, void* stream);
+
 /* ---- element-wise field / group ops on device memory (parity tests of the device arithmetic;
  *      op: 0 add, 1 sub, 2 mul, 3 sqr, 4 neg, 5 inv, 6 to_mont, 7 from_mont) ------------------ */
 int trh_field_op_dev(int field, int op, const void* a_dev, const void* b_dev, void* out_dev, size_t n, void* stream);

@@ -12,6 +12,7 @@
 //   trh::ipa_create_proof                   poly::commitment::create_proof (IPA opening)
 //   trh::IpaMsm                             poly::commitment::msm::MSM + Guard::use_challenges (the verifier's accumulator)
 //   trh::Rng                                `C::Scalar::random(rng)` for whole vectors: a ChaCha20 seed expanded on the device
+//   trh::PermutationAssembly                plonk::permutation::keygen::Assembly { copy, build_vk, build_pk } (+ the copy-constraint check)
 //
 // Reference call sites of all of these: /root/reference/src/test_utils.rs:21-49, 89-104 (through keygen_* and
 // create_proof of the halo2_proofs crate pinned at /root/reference/Cargo.lock:619-621).
@@ -534,6 +535,67 @@ struct RngScalarFn {
         RngScalarFn* s = (RngScalarFn*)self;
         if (trh_rng_next_scalar(s->rng.handle(), (int)s->field, out_mont) != TRH_OK) { s->failed = true; for (int i = 0; i < 4; ++i) out_mont[i] = 0; }
     }
+};
+
+// ---- plonk::permutation::keygen::Assembly (trh_perm_*): the copy constraints of the equality-enabled columns, the sigma columns they
+// induce -- made on the device -- and what keygen_vk / keygen_pk derive from them ---------------------------------------------------------
+// copy() merges cycles exactly as upstream does (the order of the copies decides the mapping).  Host memory, like Rng: copies and mapping()
+// need no device; the device copy of the mapping is made by the first device call after a copy.
+class PermutationAssembly {
+public:
+    PermutationAssembly(Field f, uint32_t k, uint32_t n_columns) : field(f), k(k), n((size_t)1 << (k & 31)), n_columns(n_columns) { check(trh_perm_create(n_columns, k, &p_), "permutation::Assembly::new"); }
+    PermutationAssembly(const PermutationAssembly&) = delete;
+    PermutationAssembly& operator=(const PermutationAssembly&) = delete;
+    PermutationAssembly(PermutationAssembly&& o) noexcept : field(o.field), k(o.k), n(o.n), n_columns(o.n_columns), p_(o.p_) { o.p_ = nullptr; }
+    PermutationAssembly& operator=(PermutationAssembly&& o) noexcept { std::swap(field, o.field); std::swap(k, o.k); std::swap(n, o.n); std::swap(n_columns, o.n_columns); std::swap(p_, o.p_); return *this; }
+    ~PermutationAssembly() { if (p_) trh_perm_destroy(p_); }
+    trh_perm_t handle() const { return p_; }
+    void copy(uint32_t left_column, uint32_t left_row, uint32_t right_column, uint32_t right_row) { check(trh_perm_copy(p_, left_column, left_row, right_column, right_row), "permutation::Assembly::copy"); }
+    // (left_column, left_row, right_column, right_row) per copy, in order
+    void copy_many(const std::vector<std::array<uint32_t, 4>>& quads) { check(trh_perm_copy_batch(p_, (const uint32_t*)quads.data(), quads.size()), "permutation::Assembly::copy"); }
+    // the cell (column * n + row) every cell of `count` columns from `first` maps to
+    std::vector<uint32_t> mapping(uint32_t first, uint32_t count) const { std::vector<uint32_t> m((size_t)count * n); check(trh_perm_mapping(p_, first, count, m.data()), "perm_mapping"); return m; }
+    std::vector<uint32_t> mapping() const { return mapping(0, n_columns); }
+    // the sigma columns first .. first + count - 1 in Lagrange form, count x n elements back to back
+    DeviceBuffer sigma_columns(uint32_t first, uint32_t count, void* stream = nullptr) const {
+        DeviceBuffer out((size_t)count * n * 32);
+        check(trh_perm_sigma_dev(p_, (int)field, first, count, out.data(), stream), "perm_sigma");
+        return out;
+    }
+    DeviceBuffer sigma_columns(void* stream = nullptr) const { return sigma_columns(0, n_columns, stream); }
+    // the permutation part of MockProver::verify over n_columns device columns of n canonical elements: the number of cells whose value
+    // differs from the value of the cell they map to, and the smallest of them (n_columns * n when there is none)
+    struct Check { uint64_t n_bad, first_bad_cell; };
+    Check check_columns(const std::vector<const void*>& columns, void* stream = nullptr) const {
+        require(columns.size() == n_columns, "one device pointer per column");
+        Check c{0, 0};
+        check(trh_perm_check_dev(p_, (int)field, columns.data(), &c.n_bad, &c.first_bad_cell, stream), "perm_check");
+        return c;
+    }
+    // Assembly::build_vk: params.commit_lagrange(sigma_j, Blind::default()) for every column (the default blind is one)
+    std::vector<Point> build_vk(const Params& params, void* stream = nullptr) const {
+        require(params.k == k && scalar_field(params.curve) == field, "params.k == k, over the curve whose scalars the columns hold");
+        const DeviceBuffer sigma = sigma_columns(stream);
+        return params.commit_lagrange_batch(sigma, n_columns, std::vector<Limbs>(n_columns, host::one(field)), stream);
+    }
+    // Assembly::build_pk: the sigma columns, lagrange_to_coeff of them, coeff_to_extended of those
+    struct ProvingKey { DeviceBuffer permutations, polys, cosets; };
+    ProvingKey build_pk(const EvaluationDomain& domain, void* stream = nullptr) const {
+        require(domain.k == k && domain.field == field, "domain.k == k, same field");
+        ProvingKey pk;
+        pk.permutations = sigma_columns(stream);
+        pk.polys = sigma_columns(stream);
+        domain.lagrange_to_coeff(pk.polys.data(), n_columns, stream);
+        pk.cosets = DeviceBuffer((size_t)n_columns * domain.extended_len() * 32);
+        domain.coeff_to_extended(pk.polys.data(), pk.cosets.data(), n_columns, stream);
+        return pk;
+    }
+    Field field;
+    uint32_t k;
+    size_t n;
+    uint32_t n_columns;
+private:
+    trh_perm_t p_ = nullptr;
 };
 
 // ---- poly::commitment::create_proof (IPA opening) -------------------------------------------------------------------

@@ -199,6 +199,13 @@ _SIGNATURES = {
     "trh_rng_next_scalar": ([_vp, ctypes.c_int, _u64p], ctypes.c_int),
     "trh_rng_fill_dev": ([_vp, ctypes.c_int, _vp, ctypes.c_size_t, _vp], ctypes.c_int),
     "trh_rng_fill_rows_dev": ([_vp, ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, _vp], ctypes.c_int),
+    "trh_perm_create": ([ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_vp)], ctypes.c_int),
+    "trh_perm_destroy": ([_vp], None),
+    "trh_perm_copy": ([_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32], ctypes.c_int),
+    "trh_perm_copy_batch": ([_vp, _vp, ctypes.c_size_t], ctypes.c_int),
+    "trh_perm_mapping": ([_vp, ctypes.c_uint32, ctypes.c_uint32, _vp], ctypes.c_int),
+    "trh_perm_sigma_dev": ([_vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp], ctypes.c_int),
+    "trh_perm_check_dev": ([_vp, ctypes.c_int, ctypes.POINTER(_vp), _u64p, _u64p, _vp], ctypes.c_int),
     "trh_set_timing": ([ctypes.c_int], ctypes.c_int),
     "trh_last_timing": ([ctypes.POINTER(Timing)], ctypes.c_int),
 }

@@ -347,6 +347,8 @@ bool ipa_fold_supported(const MsmFixedBase& fb, uint32_t k, uint32_t r);
 int ipa_fold_reserve(const MsmFixedBase& fb, uint32_t k, uint32_t r);
 int ipa_reserve(int curve, const trh_bases* gw, uint32_t k);  // ipa.hip: the opening's vectors and the collapse's buffers, at setup time
 int ipa_fold_generators(int curve, const MsmFixedBase& fb, size_t row, uint32_t k, uint32_t r, const u64* u_mont, void* out_xy, void* out_z, hipStream_t s);
+// ipa.hip: out[i] = x^i, i < n (trh_field_powers_dev's kernel, for callers inside an entered context: permutation.hip's omega^row and delta^column tables)
+int field_powers_device(int field, void* out_dev, size_t n, const u64 x_mont[4], hipStream_t s);
 // msm.hip
 int msm_enqueue(int curve, const void* bases_dev, const void* bases_z_or_null, const void* scalars_dev, size_t n, size_t batch,
                 size_t scalar_stride_elems, int mont, hipStream_t s, const MsmFixedBase* fb = nullptr, const void* tails_dev = nullptr, MsmFlags flags = {});

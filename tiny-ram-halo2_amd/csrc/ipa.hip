@@ -607,6 +607,11 @@ int ipa_reserve(int curve, const trh_bases* gw, uint32_t k) {
     reserve.reserve_only = true;
     return msm_enqueue(curve, sc[5].p, sc[6].p, sc[4].p, m + 2, 2, m + 2, 1, nullptr, nullptr, nullptr, reserve);
 }
+
+int field_powers_device(int field, void* out_dev, size_t n, const u64 x_mont[4], hipStream_t s) {
+    if (!n) return TRH_OK;
+    return with_field(field, [&](auto f) { return powers_t<decltype(f)>(out_dev, n, x_mont, s); });
+}
 }  // namespace trh
 
 using namespace trh;

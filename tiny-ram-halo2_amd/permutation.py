@@ -7,8 +7,13 @@ src/circuits/tables/prog.rs:151-152, i.e. 47 product columns of 4 columns each -
 built from libtrh primitives: the numerator and denominator products are one two-output expression program
 (expr.compile_outputs), the division is ff::BatchInvert (trh_field_batch_invert_dev) + an element-wise multiply, the
 running product is trh_field_prefix_product_dev.  Blinding rows and the commitment of z are the caller's (the replay
-commits product columns as ordinary Lagrange columns)."""
+commits product columns as ordinary Lagrange columns).
+
+Assembly is the keygen side of the same argument (plonk/permutation/keygen.rs): the copy constraints, the permutation they induce, the sigma
+columns made from it on the device and what keygen_vk / keygen_pk derive from them."""
 from __future__ import annotations
+
+import ctypes
 
 import numpy as np
 
@@ -26,6 +31,95 @@ def omega(field: str, k: int) -> int:
     for _ in range(k, S):
         w = w * w % _MODULUS[field]
     return w
+
+
+class Assembly:
+    """plonk/permutation/keygen.rs `Assembly` over n_columns equality-enabled columns of 2^k rows (trh_perm_*, include/trh.h): copy() records
+    a copy constraint exactly as upstream merges its cycles; the sigma columns sigma[c][r] = delta^(m / n) omega^(m % n), m = mapping[c][r],
+    are written on the device.  The handle is host memory: copies and mapping() need no device."""
+
+    def __init__(self, field: str, k: int, n_columns: int):
+        if not (0 <= k < 1 << 32 and 0 <= n_columns < 1 << 32):
+            raise ValueError(f"Assembly: k = {k}, n_columns = {n_columns}")
+        self.field, self.k, self.n, self.n_columns = field, k, 1 << k, n_columns
+        self.handle = api._vp()
+        api._check(api.lib().trh_perm_create(n_columns, k, ctypes.byref(self.handle)))
+
+    def copy(self, left_column: int, left_row: int, right_column: int, right_row: int) -> None:
+        """Assembly::copy; api.TrhError for a cell outside the columns (nothing changes then)"""
+        for v in (left_column, left_row, right_column, right_row):
+            if not 0 <= v < 1 << 32:
+                raise api.TrhError(f"Assembly.copy: {v} is no column or row index")
+        api._check(api.lib().trh_perm_copy(self.handle, left_column, left_row, right_column, right_row))
+
+    def copy_many(self, quads) -> None:
+        """copy(*q) for every row q = (left_column, left_row, right_column, right_row) of an integer array, in order; stops at the first refused one"""
+        q = np.asarray(quads)
+        if q.size and (q.min() < 0 or q.max() >= 1 << 32):
+            raise api.TrhError("Assembly.copy_many: an entry is no column or row index")
+        q = np.ascontiguousarray(q, dtype=np.uint32).reshape(-1, 4)
+        api._check(api.lib().trh_perm_copy_batch(self.handle, q.ctypes.data_as(api._vp), q.shape[0]))
+
+    def mapping(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """(count, n) uint32: the cell (column * n + row) every cell of the window maps to"""
+        count = self.n_columns - first if count is None else count
+        out = np.empty((max(count, 0), self.n), dtype=np.uint32)
+        api._check(api.lib().trh_perm_mapping(self.handle, first, count, out.ctypes.data_as(api._vp)))
+        return out
+
+    def sigma_columns(self, first: int = 0, count: int | None = None):
+        """-> device tensor (count, n, 4): the sigma columns first .. first + count - 1 (all of them by default), on the current stream"""
+        import torch
+        count = self.n_columns - first if count is None else count
+        if not (0 <= first < 1 << 32 and 0 <= count < 1 << 32):
+            raise api.TrhError(f"Assembly.sigma_columns: columns [{first}, {first} + {count})")
+        dev = torch.device("cuda", max(int(api.lib().trh_ctx_device(None)), 0))
+        out = torch.empty((count, self.n, 4), dtype=torch.int64, device=dev)
+        api._check(api.lib().trh_perm_sigma_dev(self.handle, api.FIELD_ID[self.field], first, count, api._devptr(out), torch.cuda.current_stream(dev).cuda_stream))
+        return out
+
+    def check(self, columns):
+        """the permutation part of MockProver::verify: columns = n_columns device tensors (n, 4) (or one (n_columns, n, 4) tensor) of canonical
+        stored elements -> (n_bad, first_bad): the number of cells whose value differs from the value of the cell they map to, and the
+        smallest of them as (column, row), None when the copy constraints hold"""
+        import torch
+        assert len(columns) == self.n_columns
+        cols = [columns[j] for j in range(self.n_columns)]
+        for t in cols:
+            assert t.is_contiguous() and t.shape == (self.n, 4) and t.device == cols[0].device
+        ptrs = (api._vp * self.n_columns)(*[t.data_ptr() for t in cols])
+        n_bad, first_bad = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        api._check(api.lib().trh_perm_check_dev(self.handle, api.FIELD_ID[self.field], ptrs, ctypes.byref(n_bad), ctypes.byref(first_bad),
+                                               torch.cuda.current_stream(cols[0].device).cuda_stream))
+        if not n_bad.value:
+            return 0, None
+        return int(n_bad.value), (int(first_bad.value) >> self.k, int(first_bad.value) & (self.n - 1))
+
+    def build_vk(self, params) -> np.ndarray:
+        """Assembly::build_vk: one commitment per sigma column, params.commit_lagrange(sigma, Blind::default()) -- the default blind is one --
+        through the batch commit; -> (n_columns, 12) points"""
+        assert params.k == self.k and api.SCALAR_FIELD[params.curve] == self.field
+        from .poly import _mont
+        return params.commit_lagrange_batch(self.sigma_columns(), np.tile(_mont(self.field, 1), (self.n_columns, 1)))
+
+    def build_pk(self, domain):
+        """Assembly::build_pk -> (permutations, polys, cosets): the sigma columns in Lagrange form, lagrange_to_coeff of them and
+        coeff_to_extended of those, as device tensors (n_columns, n or 2^extended_k, 4)"""
+        assert domain.k == self.k and domain.field == self.field
+        permutations = self.sigma_columns()
+        polys = domain.lagrange_to_coeff(permutations.clone())
+        return permutations, polys, domain.coeff_to_extended(polys)
+
+    def destroy(self):
+        if self.handle:
+            api.lib().trh_perm_destroy(self.handle)
+            self.handle = api._vp()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
 
 
 class GrandProduct:
