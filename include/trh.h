@@ -528,6 +528,28 @@ int trh_perm_mapping(trh_perm_t p, uint32_t first_column, uint32_t count, uint32
 int trh_perm_sigma_dev(trh_perm_t p, int field, uint32_t first_column, uint32_t count, void* out_dev, void* stream);
 int trh_perm_check_dev(trh_perm_t p, int field, const void* const* columns_dev, uint64_t* n_bad, uint64_t* first_bad_cell, void* stream);
 
+/* ---- hash_to_curve: `Params::new(k)` (halo2_proofs 0.2.0 poly/commitment.rs), 2^k + 2 calls of pasta_curves 0.4 `C::hash_to_curve(prefix)(msg)` --
+ * RFC 9380's hash_to_curve over BLAKE2b-512: expand_message_xmd with DST = prefix || "-" || "pallas" / "vesta" || "_XMD:BLAKE2b_SSWU_RO_" to two
+ * elements of the curve's BASE field, simplified SWU (Z = -13) onto the iso-curve y^2 = x^3 + A x + 1265, the 3-isogeny to y^2 = x^3 + 5, cofactor 1
+ * (csrc/hashtocurve.h restates every step; that the Rust crates produce these very bytes is recalled, not pinned -- DESIGN.md section 4).
+ * Params::new: g[i] = hash("Halo2-Parameters")(00 || le32(i)), w = hash(..)(01), u = hash(..)(02), then trh_point_fft_dev for g_lagrange.
+ * `prefix` is a NUL-terminated string of 0 - 128 bytes (longer: TRH_EINVAL).  Field elements are 4 x u64 Montgomery, points 64-byte affine
+ * PODs (the identity all zero), both 16-byte aligned on the device.  The *_dev entries are asynchronous on `stream` and ordered behind the
+ * context's previous call like the others; n = 0 succeeds and writes nothing; curve_id is TRH_PALLAS / TRH_VESTA, any other value is refused as
+ * everywhere else (tests/test_gpu_hashtocurve.py and tests/test_hashtocurve_host.py check that for these four).                              */
+/* host side, no device needed (like trh_point_from_bytes): w, u, and any single point; msg may be NULL when msg_len = 0 */
+int trh_hash_to_curve(int curve_id, const char* prefix, const uint8_t* msg, size_t msg_len, uint64_t out_xy[8]);
+/* hash_to_field alone: the message of element i is tag || le32(first + i), i < n, first + n <= 2^32 (beyond: TRH_EINVAL);
+ * u_dev: n x 2 elements, u0 then u1 of each message */
+int trh_hash_to_field_indexed_dev(int curve_id, const char* prefix, uint8_t tag, uint32_t first, size_t n, void* u_dev, void* stream);
+/* out[i] = iso_map(sum over j < per_point of swu(u[i * per_point + j])), per_point 1 (RFC 9380's map_to_curve, encode_to_curve's second half)
+ * or 2 (hash_to_curve's); u_dev: n x per_point fully reduced elements; u1 = -u0 gives the identity.  Every element costs the same fixed
+ * instruction sequence, u = 0 and u^2 = -1 / Z included.                                                                                   */
+int trh_map_to_curve_dev(int curve_id, const void* u_dev, size_t n, int per_point, void* xy_dev, void* stream);
+/* the two above back to back over scratch memory of the context: xy[i] = hash(prefix)(tag || le32(first + i)) -- g[first .. first + n) of
+ * Params::new for tag 0 */
+int trh_hash_to_curve_indexed_dev(int curve_id, const char* prefix, uint8_t tag, uint32_t first, size_t n, void* xy_dev, void* stream);
+
 /* ---- element-wise field / group ops on device memory (parity tests of the device arithmetic;
  *      op: 0 add, 1 sub, 2 mul, 3 sqr, 4 neg, 5 inv, 6 to_mont, 7 from_mont) ------------------ */
 int trh_field_op_dev(int field, int op, const void* a_dev, const void* b_dev, void* out_dev, size_t n, void* stream);

@@ -239,6 +239,32 @@ public:
         }
         return p;
     }
+    // Params::new(k): g[i] = hash_to_curve("Halo2-Parameters")(00 || le32(i)) on the device, g_lagrange = n^-1 * best_fft(g, omega^-1) by the
+    // point FFT, w and u (messages 01 and 02) from the host entry; then as the first constructor
+    static Params create(Curve c, uint32_t k, bool fixed_base_tables = true) {
+        require(k <= 24, "Params::create: k <= 24 (the point FFT's range)");
+        static const char prefix[] = "Halo2-Parameters";
+        const size_t n = (size_t)1 << k;
+        std::vector<Affine> g(n), gl(n);
+        {
+            DeviceBuffer pts(n * sizeof(Affine));
+            check(trh_hash_to_curve_indexed_dev((int)c, prefix, 0, 0, n, pts.data(), nullptr), "hash_to_curve_indexed_dev");
+            pts.download(g.data(), n * sizeof(Affine));
+            trh_domain_t d = nullptr;
+            check(trh_domain_create((int)scalar_field(c), 2, k, &d), "domain_create");
+            Limbs omega_inv, n_inv;
+            const int rc = trh_domain_constant(d, 1, omega_inv.data()) | trh_domain_constant(d, 4, n_inv.data());
+            trh_domain_destroy(d);
+            check(rc, "domain_constant");
+            check(trh_point_fft_dev((int)c, pts.data(), k, omega_inv.data(), n_inv.data(), nullptr), "point_fft_dev");
+            pts.download(gl.data(), n * sizeof(Affine));
+        }
+        Affine w, u;
+        const uint8_t m1 = 1, m2 = 2;
+        check(trh_hash_to_curve((int)c, prefix, &m1, 1, (uint64_t*)&w), "hash_to_curve");
+        check(trh_hash_to_curve((int)c, prefix, &m2, 1, (uint64_t*)&u), "hash_to_curve");
+        return Params(c, k, std::move(g), std::move(gl), w, u, fixed_base_tables);
+    }
     std::vector<uint8_t> write() const {
         std::vector<uint8_t> out{(uint8_t)k, (uint8_t)(k >> 8), (uint8_t)(k >> 16), (uint8_t)(k >> 24)};
         for (const Bases* b : {&g_, &g_lagrange_}) { const auto e = b->download_compressed(0, n); out.insert(out.end(), e.begin(), e.end()); }

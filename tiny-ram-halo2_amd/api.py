@@ -206,6 +206,10 @@ _SIGNATURES = {
     "trh_perm_mapping": ([_vp, ctypes.c_uint32, ctypes.c_uint32, _vp], ctypes.c_int),
     "trh_perm_sigma_dev": ([_vp, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp], ctypes.c_int),
     "trh_perm_check_dev": ([_vp, ctypes.c_int, ctypes.POINTER(_vp), _u64p, _u64p, _vp], ctypes.c_int),
+    "trh_hash_to_curve": ([ctypes.c_int, ctypes.c_char_p, _vp, ctypes.c_size_t, _u64p], ctypes.c_int),
+    "trh_hash_to_field_indexed_dev": ([ctypes.c_int, ctypes.c_char_p, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_size_t, _vp, _vp], ctypes.c_int),
+    "trh_map_to_curve_dev": ([ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp], ctypes.c_int),
+    "trh_hash_to_curve_indexed_dev": ([ctypes.c_int, ctypes.c_char_p, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_size_t, _vp, _vp], ctypes.c_int),
     "trh_set_timing": ([ctypes.c_int], ctypes.c_int),
     "trh_last_timing": ([ctypes.POINTER(Timing)], ctypes.c_int),
 }
@@ -575,6 +579,42 @@ def point_from_bytes(curve: str, data: bytes) -> np.ndarray:
     out = np.zeros(8, dtype=np.uint64)
     _check(lib().trh_point_from_bytes(CURVE_ID[curve], ctypes.c_char_p(bytes(data)), _p(out)))
     return out
+
+
+# ---------------------------------------------------------------------------------------
+# hash_to_curve (Params::new): csrc/blake2b.h, csrc/hashtocurve.h, csrc/hashtocurve.hip
+# ---------------------------------------------------------------------------------------
+HALO2_PARAMS_PREFIX = "Halo2-Parameters"
+
+
+def _prefix(prefix) -> bytes:
+    """the NUL-terminated string the C ABI takes; the library itself refuses more than 128 bytes"""
+    b = prefix.encode() if isinstance(prefix, str) else bytes(prefix)
+    assert b"\0" not in b, "the prefix is a C string"
+    return b
+
+
+def hash_to_curve(curve: str, prefix, msg: bytes) -> np.ndarray:
+    """pasta_curves `C::hash_to_curve(prefix)(msg)` for one message -> the 8-limb affine POD; host-side, no device needed"""
+    msg = bytes(msg)
+    out = np.zeros(8, dtype=np.uint64)
+    _check(lib().trh_hash_to_curve(CURVE_ID[curve], _prefix(prefix), ctypes.c_char_p(msg) if msg else None, len(msg), _p(out)))
+    return out
+
+
+def hash_to_field_indexed_dev(curve: str, prefix, tag: int, first: int, n: int, u_dev, stream=None) -> None:
+    """u_dev[i] = the two base-field elements of the message tag || le32(first + i), i < n: (n, 2, 4) limbs on the device"""
+    _check(lib().trh_hash_to_field_indexed_dev(CURVE_ID[curve], _prefix(prefix), tag, first, n, _devptr(u_dev), stream))
+
+
+def map_to_curve_dev(curve: str, u_dev, n: int, per_point: int, xy_dev, stream=None) -> None:
+    """xy_dev[i] = iso_map(sum of swu(u_dev[i * per_point + j])), per_point 1 or 2: (n, 8) affine PODs on the device"""
+    _check(lib().trh_map_to_curve_dev(CURVE_ID[curve], _devptr(u_dev), n, per_point, _devptr(xy_dev), stream))
+
+
+def hash_to_curve_indexed_dev(curve: str, prefix, tag: int, first: int, n: int, xy_dev, stream=None) -> None:
+    """xy_dev[i] = hash_to_curve(prefix)(tag || le32(first + i)), i < n -- g[first .. first + n) of Params::new for tag 0"""
+    _check(lib().trh_hash_to_curve_indexed_dev(CURVE_ID[curve], _prefix(prefix), tag, first, n, _devptr(xy_dev), stream))
 
 
 # ---------------------------------------------------------------------------------------

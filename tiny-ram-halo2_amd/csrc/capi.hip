@@ -222,6 +222,7 @@ static void destroy_ctx(Ctx* c) {
             lookup_release();
             ntt_release_tables();
             encoding_release();
+            hashtocurve_release();
             for (DevBuf& d : c->ipa) d.release();
             c->io.release();
             stage_release(*c);

@@ -208,6 +208,7 @@ struct Ctx {
     DevBuf scan, scan2;  // prefix-product block totals / batch-inversion running products
     DevBuf sqrt_tab[2];     // fieldsqrt.h's table per field (encoding.hip; uploaded at first use, kept like the twiddle tables)
     DevBuf enc_first_bad;   // one word: the smallest invalid index of the last decompression
+    DevBuf h2c_u;           // hashtocurve.hip: the field elements between the fused entry's hash and map kernels (one chunk of points)
     DevBuf ipa[11];  // vectors of the IPA prover (b, s', p', weights, round scalars, g‖w‖u and its lazy copy, the second halves of the p' / b ping-pong pairs,
                      // the generator fold's buckets and bucket lists -- ipafold.hip), kept across proofs
     DevBuf factors;  // ring of 16 small factor tables for the scale kernels
@@ -374,6 +375,10 @@ void lookup_release();
 int points_decompress_device(int curve, const void* bytes_dev, void* xy_dev, void* ok_dev, size_t n, hipStream_t s, u64* first_bad);
 int points_compress_device(int curve, const void* xy_dev, void* bytes_dev, size_t n, hipStream_t s);
 void encoding_release();
+// the context's copy of fieldsqrt.h's SqrtTable<F> for field id 0 (Fp) / 1 (Fq), uploaded at first use
+int sqrt_table_device(int field_id, const void** out);
+// hashtocurve.hip
+void hashtocurve_release();
 
 }  // namespace trh
 

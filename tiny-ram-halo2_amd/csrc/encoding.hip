@@ -136,6 +136,18 @@ int points_compress_device(int curve, const void* xy_dev, void* bytes_dev, size_
     TRH_HIP_TRY(hipGetLastError());
     return TRH_OK;
 }
+int sqrt_table_device(int field_id, const void** out) {
+    if (field_id == FpParams::ID) {
+        const SqrtTable<FpParams>* t = nullptr;
+        TRH_TRY(sqrt_table_dev<FpParams>(&t));
+        *out = t;
+    } else {
+        const SqrtTable<FqParams>* t = nullptr;
+        TRH_TRY(sqrt_table_dev<FqParams>(&t));
+        *out = t;
+    }
+    return TRH_OK;
+}
 void encoding_release() {
     Ctx& c = ctx();
     c.sqrt_tab[0].release(); c.sqrt_tab[1].release(); c.enc_first_bad.release();

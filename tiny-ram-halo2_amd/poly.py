@@ -359,11 +359,25 @@ class Params:
         fileobj.write(self._g.download_compressed(self.n, 1))
         fileobj.write(api.point_to_bytes(self.curve, np.concatenate([u, one])))
 
+    @classmethod
+    def new(cls, curve: str, k: int, precompute: bool = True, device="cuda:0") -> "Params":
+        """Params::new(k) (halo2_proofs 0.2.0 poly/commitment.rs): g[i] = hash_to_curve("Halo2-Parameters")(00 || le32(i)) on the device
+        (api.hash_to_curve_indexed_dev), g_lagrange from g by the point FFT, w and u -- messages 01 and 02 -- from the host entry.  The two
+        sets then pass through host memory once, into the ordinary constructor."""
+        import torch
+        n = 1 << k
+        g_dev = torch.empty((n, 8), dtype=torch.int64, device=device)
+        api.hash_to_curve_indexed_dev(curve, api.HALO2_PARAMS_PREFIX, 0, 0, n, g_dev, stream=_stream(g_dev))
+        gl_dev = cls.g_lagrange_from_g(curve, k, g_dev)
+        w = api.hash_to_curve(curve, api.HALO2_PARAMS_PREFIX, b"\x01")
+        u = api.hash_to_curve(curve, api.HALO2_PARAMS_PREFIX, b"\x02")
+        return cls(curve, k, g_dev.cpu().numpy().view(np.uint64), gl_dev.cpu().numpy().view(np.uint64), w, u, precompute=precompute)
+
     @staticmethod
     def g_lagrange_from_g(curve: str, k: int, g_dev):
         """The heavy step of `Params::new(k)`: g_lagrange = batch_normalize(n^-1 * best_fft(g, omega^-1, k)) with
         best_fft over curve points.  g_dev: device tensor (n, 8) of affine generators; returns a new tensor.
-        (The hash-to-curve derivation of g itself stays on the host.)"""
+        (The hash-to-curve derivation of g itself runs on the device too: Params.new, api.hash_to_curve_indexed_dev.)"""
         sf = api.SCALAR_FIELD[curve]
         m = _MODULUS[sf]
         omega = _ROOT_OF_UNITY[sf]

@@ -37,25 +37,31 @@ def collect(count_instructions=True):
                         counts[cur_fn] = 0
                     elif cur_fn and re.match(r"^\s+[a-z_0-9]+(\s|$)", line) and not line.strip().startswith("s_code_end"):
                         counts[cur_fn] += 1
+                # one block of the notes per kernel; the order of its keys is the YAML emitter's (alphabetical: .group_segment_fixed_size comes
+                # before .name), so a block ends where a key repeats or the notes end -- not at .name
+                def emit(cur):
+                    if not all(k in cur for k in ("short", "vgpr_count", "sgpr_count", "private_segment_fixed_size", "group_segment_fixed_size")):
+                        return
+                    prev = out.get(cur["short"])
+                    ent = {"vgpr": cur["vgpr_count"], "sgpr": cur["sgpr_count"], "scratch": cur["private_segment_fixed_size"], "lds": cur["group_segment_fixed_size"],
+                           "isa_instructions": counts.get(cur["mangled"].replace(".kd", ""), 0)}
+                    if prev is None or ent["vgpr"] > prev["vgpr"]:
+                        out[cur["short"]] = ent  # template instances that share a short name: the largest
                 cur = {}
                 for line in notes.splitlines():
-                    m = re.match(r"\s+\.(name|vgpr_count|sgpr_count|private_segment_fixed_size|group_segment_fixed_size):\s+(\S+)", line)
+                    m = re.match(r"    \.(name|vgpr_count|sgpr_count|private_segment_fixed_size|group_segment_fixed_size):\s+(\S+)", line)
                     if not m:
                         continue
                     key, val = m.group(1), m.group(2)
+                    if key in cur:
+                        emit(cur)
+                        cur = {}
                     if key == "name":
-                        cur = {"mangled": val}
-                        dem = subprocess.run(["c++filt", val], capture_output=True, text=True).stdout.strip()
-                        cur["short"] = short(dem)
+                        cur["name"] = cur["mangled"] = val
+                        cur["short"] = short(subprocess.run(["c++filt", val], capture_output=True, text=True).stdout.strip())
                     else:
                         cur[key] = int(val)
-                    if all(k in cur for k in ("short", "vgpr_count", "sgpr_count", "private_segment_fixed_size", "group_segment_fixed_size")):
-                        prev = out.get(cur["short"])
-                        ent = {"vgpr": cur["vgpr_count"], "sgpr": cur["sgpr_count"], "scratch": cur["private_segment_fixed_size"], "lds": cur["group_segment_fixed_size"],
-                               "isa_instructions": counts.get(cur["mangled"].replace(".kd", ""), 0)}
-                        if prev is None or ent["vgpr"] > prev["vgpr"]:
-                            out[cur["short"]] = ent  # template instances that share a short name: the largest
-                        cur = {}
+                emit(cur)
     return out
 
 
