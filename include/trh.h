@@ -435,6 +435,33 @@ int trh_expr_eval_dev(trh_expr_t e, const void* const* columns_dev, void* const*
  * Rotation(r) reads row (q + r) mod 2^block_log of the same block */
 int trh_expr_eval_blocks_dev(trh_expr_t e, const void* const* columns_dev, void* const* outputs_dev, uint32_t block_log, uint32_t n_blocks, void* stream);
 
+/* ---- MockProver::verify on resident columns (halo2_proofs 0.2.0 dev.rs): "which gate, which row, which lookup" for a witness that is
+ *      already in device memory.  The gate part and the lookup part are below; the permutation part is trh_perm_check_dev.  Columns are plain
+ *      values: cell poisoning and CellNotAssigned (region bookkeeping of the Rust host) are not modelled.
+ * Neither entry takes a stream: the verdict is returned in host memory, so they synchronise in any case.  Their work is ordered behind the
+ * context's previous call, whatever stream that call used, and is complete on return.  Data written OUTSIDE the library on a non-blocking
+ * stream is the caller's to synchronise before the call.
+ * Results: n_bad = the number of bad rows, first_bad_row = the smallest of them, usable_rows when there is none.  The bitmap (device memory,
+ * 8-byte aligned, may be NULL) holds one bit per row, bit r % 64 of u64 word r / 64, set for a bad row; every word is written, zeros
+ * included, so the caller never clears it; bits of rows at or beyond usable_rows are 0.
+ * trh_expr_check_dev runs a compiled program exactly as trh_expr_eval_dev does with rot_step = 1 -- a query reads
+ * column[(row + rotation) mod 2^log_n], so a rotation at the last usable row reads the blinding rows, as upstream -- and tests every output
+ * (STORE_TOP a / STORE_ACC a: one gate polynomial each) against zero on rows [0, usable_rows) instead of storing it: nothing the size of a
+ * column is written.  n_bad / first_bad_row: n_outputs entries; bitmap: n_outputs x W words, output a from word a * W, W = max(1, 2^log_n / 64).
+ * TRH_EINVAL: usable_rows of 0 or above 2^log_n, null arrays, and what trh_expr_eval_dev refuses.                                         */
+int trh_expr_check_dev(trh_expr_t e, const void* const* columns_dev, uint32_t log_n, size_t usable_rows, uint64_t* n_bad /* n_outputs */,
+                       uint64_t* first_bad_row /* n_outputs */, void* bad_bitmap_dev_or_null);
+/* trh_lookup_check_dev: input row r < usable_rows is bad when the tuple (inputs[0][r], .., inputs[width - 1][r]) equals no tuple
+ * (tables[0][t], ..) with t < usable_rows -- exact tuple membership as MockProver does it, not the theta compression of the prover.  width is
+ * 1 .. 16; the arrays are host arrays of `width` device pointers, every column has at least usable_rows elements (16-byte aligned, canonical
+ * stored words compared word by word, as in trh_perm_check_dev; typically the outputs of trh_expr_eval_dev over the lookup's input and table
+ * expressions); rows at or beyond usable_rows are never read.  1 <= usable_rows <= 2^30.  One result pair; bitmap: ceil(usable_rows / 64) words.
+ * The table's rows go into an open-addressing set in a block of the device pool (4 bytes x the power of two at or above 2 * usable_rows);
+ * trh_stat("lookup_check_probes") reports the slots the last check on this context visited.  field_id is TRH_FP / TRH_FQ; any other value is
+ * refused as everywhere else (tests/test_gpu_mock.py checks that for this entry).                                                       */
+int trh_lookup_check_dev(int field_id, const void* const* inputs_dev, const void* const* tables_dev, uint32_t width, size_t usable_rows, uint64_t* n_bad,
+                         uint64_t* first_bad_row, void* bad_bitmap_dev_or_null);
+
 /* ---- best_fft over curve points: Params::new's g -> g_lagrange -----------------------------
  * halo2_proofs::arithmetic::best_fft::<C::Curve>(a, omega, log_n): a'[i] = sum_j [omega^(i j)] a[j].
  * points_dev: 2^log_n affine PODs in device memory, transformed in place (natural order in and out)
@@ -580,7 +607,8 @@ int trh_stream_synchronize(void* stream);
  * to 2^21 pairs, equal ranges of about 2^20 above; resident bases: one up to 3 * 2^21 pairs, then 2^21, 2^22 and the rest;
  * "msm_range_tiles": the tiles of the last MSM enqueue on this context that ran as range tiles of at most 2^25 pairs (0 when it did not);
  * "ntt_tableless_passes": of the last transform, the passes after the first that had no inter-pass twiddle table and computed their twiddles
- * per element (1 from 2^26 elements, where the last pass's table would exceed 1.125 GiB; 0 below). */
+ * per element (1 from 2^26 elements, where the last pass's table would exceed 1.125 GiB; 0 below);
+ * "lookup_check_probes": the slots of the set visited by the two kernels (insert, probe) of the last trh_lookup_check_dev on this context. */
 int trh_stat(const char* name, uint64_t* value);
 /* GPU-side timing without HIP headers: events recorded on a stream between the steps (a hipEvent_t each), read afterwards.
  * trh_event_elapsed_ms waits for `end` and returns the device time between the two records. */

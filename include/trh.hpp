@@ -496,28 +496,38 @@ inline Program compile_outputs(Field f, const std::vector<Expr>& exprs) {
 class GateEvaluator {
 public:
     explicit GateEvaluator(Program p, size_t n_outputs = 1) : program(std::move(p)), n_outputs(n_outputs) {
-        check(trh_expr_create((int)program.field, program.insns.data(), program.insns.size(), (const uint64_t*)program.consts.data(), program.consts.size(),
+        trh::check(trh_expr_create((int)program.field, program.insns.data(), program.insns.size(), (const uint64_t*)program.consts.data(), program.consts.size(),
                               program.columns.size(), n_outputs, 0, &e_), "expr_create");
     }
     GateEvaluator(const GateEvaluator&) = delete;
     GateEvaluator& operator=(const GateEvaluator&) = delete;
     ~GateEvaluator() { if (e_) trh_expr_destroy(e_); }
-    void set_challenge(const Limbs& y) { check(trh_expr_set_const(e_, 0, y.data()), "expr_set_const"); }
+    void set_challenge(const Limbs& y) { trh::check(trh_expr_set_const(e_, 0, y.data()), "expr_set_const"); }
     // columns[i]: device pointer of program.columns[i] (2^log_n elements); out_dev: 2^log_n elements
     void eval(const std::vector<const void*>& columns, void* out_dev, uint32_t log_n, uint32_t rot_step, void* stream = nullptr) const {
         require(columns.size() == program.columns.size(), "one device column per program column");
         void* outs[1] = {out_dev};
-        check(trh_expr_eval_dev(e_, columns.data(), outs, log_n, rot_step, stream), "expr_eval");
+        trh::check(trh_expr_eval_dev(e_, columns.data(), outs, log_n, rot_step, stream), "expr_eval");
     }
     // columns in the coset-block layout: n_blocks x 2^block_log rows each, Rotation(r) stays inside its block
     void eval_blocks(const std::vector<const void*>& columns, void* out_dev, uint32_t block_log, uint32_t n_blocks, void* stream = nullptr) const {
         require(columns.size() == program.columns.size(), "one device column per program column");
         void* outs[1] = {out_dev};
-        check(trh_expr_eval_blocks_dev(e_, columns.data(), outs, block_log, n_blocks, stream), "expr_eval_blocks");
+        trh::check(trh_expr_eval_blocks_dev(e_, columns.data(), outs, block_log, n_blocks, stream), "expr_eval_blocks");
     }
     void eval_outputs(const std::vector<const void*>& columns, const std::vector<void*>& outs, uint32_t log_n, uint32_t rot_step, void* stream = nullptr) const {
         require(columns.size() == program.columns.size() && outs.size() == n_outputs, "one device pointer per program column / output");
-        check(trh_expr_eval_dev(e_, columns.data(), outs.data(), log_n, rot_step, stream), "expr_eval");
+        trh::check(trh_expr_eval_dev(e_, columns.data(), outs.data(), log_n, rot_step, stream), "expr_eval");
+    }
+    // the gate part of MockProver::verify: every output (one gate polynomial each) tested against zero on rows [0, usable_rows), nothing stored.
+    // n_bad[a] rows fail output a, the smallest is first_bad_row[a] (usable_rows when none); bitmap_dev (optional): n_outputs x max(1, 2^log_n / 64)
+    // u64 words, one bit per row.  No stream: the verdict comes back to the host, ordered behind the context's previous call (trh.h)
+    struct Check { std::vector<uint64_t> n_bad, first_bad_row; };
+    Check check(const std::vector<const void*>& columns, uint32_t log_n, size_t usable_rows, void* bitmap_dev = nullptr) const {
+        require(columns.size() == program.columns.size(), "one device column per program column");
+        Check c{std::vector<uint64_t>(n_outputs), std::vector<uint64_t>(n_outputs)};
+        trh::check(trh_expr_check_dev(e_, columns.data(), log_n, usable_rows, c.n_bad.data(), c.first_bad_row.data(), bitmap_dev), "expr_check");
+        return c;
     }
     Program program;
     size_t n_outputs;
@@ -701,6 +711,16 @@ inline void lookup_permute(Field f, const void* input_dev, const void* table_dev
 inline void lookup_permute_batch(Field f, const void* inputs_dev, const void* tables_dev, size_t usable_rows, size_t row_stride, size_t batch, void* permuted_inputs_dev,
                                  void* permuted_tables_dev, void* stream = nullptr) {
     check(trh_lookup_permute_batch_dev((int)f, inputs_dev, tables_dev, usable_rows, row_stride, batch, permuted_inputs_dev, permuted_tables_dev, stream), "permute_expression_pair (batch)");
+}
+
+// the lookup part of MockProver::verify: the input rows below usable_rows whose tuple (one element per input column) equals no table row's
+// tuple -- exact membership, not the theta compression.  bitmap_dev (optional): ceil(usable_rows / 64) u64 words, one bit per row.  No stream (trh.h)
+struct LookupCheck { uint64_t n_bad, first_bad_row; };
+inline LookupCheck lookup_check(Field f, const std::vector<const void*>& inputs, const std::vector<const void*>& tables, size_t usable_rows, void* bitmap_dev = nullptr) {
+    require(inputs.size() == tables.size(), "as many input columns as table columns");
+    LookupCheck c{0, 0};
+    check(trh_lookup_check_dev((int)f, inputs.data(), tables.data(), (uint32_t)inputs.size(), usable_rows, &c.n_bad, &c.first_bad_row, bitmap_dev), "lookup_check");
+    return c;
 }
 
 // z[0] = z0, z[i + 1] = z[i] * num(row i) / den(row i): the product columns of the permutation argument

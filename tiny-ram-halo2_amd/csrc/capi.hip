@@ -1380,6 +1380,7 @@ int trh_stat(const char* name, uint64_t* value) {
         return TRH_OK;
     }
     if (strcmp(name, "ipa_generator_collapses") == 0) { *value = ctx().ipa_collapses; return TRH_OK; }
+    if (strcmp(name, "lookup_check_probes") == 0) { *value = ctx().lookup_check_probes; return TRH_OK; }
     set_error("trh_stat: unknown counter '%s'", name);
     return TRH_EINVAL;
 }

@@ -107,15 +107,11 @@ __device__ __forceinline__ Fy<F> ldg_column(const uint4* p) {
     return r;
 }
 
-template <class F>
-__global__ void __launch_bounds__(THREADS) expr_eval_kernel(const DevInsn* __restrict__ prog, u32 n_insn, const uint4* const* __restrict__ ptrs, u32 n_columns,
-                                                            const uint4* __restrict__ consts, u32 log_n, u32 rot_step, u32 n_blocks) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    // rows: one cyclic domain of 2^log_n rows (n_blocks = 0), or n_blocks cosets of 2^log_n rows each -- a rotation stays inside its block
-    const size_t N = (size_t)1 << log_n, total = n_blocks ? (size_t)n_blocks << log_n : N;
-    const size_t gid = (size_t)blockIdx.x * THREADS + threadIdx.x;
-    const size_t row = gid < total ? gid : gid & (N - 1);  // surplus lanes of the last workgroup repeat rows, their stores are masked
-    const bool live = gid < total;
+// The interpreter loop, shared by the two kernels below: what becomes of an output (STORE_TOP / STORE_ACC a) is the sink's business --
+// sink(a, value) is called by every lane of the workgroup at the same instruction (the program is uniform), so it may vote.
+template <class F, class Sink>
+__device__ __forceinline__ void expr_run(unsigned char* smem, const DevInsn* __restrict__ prog, u32 n_insn, const uint4* const* __restrict__ ptrs,
+                                         const uint4* __restrict__ consts, size_t N, u32 rot_step, size_t row, Sink& sink) {
     const size_t row_base = row & ~(N - 1);
     Fy<F> T = fy_zero<F>(), Nx = fy_zero<F>(), ACC = fy_zero<F>();
     for (u32 pc = 0; pc < n_insn; ++pc) {
@@ -158,13 +154,7 @@ __global__ void __launch_bounds__(THREADS) expr_eval_kernel(const DevInsn* __res
             case TRH_EXPR_STORE_TOP:  // out[a][row] = T; pop
             case TRH_EXPR_STORE_ACC: {
                 const Fe<F> v = fy_to_fe(in.op == TRH_EXPR_STORE_ACC ? ACC : T);
-                if (live) {
-                    u32 w[8];
-                    fe_store(v, w);
-                    uint4* o = (uint4*)ptrs[n_columns + in.a] + 2 * row;
-                    o[0] = make_uint4(w[0], w[1], w[2], w[3]);
-                    o[1] = make_uint4(w[4], w[5], w[6], w[7]);
-                }
+                sink(in.a, v);
                 if (in.op == TRH_EXPR_STORE_TOP) {
                     T = Nx;
                     if (in.slot != NO_SLOT) Nx = lds_get<F>(smem, in.slot);
@@ -174,6 +164,57 @@ __global__ void __launch_bounds__(THREADS) expr_eval_kernel(const DevInsn* __res
             default: break;
         }
     }
+}
+
+template <class F>
+__global__ void __launch_bounds__(THREADS) expr_eval_kernel(const DevInsn* __restrict__ prog, u32 n_insn, const uint4* const* __restrict__ ptrs, u32 n_columns,
+                                                            const uint4* __restrict__ consts, u32 log_n, u32 rot_step, u32 n_blocks) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    // rows: one cyclic domain of 2^log_n rows (n_blocks = 0), or n_blocks cosets of 2^log_n rows each -- a rotation stays inside its block
+    const size_t N = (size_t)1 << log_n, total = n_blocks ? (size_t)n_blocks << log_n : N;
+    const size_t gid = (size_t)blockIdx.x * THREADS + threadIdx.x;
+    const size_t row = gid < total ? gid : gid & (N - 1);  // surplus lanes of the last workgroup repeat rows, their stores are masked
+    const bool live = gid < total;
+    auto store = [&](u32 a, const Fe<F>& v) {  // out[a][row] = v
+        if (live) {
+            u32 w[8];
+            fe_store(v, w);
+            uint4* o = (uint4*)ptrs[n_columns + a] + 2 * row;
+            o[0] = make_uint4(w[0], w[1], w[2], w[3]);
+            o[1] = make_uint4(w[4], w[5], w[6], w[7]);
+        }
+    };
+    expr_run<F>(smem, prog, n_insn, ptrs, consts, N, rot_step, row, store);
+}
+
+// MockProver's gate check: the same program over one cyclic domain with rot_step 1, every output tested against zero on the rows below
+// usable_rows instead of being stored.  A wave holds 64 consecutive, 64-aligned rows, so the verdict of an output is one ballot: lane 0
+// writes it as word a * W + gid / 64 of the bitmap (every word, zeros included), and only a wave that saw a bad row adds its count to
+// result[2 a] and lowers result[2 a + 1] to its smallest bad row -- a satisfied witness issues no atomics.
+template <class F>
+__global__ void __launch_bounds__(THREADS) expr_check_kernel(const DevInsn* __restrict__ prog, u32 n_insn, const uint4* const* __restrict__ ptrs,
+                                                             const uint4* __restrict__ consts, u32 log_n, size_t usable_rows,
+                                                             unsigned long long* __restrict__ result, unsigned long long* __restrict__ bitmap, size_t W) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const size_t N = (size_t)1 << log_n;
+    const size_t gid = (size_t)blockIdx.x * THREADS + threadIdx.x;
+    const size_t row = gid & (N - 1);  // lanes beyond the domain (2^log_n < 256) repeat rows and are masked: usable_rows <= 2^log_n
+    const bool live = gid < usable_rows;
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    auto test = [&](u32 a, const Fe<F>& v) {
+        u32 w[8];
+        fe_store(v, w);
+        const bool bad = live && (w[0] | w[1] | w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) != 0;
+        const unsigned long long ballot = __ballot(bad);
+        if (lane0) {
+            if (bitmap && (gid >> 6) < W) bitmap[(size_t)a * W + (gid >> 6)] = ballot;
+            if (ballot) {
+                atomicAdd(result + 2 * (size_t)a, (unsigned long long)__popcll(ballot));
+                atomicMin(result + 2 * (size_t)a + 1, (unsigned long long)(gid + (size_t)(__ffsll((long long)ballot) - 1)));
+            }
+        }
+    };
+    expr_run<F>(smem, prog, n_insn, ptrs, consts, N, 1u, row, test);
 }
 
 // c (canonical Montgomery words, < m) -> 32 c mod m, the same words a column load produces lazily: five modular doublings
@@ -337,6 +378,8 @@ int trh_expr_create(int field, const trh_expr_insn_t* insns, size_t n_insn, cons
     if (!(ctx().attr_done & ATTR_EXPR)) {  // per device
         TRH_HIP_TRY(hipFuncSetAttribute((const void*)expr_eval_kernel<FpParams>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         TRH_HIP_TRY(hipFuncSetAttribute((const void*)expr_eval_kernel<FqParams>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        TRH_HIP_TRY(hipFuncSetAttribute((const void*)expr_check_kernel<FpParams>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        TRH_HIP_TRY(hipFuncSetAttribute((const void*)expr_check_kernel<FqParams>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         ctx().attr_done |= ATTR_EXPR;
     }
     *out = e;
@@ -403,6 +446,47 @@ static int expr_eval(trh_expr* e, const void* const* columns_dev, void* const* o
     });
     TRH_HIP_TRY(hipGetLastError());
     TRH_HIP_TRY(hipStreamSynchronize(s));  // h_ptrs is reused by the next call
+    return TRH_OK;
+}
+
+int trh_expr_check_dev(trh_expr* e, const void* const* columns_dev, uint32_t log_n, size_t usable_rows, uint64_t* n_bad, uint64_t* first_bad_row,
+                       void* bad_bitmap_dev_or_null) {
+    TRH_TRY(require_init());
+    if (!e || !n_bad || !first_bad_row || (e->n_columns && !columns_dev)) { set_error("expr_check: null pointer"); return TRH_EINVAL; }
+    if (log_n > 30) { set_error("expr_check: log_n %u too large", log_n); return TRH_EINVAL; }
+    const size_t N = (size_t)1 << log_n;
+    if (usable_rows == 0 || usable_rows > N) { set_error("expr_check: usable_rows %zu outside 1 .. 2^%u", usable_rows, log_n); return TRH_EINVAL; }
+    if (((uintptr_t)bad_bitmap_dev_or_null & 7) != 0) { set_error("expr_check: the bitmap must be 8-byte aligned"); return TRH_EINVAL; }
+    std::lock_guard<std::mutex> lk(e->mu);
+    for (uint32_t i = 0; i < e->n_columns; ++i) {
+        if (!columns_dev[i]) { set_error("expr_check: column %u is null", i); return TRH_EINVAL; }
+        e->h_ptrs[i] = columns_dev[i];
+    }
+    TRH_ENTER(0);  // the verdict goes to host memory: no stream parameter, the work follows the context's previous call (trh.h)
+    Range range("trh_expr_check_dev");
+    Ctx& c = ctx();
+    const hipStream_t s = nullptr;
+    // the (count, smallest row) pair of every output, in context scratch, initialised on the stream before the launch
+    std::vector<unsigned long long> result(2 * (size_t)e->n_outputs);
+    for (uint32_t a = 0; a < e->n_outputs; ++a) { result[2 * a] = 0; result[2 * a + 1] = ~0ull; }
+    TRH_TRY(c.scan.ensure(result.size() * 8));
+    unsigned long long* d_result = c.scan.as<unsigned long long>();
+    TRH_HIP_TRY(hipMemcpyAsync(d_result, result.data(), result.size() * 8, hipMemcpyHostToDevice, s));
+    if (e->n_columns) TRH_HIP_TRY(hipMemcpyAsync(e->d_ptrs, e->h_ptrs.data(), (size_t)e->n_columns * sizeof(void*), hipMemcpyHostToDevice, s));
+    const unsigned blocks = (unsigned)((N + THREADS - 1) / THREADS);
+    const size_t lds = (size_t)e->lds_slots * THREADS * 36;
+    const size_t W = N >= 64 ? N / 64 : 1;
+    with_field(e->field, [&](auto f) {
+        hipLaunchKernelGGL((expr_check_kernel<decltype(f)>), dim3(blocks), dim3(THREADS), lds, s, (const DevInsn*)e->d_prog, e->n_insn, (const uint4* const*)e->d_ptrs,
+                           (const uint4*)e->d_consts, log_n, usable_rows, d_result, (unsigned long long*)bad_bitmap_dev_or_null, W);
+    });
+    TRH_HIP_TRY(hipGetLastError());
+    TRH_HIP_TRY(hipMemcpyAsync(result.data(), d_result, result.size() * 8, hipMemcpyDeviceToHost, s));
+    TRH_HIP_TRY(hipStreamSynchronize(s));  // h_ptrs is reused by the next call
+    for (uint32_t a = 0; a < e->n_outputs; ++a) {
+        n_bad[a] = result[2 * a];
+        first_bad_row[a] = result[2 * a] ? result[2 * a + 1] : (uint64_t)usable_rows;
+    }
     return TRH_OK;
 }
 

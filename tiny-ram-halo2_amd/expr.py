@@ -302,6 +302,27 @@ class GateEvaluator:
         api._check(api.lib().trh_expr_eval_blocks_dev(self.handle, ptrs, outs, block_log, n_blocks, stream))
         return o4[0] if self.n_outputs == 1 else o4
 
+    def check(self, columns: dict, log_n: int, usable_rows: int, bitmap: bool = False):
+        """The gate part of MockProver::verify (trh_expr_check_dev): the program runs as in eval(..., rot_step=1), and every output is
+        tested against zero on rows [0, usable_rows) instead of being stored.  Returns (n_bad, first_bad_row) -- numpy uint64 arrays with
+        one entry per output, first_bad_row = usable_rows where an output has no bad row -- and, with bitmap=True, a device tensor
+        (n_outputs, max(1, 2^log_n / 64)) of int64 words: bit r % 64 of word r // 64 is set for a bad row r.  Takes no stream: the work is
+        ordered behind the library's previous call on this context and complete on return; columns written by other code on a
+        non-blocking stream are the caller's to synchronise first"""
+        import torch
+        first = next(iter(columns.values()))
+        n = 1 << log_n
+        ptrs = (ctypes.c_void_p * max(1, len(self.program.columns)))()
+        for i, key in enumerate(self.program.columns):
+            t = columns[key]
+            assert t.shape[-2] == n and t.is_contiguous(), key
+            ptrs[i] = t.data_ptr()
+        n_bad = np.zeros(self.n_outputs, dtype=np.uint64)
+        first_bad = np.zeros(self.n_outputs, dtype=np.uint64)
+        words = torch.empty((self.n_outputs, max(1, n // 64)), dtype=torch.int64, device=first.device) if bitmap else None
+        api._check(api.lib().trh_expr_check_dev(self.handle, ptrs, log_n, usable_rows, api._p(n_bad), api._p(first_bad), words.data_ptr() if bitmap else None))
+        return (n_bad, first_bad, words) if bitmap else (n_bad, first_bad)
+
     def __del__(self):
         try:
             if getattr(self, "handle", None):
