@@ -435,6 +435,42 @@ int trh_expr_eval_dev(trh_expr_t e, const void* const* columns_dev, void* const*
  * Rotation(r) reads row (q + r) mod 2^block_log of the same block */
 int trh_expr_eval_blocks_dev(trh_expr_t e, const void* const* columns_dev, void* const* outputs_dev, uint32_t block_log, uint32_t n_blocks, void* stream);
 
+/* ---- the permutation and lookup terms of h(X): plonk/permutation/prover.rs and plonk/lookup/prover.rs `Committed::construct` ----------
+ * What create_proof folds into the quotient's numerator behind the custom gates, over resident extended columns, per row:
+ *   l_active = 1 - (l_last + l_blind), last = Rotation(-(blinding_factors + 1)), X = the row's domain point, acc = acc * y + t for every t:
+ *   permutation (n_sets = ceil(n_perm_columns / chunk_len) sets; nothing when n_perm_columns = 0)
+ *     l0 (1 - z_0);  l_last (z_last^2 - z_last), z_last the last set's column;  l0 (z_s - z_(s-1)(last)) for s = 1 .. n_sets - 1;
+ *     l_active (z_s(+1) prod_j (v_j + beta sigma_j + gamma) - z_s prod_j (v_j + beta delta^j X + gamma)) for s = 0 .. n_sets - 1,
+ *     j over the set's columns, delta^j by the global column index
+ *   every lookup, in order (A, S compressed input / table, A', S' permuted, z the product column)
+ *     l0 (1 - z);  l_last (z^2 - z);  l_active (z(+1) (A' + beta)(S' + gamma) - z (A + beta)(S + gamma));  l0 (A' - S');
+ *     l_active (A' - S')(A' - A'(-1))
+ * The handle holds what depends on the shape only (the tables X is made from, delta^j, the staging of the pointer table).  A call takes
+ * the columns in either layout of the extended domain: n_blocks = 0 is the flat one (2^extended_k rows, Rotation(r) = r * 2^(extended_k - k)
+ * rows, cyclic), n_blocks >= 1 the coset blocks of trh_domain_coeff_to_extended_blocks (n_blocks x 2^k rows, Rotation(r) inside a block).
+ * acc holds the fold so far -- the STORE_ACC output of the gates' program run with the same y, or zeros -- and receives the result
+ * (canonical Montgomery words, bit-exact).  With no column and no lookup acc is left as it is.  Every pointer is device memory, 16-byte
+ * aligned; the arrays themselves are host arrays.  The stream travels in the struct.  Like trh_expr_eval_dev the entry stages its pointer
+ * table in the handle and returns with the stream SYNCHRONISED; calls on one handle are serialised.
+ * TRH_EINVAL: chunk_len = 0, blinding_factors + 2 > 2^k (create); n_blocks above 2^(extended_k - k), a null array whose count is
+ * non-zero, a null column, null acc / l0 / l_blind / l_last, acc equal to any input pointer (a rotated read would see rows already
+ * folded).                                                                                                                       */
+typedef struct trh_quotient* trh_quotient_t;
+int trh_quotient_create(trh_domain_t d, uint32_t n_perm_columns, uint32_t chunk_len, uint32_t n_lookups, uint32_t blinding_factors, trh_quotient_t* out);
+void trh_quotient_destroy(trh_quotient_t q);
+typedef struct trh_quotient_args {
+    const void* const* perm_values;  /* n_perm_columns extended columns, permutation column order */
+    const void* const* perm_sigmas;  /* n_perm_columns */
+    const void* const* perm_z;       /* ceil(n_perm_columns / chunk_len) */
+    const void* const* lookups;      /* n_lookups x 5: A, S, A', S', z */
+    const void *l0, *l_blind, *l_last;
+    uint64_t beta[4], gamma[4], y[4]; /* Montgomery */
+    void* acc;                       /* in / out: the fold so far (the gates' STORE_ACC output, or zeros) */
+    uint32_t n_blocks;               /* 0: flat layout; else coset blocks, 1 .. 2^(extended_k - k) */
+    void* stream;
+} trh_quotient_args_t;
+int trh_quotient_terms_dev(trh_quotient_t q, const trh_quotient_args_t* args);
+
 /* ---- MockProver::verify on resident columns (halo2_proofs 0.2.0 dev.rs): "which gate, which row, which lookup" for a witness that is
  *      already in device memory.  The gate part and the lookup part are below; the permutation part is trh_perm_check_dev.  Columns are plain
  *      values: cell poisoning and CellNotAssigned (region bookkeeping of the Rust host) are not modelled.

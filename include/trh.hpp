@@ -382,6 +382,8 @@ public:
         check(trh_domain_extended_to_coeff_host(d_, (uint64_t*)a.data(), divide_by_vanishing_first ? 1 : 0), "extended_to_coeff_host");
     }
 
+    trh_domain_t handle() const { return d_; }
+
     Field field;
     uint32_t k, extended_k = 0;
     size_t n;
@@ -533,6 +535,40 @@ public:
     size_t n_outputs;
 private:
     trh_expr_t e_ = nullptr;
+};
+
+// ---- the permutation and lookup terms of h(X) (trh_quotient_*): what plonk::create_proof folds into the quotient's numerator behind the custom
+// gates, over resident extended columns in either layout (n_blocks = 0: flat, 2^extended_k rows; else coset blocks of 2^k rows).  acc_dev
+// holds the fold so far -- GateEvaluator's output for the same y, or zeros -- and receives the result.  Returns with the stream synchronised.
+class QuotientTerms {
+public:
+    struct Columns {
+        std::vector<const void*> values, sigmas;  // n_perm_columns each, permutation column order
+        std::vector<const void*> zs;              // ceil(n_perm_columns / chunk_len) product columns
+        std::vector<const void*> lookups;         // n_lookups x 5: A, S, A', S', z
+        const void *l0 = nullptr, *l_blind = nullptr, *l_last = nullptr;
+    };
+    QuotientTerms(const EvaluationDomain& d, uint32_t n_perm_columns, uint32_t chunk_len, uint32_t n_lookups, uint32_t blinding_factors)
+        : n_perm_columns(n_perm_columns), chunk_len(chunk_len), n_lookups(n_lookups) {
+        check(trh_quotient_create(d.handle(), n_perm_columns, chunk_len, n_lookups, blinding_factors, &q_), "quotient_create");
+    }
+    QuotientTerms(const QuotientTerms&) = delete;
+    QuotientTerms& operator=(const QuotientTerms&) = delete;
+    ~QuotientTerms() { if (q_) trh_quotient_destroy(q_); }
+    size_t n_sets() const { return ((size_t)n_perm_columns + chunk_len - 1) / chunk_len; }
+    void eval(void* acc_dev, const Columns& c, const Limbs& beta, const Limbs& gamma, const Limbs& y, uint32_t n_blocks = 0, void* stream = nullptr) const {
+        require(c.values.size() == n_perm_columns && c.sigmas.size() == n_perm_columns && c.zs.size() == n_sets() && c.lookups.size() == 5 * (size_t)n_lookups,
+                "one device column per permutation column, set and lookup column");
+        trh_quotient_args_t a{};
+        a.perm_values = c.values.data(); a.perm_sigmas = c.sigmas.data(); a.perm_z = c.zs.data(); a.lookups = c.lookups.data();
+        a.l0 = c.l0; a.l_blind = c.l_blind; a.l_last = c.l_last;
+        for (int i = 0; i < 4; ++i) { a.beta[i] = beta[i]; a.gamma[i] = gamma[i]; a.y[i] = y[i]; }
+        a.acc = acc_dev; a.n_blocks = n_blocks; a.stream = stream;
+        check(trh_quotient_terms_dev(q_, &a), "quotient_terms");
+    }
+    uint32_t n_perm_columns, chunk_len, n_lookups;
+private:
+    trh_quotient_t q_ = nullptr;
 };
 
 // ---- the prover's random scalars from a ChaCha20 seed (trh_rng_*): `C::Scalar::random(&mut rng)` for whole vectors ------------------

@@ -64,6 +64,14 @@ class IoStats(ctypes.Structure):
                 ("h2d_zero_bytes", ctypes.c_double)]
 
 
+class QuotientArgs(ctypes.Structure):
+    """trh_quotient_args_t"""
+    _fields_ = [("perm_values", ctypes.POINTER(ctypes.c_void_p)), ("perm_sigmas", ctypes.POINTER(ctypes.c_void_p)), ("perm_z", ctypes.POINTER(ctypes.c_void_p)),
+                ("lookups", ctypes.POINTER(ctypes.c_void_p)), ("l0", ctypes.c_void_p), ("l_blind", ctypes.c_void_p), ("l_last", ctypes.c_void_p),
+                ("beta", ctypes.c_uint64 * 4), ("gamma", ctypes.c_uint64 * 4), ("y", ctypes.c_uint64 * 4), ("acc", ctypes.c_void_p),
+                ("n_blocks", ctypes.c_uint32), ("stream", ctypes.c_void_p)]
+
+
 _SIGNATURES = {
     "trh_init": ([ctypes.c_int], ctypes.c_int),
     "trh_shutdown": ([], None),
@@ -153,6 +161,9 @@ _SIGNATURES = {
     "trh_expr_check_dev": ([_vp, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_size_t, _u64p, _u64p, _vp], ctypes.c_int),
     "trh_lookup_check_dev": ([ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_size_t, _u64p, _u64p, _vp],
                              ctypes.c_int),
+    "trh_quotient_create": ([_vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_vp)], ctypes.c_int),
+    "trh_quotient_destroy": ([_vp], None),
+    "trh_quotient_terms_dev": ([_vp, ctypes.POINTER(QuotientArgs)], ctypes.c_int),
     "trh_field_prefix_product_rows_dev": ([ctypes.c_int, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp], ctypes.c_int),
     "trh_field_prefix_sum_dev": ([ctypes.c_int, _vp, _vp, ctypes.c_size_t, _vp], ctypes.c_int),
     "trh_poly_lincomb_dev": ([ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, _u64p, _vp, _vp], ctypes.c_int),

@@ -226,6 +226,12 @@ int pre_block_table(trh_domain* d, uint32_t n_blocks, hipStream_t s, const void*
 }
 
 }  // namespace
+
+// the shape of a handle for the other files of the library (quotient.hip): the struct itself stays private to this file
+void domain_shape(const trh_domain* d, int* field, u32* j, u32* k, u32* extended_k) {
+    *field = d->field; *j = d->j; *k = d->k; *extended_k = d->extended_k;
+}
+
 }  // namespace trh
 
 using namespace trh;

@@ -203,7 +203,7 @@ def _column_loop_two_contexts(params, dom, batches, blinds, ext_buf, D, blocks, 
 
 
 def run(word_bits: int, batch: int = 64, hook=None, device: int = 0, verbose: bool = True, precompute: bool = True, columns: str = "random",
-        keygen: bool = True, extended: str = "blocks", overlap: bool = False, gates_dir: str | None = None) -> dict:
+        keygen: bool = True, extended: str = "blocks", overlap: bool = False, gates_dir: str | None = None, h_args: bool = False) -> dict:
     import torch
 
     from . import multiopen
@@ -487,6 +487,33 @@ def run(word_bits: int, batch: int = 64, hook=None, device: int = 0, verbose: bo
                 hook("h_eval", dict(gates=rgates, resident=rres, log_n=ek, rot_step=1 << (ek - k), y=0x5EED, field=field, real=True), h_real)
             checked += 1
         del rcols, rres, rout, h_real, rev
+    # --- h(X), the permutation and lookup arguments' terms (quotient.QuotientTerms) at the reference's shape: 188 equality-enabled columns in
+    # sets of 4, 31 lookups.  Every argument column is a distinct resident extended column (copies of this batch's, as above); the fold
+    # continues the gate step's accumulator with the same y.  Opt-in, reported beside the other times and outside gpu_ms_total ---
+    args_info = None
+    if h_args:
+        from . import quotient
+        chunk = N_SIGMA // N_PERM_PRODUCTS
+        qt = quotient.QuotientTerms(dom, N_SIGMA, chunk, N_LOOKUPS, BLINDING_ROWS - 1)
+        n_arg = 2 * N_SIGMA + N_PERM_PRODUCTS + 5 * N_LOOKUPS
+        acols = torch.empty((n_arg, ext_rows, 4), dtype=torch.int64, device=dev)
+        for i in range(n_arg):
+            acols[i].copy_(ext_keep[i % nres].reshape(ext_rows, 4))
+        ls = quotient.lagrange_basis_columns(dom, BLINDING_ROWS - 1, D if blocks else None)
+        split = [acols[i] for i in range(n_arg)]
+        a_values, a_sigmas, a_zs = split[:N_SIGMA], split[N_SIGMA:2 * N_SIGMA], split[2 * N_SIGMA:2 * N_SIGMA + N_PERM_PRODUCTS]
+        a_lookups = [split[2 * N_SIGMA + N_PERM_PRODUCTS + 5 * i:2 * N_SIGMA + N_PERM_PRODUCTS + 5 * i + 5] for i in range(N_LOOKUPS)]
+        acc = h_num.reshape(ext_rows, 4).clone()
+        call = lambda: qt.eval(acc, a_values, a_sigmas, a_zs, a_lookups, ls[0], ls[1], ls[2], 0xBE7A, 0x6A33A, 0x5EED, n_blocks=D if blocks else None)  # noqa: E731
+        call()  # untimed first call
+        acc.copy_(h_num.reshape(ext_rows, 4))
+        e0 = ev()
+        call()
+        e1 = ev()
+        torch.cuda.synchronize()
+        args_info = {"ms": round(e0.elapsed_time(e1), 3), "perm_columns": N_SIGMA, "chunk_len": chunk, "lookups": N_LOOKUPS, "columns_read": n_arg + 4,
+                     "bytes_read": (n_arg + 4) * ext_rows * 32}
+        del acols, split, a_values, a_sigmas, a_zs, a_lookups, acc, ls, qt
     del ext_keep, ext_buf, res, h_num
 
     # --- coefficient-basis commits: vanishing random poly, h pieces ---
@@ -626,6 +653,8 @@ def run(word_bits: int, batch: int = 64, hook=None, device: int = 0, verbose: bo
            "scope": "GPU time of the offloaded arithmetic of ONE create_proof incl. the multiopen folds / divisions; witness generation, the transcript and PCIe are not in it",
            "keygen_gpu_ms": keygen_ms, "fixed_base_tables": bool(precompute), "setup_precompute_ms": round(precompute_ms, 3),
            "wall_s_including_host_input_generation": round(wall, 3), "checked_against_oracle": checked, "clock_warmup": warm}
+    if args_info is not None:
+        out["h_args_ms"], out["h_args"] = args_info["ms"], args_info
     if verbose:
         print(json.dumps(out))
     return out
@@ -1052,6 +1081,7 @@ def main():
     repo_golden = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")  # the command line's default, not the package's
     ap.add_argument("--gates-dir", default=repo_golden if os.path.isdir(repo_golden) else None,
                     help="directory with exe_tempvar_gates.json / chip_gates.json: h(X) is then also timed on the reference's gate polynomials")
+    ap.add_argument("--h-args", action="store_true", help="resident mode: also time the permutation and lookup arguments' terms of h(X) (188 columns in sets of 4, 31 lookups)")
     ap.add_argument("--devices", default=None, help="comma-separated device list (a device may repeat): the per-column phase column-sharded over one context + thread per entry")
     a = ap.parse_args()
     if a.devices is not None:
@@ -1060,7 +1090,7 @@ def main():
     if a.mode != "resident":
         run_dropin(a.word_bits, {"dropin": "literal", "dropin-batched": "batched", "dropin-batched-blocks": "batched-blocks"}[a.mode], a.batch, columns=a.columns, max_columns=a.max_columns)
         return
-    run(a.word_bits, a.batch, precompute=not a.no_precompute, columns=a.columns, keygen=not a.no_keygen, extended=a.extended, overlap=a.overlap, gates_dir=a.gates_dir)
+    run(a.word_bits, a.batch, precompute=not a.no_precompute, columns=a.columns, keygen=not a.no_keygen, extended=a.extended, overlap=a.overlap, gates_dir=a.gates_dir, h_args=a.h_args)
 
 
 if __name__ == "__main__":
