@@ -292,3 +292,28 @@ def run_with_options(script: str, env: dict, timeout: int = 600) -> str:
 
 def point_hex(p) -> str:
     return "".join(f"{int(v):016x}" for v in np.asarray(p, dtype=np.uint64).reshape(-1))
+
+
+# ---- a numerator the vanishing polynomial divides: what blocks_to_quotient (device and host forms) is asked to take back to h(X) ------
+def vanishing_multiple(field: str, j: int, k: int, seed: int):
+    """h: (j - 1) 2^k random coefficients (synth.field_elements(seed, .)); h_ext: h on the extended coset zeta * extended_omega^i
+    (zero-pad to 2^extended_k, zeta shift, best_fft: EvaluationDomain::coeff_to_extended on a longer polynomial); num = h_ext * t with
+    t = X^n - 1 on the coset (period 2^(extended_k - k)).  All (., 4) uint64 limb arrays from the oracle.  Returns (h, h_ext, num)."""
+    import cpu_ref
+    import pasta as o
+    from tiny_ram_halo2_amd import synth
+    f = o.FIELDS[field]
+    cd = cpu_ref.EvaluationDomain(field, j, k)
+    n, ek, D = 1 << k, cd.extended_k, j - 1
+    N = 1 << ek
+    h = synth.field_elements(seed, D * n)
+    padded = np.zeros((N, 4), dtype=np.uint64)
+    padded[: D * n] = h
+    zs = [1, cd.c.g_coset, cd.c.g_coset_inv]
+    fac = np.array([f.limbs(zs[i % 3]) for i in range(3)], dtype=np.uint64)
+    padded[: D * n] = cpu_ref.field_op(field, "mul", padded[: D * n], np.tile(fac, (D * n // 3 + 1, 1))[: D * n])
+    h_ext = cpu_ref.best_fft(field, padded, np.array(f.limbs(cd.c.extended_omega), np.uint64), ek, cpu_ref.hardware_threads())
+    # multiply by the inverses' inverses (t_evaluations holds 1 / t)
+    t_vals = np.array([f.limbs(pow(v, -1, f.m)) for v in cd.c.t_evaluations], dtype=np.uint64)
+    num = cpu_ref.field_op(field, "mul", h_ext, np.tile(t_vals, (N // len(t_vals), 1)))
+    return h, h_ext, num

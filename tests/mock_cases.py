@@ -1,5 +1,5 @@
 """Inputs of the lookup check (trh_lookup_check_dev / csrc/tuplehash.h) and their expected verdicts, shared by tests/test_mock_host.py (the
-set built sequentially on the host by tests/native/tuplehash_test) and tests/test_gpu_mock.py (the device kernels): both must answer
+set built sequentially on the host by tests/native/tuplehash_test.cpp) and tests/test_gpu_mock.py (the device kernels): both must answer
 these very inputs alike, and both must stay within the probe cap on them.
 
 An element is four u64 words compared as they are, so the cases write stored words directly: element(v, top) = words (v, 0, 0, top << 32),

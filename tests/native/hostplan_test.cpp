@@ -1,6 +1,7 @@
 // csrc/hostplan.h without a device: the range boundaries msm_host_tiled (capi.hip) cuts an MSM with host scalars at, in both modes
 // (host bases: equal ranges of ceil(n / ceil(n / 2^20)) pairs above 2^21; resident bases: 2^21, 2^22, the rest above 3 * 2^21), and the
-// pass plan of the NTT for every accepted size.  The range counts asserted here are the ones the GPU tests expect from trh_stat
+// pass plan of the NTT for every accepted size and the number of transforms its lazy passes run per launch set (ntt_lazy_chunk: the invariants
+// over log_n 12..27 and the block counts in use, and the literal values tests/test_gpu_domain_chunks.py builds its cases on).  The range counts asserted here are the ones the GPU tests expect from trh_stat
 // "msm_host_ranges" (tests/test_gpu_dropin.py, tests/test_gpu_realsize.py).  Then the launch plan of an MSM on the device (msm_route, msm_plan):
 // the invariants the kernels of msm.hip rely on over a sweep of shapes, the routes at their edges and the geometry of named shapes.
 // Plain C++, run by tests/test_hostcombine.py.
@@ -84,6 +85,39 @@ int main() {
         ntt_plan_passes(25, s, &P, &tlog); expect(P == 3 && s[0] == 9 && s[1] == 8 && s[2] == 8, "2^25 is 9 + 8 + 8", 25, P);
         ntt_plan_passes(26, s, &P, &tlog); expect(P == 3 && s[0] == 9 && s[1] == 9 && s[2] == 8, "2^26 is 9 + 9 + 8", 26, P);
         ntt_plan_passes(27, s, &P, &tlog); expect(P == 3 && s[0] == 9 && s[1] == 9 && s[2] == 9, "2^27 is 9 + 9 + 9", 27, P);
+    }
+
+    // transforms per launch set of the lazy passes (log_n >= 12): the rule ntt_device_t runs by and ntt_prepare sizes the scratch by
+    {
+        const size_t cap = (size_t)2 << 30;
+        const size_t block_counts[] = {0, 1, 3, 5, 8};
+        for (int log_n = 12; log_n <= 27; ++log_n) for (size_t blocks : block_counts) {
+            const size_t fit = cap / ((size_t)72 << log_n), unit = blocks ? blocks : 1;
+            // batches (whole polynomials) below, at and above what fits, and far above
+            const size_t polys[] = {1, 2, 7, fit / unit, fit / unit + 1, 2 * (fit / unit) + 3, 100000};
+            for (size_t p : polys) {
+                if (p == 0) continue;
+                const size_t batch = p * unit, chunk = ntt_lazy_chunk(log_n, blocks, batch);
+                expect(chunk >= 1 && chunk <= batch, "1 <= chunk <= batch", log_n, chunk);
+                if (blocks) expect(chunk % blocks == 0, "whole polynomials per launch set", log_n, chunk);
+                const bool raised = fit < unit;  // (from 2^25 not even one transform's two planes fit: it runs alone)
+                if (raised) expect(chunk == unit, "fewer than one polynomial fits: one polynomial", log_n, chunk);
+                else expect(2 * chunk * ((size_t)36 << log_n) <= cap, "both raw planes within 2 GiB", log_n, chunk);
+                // nothing larger would do: the next whole polynomial is beyond the batch or beyond the scratch
+                if (!raised && chunk + unit <= batch) expect(2 * (chunk + unit) * ((size_t)36 << log_n) > cap, "the largest set that fits", log_n, chunk);
+            }
+        }
+        const size_t big = 1000000 * 120;  // a multiple of 3, 5 and 8
+        expect(ntt_lazy_chunk(12, 0, big) == 7281, "2^12: 7281", 12, ntt_lazy_chunk(12, 0, big));
+        expect(ntt_lazy_chunk(18, 0, big) == 113, "2^18: 113", 18, ntt_lazy_chunk(18, 0, big));
+        expect(ntt_lazy_chunk(21, 0, big) == 14, "2^21: 14", 21, ntt_lazy_chunk(21, 0, big));
+        expect(ntt_lazy_chunk(22, 0, big) == 7, "2^22: 7", 22, ntt_lazy_chunk(22, 0, big));
+        expect(ntt_lazy_chunk(18, 5, big) == 110, "2^18, 5 blocks: 110", 18, ntt_lazy_chunk(18, 5, big));
+        expect(ntt_lazy_chunk(18, 8, big) == 112, "2^18, 8 blocks: 112", 18, ntt_lazy_chunk(18, 8, big));
+        expect(ntt_lazy_chunk(18, 3, big) == 111, "2^18, 3 blocks: 111", 18, ntt_lazy_chunk(18, 3, big));
+        expect(ntt_lazy_chunk(12, 5, big) == 7280, "2^12, 5 blocks: 7280", 12, ntt_lazy_chunk(12, 5, big));
+        expect(ntt_lazy_chunk(22, 8, big) == 8, "2^22, 8 blocks: 7 raised to 8", 22, ntt_lazy_chunk(22, 8, big));
+        expect(ntt_lazy_chunk(22, 8, 24) == 8 && ntt_lazy_chunk(18, 5, 160) == 110 && ntt_lazy_chunk(18, 5, 105) == 105, "capped at the batch", 18, ntt_lazy_chunk(18, 5, 105));
     }
 
     // MSM launch plan: invariants over the sweep

@@ -214,6 +214,81 @@ def test_domain_host_forms_vs_oracle():
     assert (got == np.asarray(want).reshape(-1, 4)[: got.shape[0]]).all()
 
 
+def _group_for(bytes_per_column):
+    """columns per pipeline item of the host forms (csrc/domain.hip group_for): the smallest power of two, at most 64, that makes 32 MiB"""
+    g = 1
+    while g < 64 and g * bytes_per_column < (32 << 20):
+        g <<= 1
+    return g
+
+
+def _group_edges(group, count):
+    """the first and the last column of every pipeline item"""
+    return sorted({i for g0 in range(0, count, group) for i in (g0, min(g0 + group, count) - 1)})
+
+
+@pytest.mark.parametrize("field,j,k,counts,groups", [("fp", 6, 11, (131, 131, 131), (64, 64, 64)), ("fq", 6, 16, (37, 5, 9), (16, 2, 4))])
+def test_domain_host_forms_past_one_group(field, j, k, counts, groups):
+    """lagrange_to_coeff_host / coeff_to_extended_host / coeff_to_extended_blocks_host on more columns than one pipeline item holds: two full
+    groups and a ragged last one, distinct columns.  k = 11: every column against the oracle.  k = 16: the first and the last column of every
+    group against the oracle, every column against the device form of the same entry (one call on the stacked columns)"""
+    import torch
+    dom = poly.EvaluationDomain(field, j, k)
+    cd = cpu_ref.EvaluationDomain(field, j, k, threads=min(cpu_ref.hardware_threads(), 16))
+    n, ek, D = 1 << k, dom.extended_k, j - 1
+    N, stride = 1 << ek, 1 << (ek - k)
+    assert (_group_for(32 << k), _group_for(32 << ek), _group_for(D * (32 << k))) == groups
+    for count, group in zip(counts, groups):
+        assert count > 2 * group and count % group != 0
+    to_dev = lambda cols: torch.from_numpy(np.stack(cols).view(np.int64)).cuda()  # noqa: E731
+    to_host = lambda t: t.cpu().numpy().view(np.uint64)  # noqa: E731
+    every = k == 11
+    orig = [np.ascontiguousarray(synth.field_elements(0x6D00 + 1000 * k + i, n)) for i in range(max(counts))]
+
+    count, group = counts[0], groups[0]
+    cols = [c.copy() for c in orig[:count]]
+    dom.lagrange_to_coeff_host(cols)
+    for i in (range(count) if every else _group_edges(group, count)):
+        assert (cols[i] == cd.lagrange_to_coeff(orig[i])).all(), i
+    if not every:
+        assert (np.stack(cols) == to_host(dom.lagrange_to_coeff(to_dev(orig[:count])))).all()
+
+    count, group = counts[1], groups[1]
+    ext = dom.coeff_to_extended_host(orig[:count])
+    want = {i: np.asarray(cd.coeff_to_extended(orig[i])).reshape(N, 4) for i in (range(count) if every else _group_edges(group, count))}
+    for i, w in want.items():
+        assert ext[i].shape == (N, 4) and (ext[i] == w).all(), i
+    if not every:
+        assert (np.stack(ext) == to_host(dom.coeff_to_extended(to_dev(orig[:count])))).all()
+    del ext
+
+    count, group = counts[2], groups[2]
+    blk = dom.coeff_to_extended_blocks_host(orig[:count], D)
+    for i in (range(count) if every else _group_edges(group, count)):
+        w = want[i] if i in want else np.asarray(cd.coeff_to_extended(orig[i])).reshape(N, 4)
+        for r in range(D):
+            assert (blk[i][r] == w[r::stride]).all(), (i, r)
+    if not every:
+        assert (np.stack(blk) == to_host(dom.coeff_to_extended_blocks(to_dev(orig[:count]), D))).all()
+
+
+@pytest.mark.parametrize("field,k,j", [("fp", 5, 6), ("fq", 11, 6)])
+def test_blocks_to_quotient_host(field, k, j):
+    """trh_domain_blocks_to_quotient_host on a numerator the vanishing polynomial divides (and, without the division, on h's own values): h
+    back coefficient for coefficient, also when the result is written over the numerator (the header allows h_coeff == num_blocks)"""
+    from common import vanishing_multiple
+    dom = poly.EvaluationDomain(field, j, k)
+    D, stride = j - 1, 1 << (dom.extended_k - k)
+    h, h_ext, num = vanishing_multiple(field, j, k, 0x7140 + k)
+    for vals, divide in ((num, True), (h_ext, False)):
+        blocks = np.ascontiguousarray(np.stack([vals[r::stride] for r in range(D)]))
+        keep = blocks.copy()
+        assert (dom.blocks_to_quotient_host(blocks, divide_by_vanishing=divide) == h).all(), divide
+        assert (blocks == keep).all()   # the host form reads its input only
+        api._check(api.lib().trh_domain_blocks_to_quotient_host(dom.handle(), api._p(blocks), api._p(blocks), 1 if divide else 0))
+        assert (blocks.reshape(-1, 4) == h).all(), divide
+
+
 def test_pinned_caller_memory_skips_the_ring():
     """memory from trh_host_alloc / trh_host_register is read and written by the DMA engine directly: same results"""
     field, log_n = "fp", 16

@@ -10,6 +10,7 @@ import torch
 
 import cpu_ref
 import pasta as o
+from common import vanishing_multiple
 from tiny_ram_halo2_amd import api, poly, synth
 
 pytestmark = pytest.mark.gpu
@@ -320,18 +321,8 @@ def test_extended_domain_as_coset_blocks(field, k, j):
             for r in range(nb):
                 assert (g[i, r] == want[wi][r::step]).all(), (nb, i, r)
     # (2) quotient from j - 1 blocks
-    h = synth.field_elements(0x40 + k, D * n)
-    lim = lambda v: np.array(f.limbs(v), np.uint64)  # noqa: E731
-    # h on the extended coset: zero-pad to 2^extended_k, zeta shift, best_fft (EvaluationDomain::coeff_to_extended on a longer polynomial)
-    padded = np.zeros((N, 4), dtype=np.uint64)
-    padded[: D * n] = h
-    zs = [1, cd.c.g_coset, cd.c.g_coset_inv]
-    fac = np.array([f.limbs(zs[i % 3]) for i in range(3)], dtype=np.uint64)
-    padded[: D * n] = cpu_ref.field_op(field, "mul", padded[: D * n], np.tile(fac, (D * n // 3 + 1, 1))[: D * n])
-    h_ext = cpu_ref.best_fft(field, padded, lim(cd.c.extended_omega), ek, cpu_ref.hardware_threads())
-    # numerator = h * t with t = X^n - 1 on the coset (period 2^(extended_k - k)): multiply by the inverses' inverses
-    t_vals = np.array([f.limbs(pow(v, -1, f.m)) for v in cd.c.t_evaluations], dtype=np.uint64)
-    num = cpu_ref.field_op(field, "mul", h_ext, np.tile(t_vals, (N // len(t_vals), 1)))
+    # h (random), h on the extended coset and the numerator h * (X^n - 1) there, all from the oracle
+    h, h_ext, num = vanishing_multiple(field, j, k, 0x40 + k)
     ref = np.asarray(cd.extended_to_coeff(cd.divide_by_vanishing_poly(num.copy()))).reshape(-1, 4)
     assert (ref[: D * n] == h).all()                        # the oracle's own chain returns h
     blocks = np.stack([num[r::step] for r in range(D)])     # the numerator on blocks 0 .. j - 2

@@ -1,7 +1,7 @@
 """CPU tests of the MockProver layer (tiny_ram_halo2_amd/mock.py, trh_expr_check_dev, trh_lookup_check_dev): what needs no device.
 
   * decode_failures / bitmap_rows: bitmaps -> failure records, their order and the max_failures cap (a pure function of host arrays);
-  * csrc/tuplehash.h, the set behind the lookup check, built sequentially by tests/native/tuplehash_test (address + undefined sanitizers)
+  * csrc/tuplehash.h, the set behind the lookup check, built sequentially by tests/native/tuplehash_test.cpp (compiled here, address + undefined sanitizers)
     over the inputs of tests/mock_cases.py -- the inputs tests/test_gpu_mock.py gives the device -- against a Python set of tuples, and the
     slots it visits against the probe cap;
   * without a device both entries fail loudly."""
@@ -17,8 +17,17 @@ import mock_cases as mc
 from tiny_ram_halo2_amd import api, expr, mock
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TUPLEHASH_TEST = os.path.join(ROOT, "tests", "native", "tuplehash_test")
 WIDTHS = (1, 2, 5, 16)
+
+
+@pytest.fixture(scope="module")
+def tuplehash_test(tmp_path_factory):
+    """tests/native/tuplehash_test.cpp compiled once, with the Makefile's flags, outside the tree: the test then needs nothing that a build
+    left under tests/"""
+    exe = str(tmp_path_factory.mktemp("tuplehash") / "tuplehash_test")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           os.path.join(ROOT, "tests", "native", "tuplehash_test.cpp"), "-o", exe])
+    return exe
 
 
 def _words(n_words, rows):
@@ -75,10 +84,9 @@ def _write_case(path, inputs, tables, usable):
 
 
 @pytest.mark.parametrize("width", WIDTHS)
-def test_tuple_set_on_the_host_matches_a_python_set_and_the_probe_cap(width, tmp_path):
+def test_tuple_set_on_the_host_matches_a_python_set_and_the_probe_cap(width, tmp_path, tuplehash_test):
     """every case of mock_cases through the header's own insert / probe code: the verdict equals the Python model's, the program's own
     std::set agrees row by row, the probe total is within the cap, and the sanitizers stay quiet"""
-    assert os.path.exists(TUPLEHASH_TEST), "tests/native/tuplehash_test is missing: run `make`"
     cases, files = [], []
     for kind in mc.TABLES:
         for usable in mc.sizes(kind):
@@ -88,7 +96,7 @@ def test_tuple_set_on_the_host_matches_a_python_set_and_the_probe_cap(width, tmp
                 _write_case(path, inputs, tables, usable)
                 cases.append((kind, usable, bad, inputs, tables))
                 files.append(path)
-    r = subprocess.run([TUPLEHASH_TEST] + files, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([tuplehash_test] + files, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [json.loads(line) for line in r.stdout.splitlines()]
     assert len(lines) == len(cases)

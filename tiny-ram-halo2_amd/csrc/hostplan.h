@@ -1,6 +1,6 @@
 // Host-side shape decisions of the two headline operations, free of HIP types so that a plain C++ test can check them
 // (tests/native/hostplan_test.cpp): where msm_host_tiled (capi.hip) cuts an MSM with host scalars into ranges, how
-// ntt.hip splits a transform into passes, and the launch plan of an MSM on the device (msm.hip: route, Pippenger geometry,
+// ntt.hip splits a transform into passes and a batch into launch sets, and the launch plan of an MSM on the device (msm.hip: route, Pippenger geometry,
 // scratch layout) as a pure function of its shape.
 #pragma once
 #include <cstddef>
@@ -48,6 +48,20 @@ inline void ntt_plan_passes(int log_n, int* sizes, int* n_passes, int* tile_log)
         for (int p = 0; p < P; ++p) { sizes[p] = (rem + (P - p) - 1) / (P - p); rem -= sizes[p]; }
     }
     *n_passes = P; *tile_log = NTT_TILE_LOG;
+}
+
+constexpr size_t NTT_MAX_SCRATCH = (size_t)2 << 30;  // raw scratch of one call of the lazy passes at most
+constexpr size_t NTT_RAW_BYTES = 36;                  // a raw nine-limb element; the passes alternate between two such planes per transform
+
+// transforms per launch set of the lazy passes (ntt_device_t runs by it, ntt_prepare sizes the scratch by it): what fits 2 GiB of raw
+// scratch at 72 B per element, at least one; with coset blocks (blocks != 0: the kernel takes the block as index % blocks inside a
+// launch) whole polynomials only -- a multiple of `blocks`, and `blocks` where fewer would fit; never more than the batch
+inline size_t ntt_lazy_chunk(int log_n, size_t blocks, size_t batch) {
+    size_t chunk = NTT_MAX_SCRATCH / (((size_t)1 << log_n) * 2 * NTT_RAW_BYTES);
+    if (chunk < 1) chunk = 1;
+    if (blocks) chunk = chunk < blocks ? blocks : chunk - chunk % blocks;
+    if (chunk > batch) chunk = batch;
+    return chunk;
 }
 
 // ---------------------------------------------------------------------------------------

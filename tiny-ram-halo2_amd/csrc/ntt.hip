@@ -694,11 +694,7 @@ int ntt_device_t(void* a_dev, uint32_t log_n, const u64 omega[4], size_t batch, 
     if (scale && !(all_lazy && t->scaled)) { set_error("ntt: this size cannot take a factor in its tables (ntt_can_fold_scale)"); return TRH_EINVAL; }
     if (all_lazy) {
         // signed-domain passes: caller's words -> raw nine-limb scratch -> ... -> caller's words (canonical)
-        const size_t max_tmp = (size_t)2 << 30;
-        size_t chunk = max_tmp / (N * 72);
-        if (chunk < 1) chunk = 1;
-        if (fu && fu->blocks) chunk = chunk < fu->blocks ? fu->blocks : chunk - chunk % fu->blocks;  // whole polynomials per launch: block = index % blocks
-        if (chunk > batch) chunk = batch;
+        const size_t chunk = hostplan::ntt_lazy_chunk((int)log_n, fu ? fu->blocks : 0, batch);  // whole polynomials per launch: block = index % blocks
         TRH_TRY(c.ntt_tmp.ensure(2 * chunk * N * 36));
         char* raw[2] = {(char*)c.ntt_tmp.p, (char*)c.ntt_tmp.p + chunk * N * 36};
         for (int p = 1; p < P; ++p) c.ntt_tableless_passes += t->direct[p].p == nullptr;
@@ -823,11 +819,7 @@ int ntt_prepare(int field, uint32_t log_n, const u64 omega[4], const u64* scale,
     plan_passes((int)log_n, sizes, &P, &tlog);
     const size_t N = (size_t)1 << log_n;
     if (ntt_can_fuse(log_n) && P >= 2) {  // the signed passes' raw scratch: the chunking of ntt_device_t
-        size_t chunk = ((size_t)2 << 30) / (N * 72);
-        if (chunk < 1) chunk = 1;
-        if (blocks) chunk = chunk < blocks ? blocks : chunk - chunk % blocks;
-        if (chunk > batch) chunk = batch;
-        return c.ntt_tmp.ensure(2 * chunk * N * 36);
+        return c.ntt_tmp.ensure(2 * hostplan::ntt_lazy_chunk((int)log_n, blocks, batch) * N * 36);
     }
     if (P > 1) {
         size_t chunk = ((size_t)2 << 30) / (N * 32);
