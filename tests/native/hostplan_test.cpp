@@ -189,6 +189,47 @@ int main() {
             expect(p.use_bin_shape == r.use_bin, "named shape: LDS bin sort", r.n, r.batch);
         }
     }
+    // collision shapes: the plan numbers tests/msm_collision_cases.py (SHAPES) builds the cases of tests/test_gpu_msm_collisions.py on -- which
+    // segment offset a bucket starts at, how many pieces the combine adds with how many lanes, which buckets share a reduce slice, which
+    // slices meet in a workgroup's tree.  A plan change that fails here means those cases no longer aim where their names say.
+    {
+        const struct { size_t n_lo, n_hi, batch; int fc, ov, c; unsigned seg_len0, nbk, tpw, slice, rblocks, lanes; } rows[] = {
+            {64, 2400, 1, 0, 8, 8, 16, 128, 128, 1, 1, 1},              // "c8": one lane per bucket (fewer than three pieces)
+            {64, 2400, 2, 0, 8, 8, 16, 128, 128, 1, 1, 1},
+            {1024, 2048, 1, 0, 3, 3, 16, 4, 4, 1, 1, 4},                // "c3": 16 / 32 pieces per bucket, four lanes
+            {512, 512, 1, 0, 15, 15, 16, 16384, 2048, 8, 8, 1},         // "c15": slices of 8, running sums
+            {512, 512, 1, 0, 17, 17, 16, 65536, 4096, 16, 16, 1},       // "c17", "c18": slices of 16 and 32, the live-bucket branch
+            {512, 512, 1, 0, 18, 18, 16, 131072, 4096, 32, 16, 1},
+            {512, 512, 1, 16, 0, 16, 16, 32768, 16384, 2, 64, 1},       // "table16": one bucket set, slices of 2
+            {512, 6143, 8, 0, 0, 8, 16, 128, 128, 1, 1, 1},             // eight items: the plan's own c = 8, adaptive segments
+        };
+        for (const auto& r : rows) for (size_t n : {r.n_lo, (r.n_lo + r.n_hi) / 2, r.n_hi}) {
+            const MsmShape sh{n, r.batch, r.fc, r.ov, 4};
+            const MsmPlan p = msm_plan(sh);
+            expect(msm_route(sh, false, false) == MSM_ROUTE_PIPELINE, "collision shape: the pipeline", n, r.c);
+            expect(p.c == r.c && p.Ws == (r.fc ? 1 : num_windows(r.c)) && p.nbk == r.nbk, "collision shape: window bits, bucket sets, buckets", n, r.c);
+            expect(p.seg_len0 == r.seg_len0, "collision shape: segments of 16 entries", n, p.seg_len0);
+            expect(p.tpw == r.tpw && p.slice == r.slice && p.rblocks == r.rblocks, "collision shape: reduce geometry", n, p.slice);
+            // The next two rules are COPIES: the lanes per bucket are decided in stage_accumulate and the quad / thread form of the reduction in
+            // stage_reduce (msm.hip), not by a function of hostplan.h.  What is asserted here is that the plan numbers those rules read give the
+            // form the cases are built for; a change of the rules themselves in msm.hip must be carried over to these lines by hand.
+            const size_t pieces = p.ns / ((size_t)p.nbk * p.seg_len0);  // stage_accumulate: four lanes per bucket from three expected pieces
+            expect((pieces >= 3 && p.nbk >= 4 ? 4u : 1u) == r.lanes, "collision shape: lanes per bucket of the combine", n, pieces);
+            expect(p.adaptive == (r.batch >= 8), "collision shape: adaptive segments for eight items", n, r.batch);
+            if (p.adaptive) expect(msm_segments_counted(p, n, (uint32_t)n).seg_len == 16, "collision shape: counted segments of 16", n, r.batch);
+            if (r.fc) {  // the quad reduction takes this shape: 16384 quads of 2 buckets, 256 workgroups of 64 quads
+                expect((size_t)p.tpw * 4 * p.Ws <= ((size_t)1 << 16) && p.nbk % p.tpw == 0 && p.tpw >= 64, "collision shape: the table shape passes the quad gate at tpw", n, p.tpw);
+            } else expect(p.Ws > 8, "collision shape: more than 8 bucket sets keep the thread-per-slice reduction", n, p.Ws);
+        }
+        // 2048 entries in one bucket at c = 3: 128 segments, beyond HEAVY_PIECES
+        expect(msm_plan(MsmShape{2048, 1, 0, 3, 4}).nseg0 == 128 && 128 - 1 > HEAVY_PIECES, "collision shape: a 2048-entry bucket is heavy", 2048, HEAVY_PIECES);
+        // the small kernel's cases
+        expect(msm_route(MsmShape{2, 1, 0, 0, 4}, false, false) == MSM_ROUTE_SMALL && msm_route(MsmShape{400, 2, 0, 0, 4}, false, false) == MSM_ROUTE_SMALL && SMALL_C == 5,
+               "collision shape: one launch, c = 5", 400, SMALL_C);
+        // tests/test_gpu_parity.py test_msm_all_same_base_skewed and its twin under the override
+        expect(msm_route(MsmShape{5000, 1, 0, 0, 4}, false, false) == MSM_ROUTE_SMALL && msm_route(MsmShape{5000, 1, 0, 8, 4}, false, false) == MSM_ROUTE_PIPELINE,
+               "5000 pairs: one launch; the pipeline under a window override", 5000, 8);
+    }
     std::printf(bad ? "hostplan: FAILED (%d)\n" : "hostplan: ok\n", bad);
     return bad ? 1 : 0;
 }

@@ -202,16 +202,37 @@ def test_msm_canonical_scalars_and_offset():
         b.msm(sc, offset=1)  # range exceeds the resident bases
 
 
-def test_msm_all_same_base_skewed():
-    """all scalars small and all bases equal: every pair lands in a handful of buckets"""
+def _all_same_base_skewed():
     curve, n = "pallas", 5000
     f = o.CURVES[curve].scalar
     vals = [(i % 3) for i in range(n)]
     sc = np.array([f.limbs(v) for v in vals], np.uint64)
     g = np.array(o.CURVES[curve].affine_limbs(o.CURVES[curve].generator), np.uint64)
-    bases = np.tile(g, (n, 1))
+    return curve, sc, np.tile(g, (n, 1)), o.CURVES[curve].mul(sum(vals), o.CURVES[curve].generator)
+
+
+def test_msm_all_same_base_skewed():
+    """all scalars small and all bases equal: every pair lands in a handful of buckets.  5000 pairs are ONE launch (msm_small_kernel:
+    buckets 1 and 2 of window 0, about a hundred equal entries per lane)"""
+    curve, sc, bases, want = _all_same_base_skewed()
+    small = api.stat("msm_small_launches")
     got = api.best_multiexp(curve, sc, bases)
-    want = o.CURVES[curve].mul(sum(vals), o.CURVES[curve].generator)
+    assert api.stat("msm_small_launches") == small + 1
+    assert o.CURVES[curve].affine_from_limbs(got[:8]) == want
+
+
+def test_msm_all_same_base_skewed_through_the_pipeline():
+    """the same under a window override, so that the per-window pipeline sees all-equal buckets too: c = 8, two buckets of about 1667 equal
+    entries each in segments of 16 -- every thread of the accumulation doubles once, and a bucket's 105 equal pieces (more than HEAVY_PIECES)
+    are added by a workgroup"""
+    curve, sc, bases, want = _all_same_base_skewed()
+    small = api.stat("msm_small_launches")
+    try:
+        api.set_window_bits(8)
+        got = api.best_multiexp(curve, sc, bases)
+    finally:
+        api.set_window_bits(0)
+    assert api.stat("msm_small_launches") == small
     assert o.CURVES[curve].affine_from_limbs(got[:8]) == want
 
 
