@@ -365,6 +365,20 @@ int trh_product_terms_dev(int field, const trh_product_term_t* terms, const uint
 int trh_field_prefix_product_dev(int field, const void* a_dev, void* out_dev, size_t n, void* stream);
 /* the same for `rows` independent vectors of n elements stored back to back (all product columns of a proof at once) */
 int trh_field_prefix_product_rows_dev(int field, const void* a_dev, void* out_dev, size_t n, size_t rows, void* stream);
+/* chains the product columns of consecutive permutation sets (plonk/permutation/prover.rs Argument::commit starts set s from
+ * z_(s-1)[u], u = the number of usable rows) after trh_field_prefix_product_rows_dev has made every row start from one: with z_in the
+ * rows on entry, row r >= 1 becomes z_in[r][i] * c_r, c_r = prod_{t < r} z_in[t][link]; row 0 stays.  In place, canonical Montgomery
+ * words in and out, bit-exact.  rows <= 1 succeeds and does nothing.  Asynchronous on args->stream (the stream travels in the struct,
+ * as in trh_quotient_args_t), ordered behind the context's previous call; the rows - 1 carries are formed in the context's scratch by
+ * a one-workgroup launch, then one pass multiplies: no host read, no synchronisation.
+ * TRH_EINVAL: an unknown field id, n no power of two, link >= n, a null or misaligned z.                                          */
+typedef struct trh_product_chain_args {
+    void*  z;        /* rows x n stored elements back to back, in place: the output of trh_field_prefix_product_rows_dev */
+    size_t n, rows;  /* n = 2^k elements per row */
+    size_t link;     /* the row index u whose value starts the next set, link < n */
+    void*  stream;
+} trh_product_chain_args_t;
+int trh_product_chain_dev(int field_id, const trh_product_chain_args_t* args);
 /* out[i] = sum_{j < i} a[j], out[0] = 0 */
 int trh_field_prefix_sum_dev(int field, const void* a_dev, void* out_dev, size_t n, void* stream);
 

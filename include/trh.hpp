@@ -808,6 +808,13 @@ inline void grand_products(Field f, uint32_t k, const std::vector<std::vector<tr
     check(trh_stream_synchronize(stream), "grand_products sync");  // nd is released on return
 }
 
+// Argument::commit's link between consecutive permutation sets, in place on the rows x n output of grand_products (trh_product_chain_dev)
+inline void chain_products(Field f, void* z_dev, size_t n, size_t rows, size_t link, void* stream = nullptr) {
+    trh_product_chain_args_t a{};
+    a.z = z_dev; a.n = n; a.rows = rows; a.link = link; a.stream = stream;
+    check(trh_product_chain_dev((int)f, &a), "product_chain");
+}
+
 // arithmetic::kate_division by (X - z) for polynomials of n coefficients.  The powers of z and 1 / z are built once, on the stream
 // the divisions will run on (the constructor takes it: tables built on another stream could still be in flight when divide() reads
 // them); z = 0 (z_inv ignored) divides by X: the quotient is the coefficient list shifted down by one.

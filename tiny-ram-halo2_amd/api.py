@@ -72,6 +72,11 @@ class QuotientArgs(ctypes.Structure):
                 ("n_blocks", ctypes.c_uint32), ("stream", ctypes.c_void_p)]
 
 
+class ProductChainArgs(ctypes.Structure):
+    """trh_product_chain_args_t"""
+    _fields_ = [("z", ctypes.c_void_p), ("n", ctypes.c_size_t), ("rows", ctypes.c_size_t), ("link", ctypes.c_size_t), ("stream", ctypes.c_void_p)]
+
+
 _SIGNATURES = {
     "trh_init": ([ctypes.c_int], ctypes.c_int),
     "trh_shutdown": ([], None),
@@ -165,6 +170,7 @@ _SIGNATURES = {
     "trh_quotient_destroy": ([_vp], None),
     "trh_quotient_terms_dev": ([_vp, ctypes.POINTER(QuotientArgs)], ctypes.c_int),
     "trh_field_prefix_product_rows_dev": ([ctypes.c_int, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp], ctypes.c_int),
+    "trh_product_chain_dev": ([ctypes.c_int, ctypes.POINTER(ProductChainArgs)], ctypes.c_int),
     "trh_field_prefix_sum_dev": ([ctypes.c_int, _vp, _vp, ctypes.c_size_t, _vp], ctypes.c_int),
     "trh_poly_lincomb_dev": ([ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_size_t, _u64p, _vp, _vp], ctypes.c_int),
     "trh_poly_kate_division_dev": ([ctypes.c_int, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, _vp], ctypes.c_int),

@@ -169,6 +169,35 @@ int prefix_scan_t(const void* a, void* out, size_t n, hipStream_t s, size_t rows
     TRH_HIP_TRY(hipGetLastError());
     return TRH_OK;
 }
+// ---- chained product columns (plonk/permutation/prover.rs Argument::commit: z_s[0] = z_(s-1)[u]) ------------------------------
+// carries[r] = prod_{t < r} z[t][link] for r < rows (carries[0] = 1), one workgroup: thread t owns the rows [t * per, (t + 1) * per).
+// It reads the rows as they are on entry and runs BEFORE the pass below rewrites them: a workgroup of that pass that redid the
+// short product itself would race the in-place stores of the others.
+template <class F>
+__global__ void __launch_bounds__(256) chain_carries_kernel(const uint4* __restrict__ z, size_t n, size_t link, u32 rows, uint4* __restrict__ carries) {
+    __shared__ Fe<F> sh[256];
+    const u32 per = (rows + 255u) / 256u;
+    const u32 lo = threadIdx.x * per;
+    Fe<F> p = fe_one<F>();
+    for (u32 k = 0; k < per; ++k)
+        if (lo + k < rows) p = fe_mul(p, load_fe<F>(z + 2 * ((size_t)(lo + k) * n + link)));
+    Fe<F> total;
+    Fe<F> run = block_exclusive_scan<F, OpMul<F>>(sh, p, total);
+    for (u32 k = 0; k < per; ++k) {
+        if (lo + k >= rows) break;
+        store_fe<F>(carries + 2 * (lo + k), run);
+        run = fe_mul(run, load_fe<F>(z + 2 * ((size_t)(lo + k) * n + link)));
+    }
+}
+// z[r][i] <- z[r][i] * carries[r] for r = 1 .. rows - 1: one pass over (rows - 1) * 2^log_n elements, a load, a multiply and a store each
+template <class F>
+__global__ void __launch_bounds__(256) chain_apply_kernel(uint4* __restrict__ z, u32 log_n, size_t total, const uint4* __restrict__ carries) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const size_t e = i + ((size_t)1 << log_n);  // row 0 stays
+        store_fe<F>(z + 2 * e, fe_mul(load_fe<F>(z + 2 * e), load_fe<F>(carries + 2 * (e >> log_n))));
+    }
+}
 // ---- multiopen building blocks (halo2_proofs 0.2.0 poly/multiopen/prover.rs) -----------------------------
 // out[i] = sum_b coeff[b] * polys[b][i]: the x1 / x4 linear combinations of the queried polynomials
 template <class F>
@@ -324,6 +353,36 @@ int trh_field_prefix_product_rows_dev(int field, const void* a_dev, void* out_de
     TRH_ENTER(stream);
     Range range("trh_field_prefix_product_rows_dev");
     return with_field(field, [&](auto f) { return prefix_scan_t<decltype(f), OpMul<decltype(f)>>(a_dev, out_dev, n, (hipStream_t)stream, rows); });
+}
+
+int trh_product_chain_dev(int field_id, const trh_product_chain_args_t* args) {
+    TRH_TRY(require_init());
+    TRH_TRY(check_field(field_id));
+    if (!args) { set_error("product_chain: null pointer"); return TRH_EINVAL; }
+    const size_t n = args->n, rows = args->rows;
+    if (rows <= 1) return TRH_OK;  // nothing to chain
+    if (!args->z) { set_error("product_chain: null pointer"); return TRH_EINVAL; }
+    if (n == 0 || (n & (n - 1)) != 0) { set_error("product_chain: n = %zu is no power of two", n); return TRH_EINVAL; }
+    if (args->link >= n) { set_error("product_chain: link %zu is outside the %zu rows of a column", args->link, n); return TRH_EINVAL; }
+    if (rows > ((size_t)1 << 24) || rows > (((size_t)1 << 40) / n)) { set_error("product_chain: %zu rows of %zu elements are too many", rows, n); return TRH_EINVAL; }
+    if (((uintptr_t)args->z & 15) != 0) { set_error("product_chain: elements must be 16-byte aligned"); return TRH_EINVAL; }
+    TRH_ENTER(args->stream);
+    Range range("trh_product_chain_dev");
+    Ctx& c = ctx();
+    hipStream_t s = (hipStream_t)args->stream;
+    TRH_TRY(c.scan.ensure(rows * 32));
+    u32 log_n = 0;
+    while (((size_t)1 << log_n) < n) ++log_n;
+    const size_t total = (rows - 1) * n;
+    const size_t want = (total + 255) / 256;
+    const unsigned blocks = (unsigned)(want < ((size_t)1 << 20) ? want : (size_t)1 << 20);
+    with_field(field_id, [&](auto f) {
+        typedef decltype(f) F;
+        hipLaunchKernelGGL((chain_carries_kernel<F>), dim3(1), dim3(256), 0, s, (const uint4*)args->z, n, args->link, (u32)rows, c.scan.as<uint4>());
+        hipLaunchKernelGGL((chain_apply_kernel<F>), dim3(blocks), dim3(256), 0, s, (uint4*)args->z, log_n, total, c.scan.as<uint4>());
+    });
+    TRH_HIP_TRY(hipGetLastError());
+    return TRH_OK;
 }
 
 int trh_field_prefix_sum_dev(int field, const void* a_dev, void* out_dev, size_t n, void* stream) {

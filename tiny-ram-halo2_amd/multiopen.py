@@ -168,3 +168,78 @@ def create_proof(params, rng, transcript, queries, polys: dict, blinds: dict, s_
     if s_poly is None:  # the prover's random s(X): n draws (a caller that times the phase hands the host array in)
         s_poly = np.stack([_limbs(sf, rng()) for _ in range(n)])
     return ipa.create_proof_native(params, rng, transcript, p_poly, p_blind, x3, s_poly, rng())
+
+
+# ---------------------------------------------------------------------------------------
+# poly::multiopen::verify_proof -- the mirror of create_proof above (poly/multiopen/verifier.rs, as recalled)
+# ---------------------------------------------------------------------------------------
+def lagrange_interpolate(m: int, points, evals):
+    """coefficients (lowest first) of the polynomial of degree < len(points) through (points[i], evals[i]); the points are distinct"""
+    assert len(points) == len(evals) and len(set(p % m for p in points)) == len(points)
+    out = [0] * len(points)
+    for j, (xj, yj) in enumerate(zip(points, evals)):
+        num, den = [1], 1  # prod_{i != j} (X - x_i) and prod_{i != j} (x_j - x_i)
+        for i, xi in enumerate(points):
+            if i == j:
+                continue
+            num = [((num[t - 1] if t else 0) - xi * (num[t] if t < len(num) else 0)) % m for t in range(len(num) + 1)]
+            den = den * (xj - xi) % m
+        scale = yj * pow(den, -1, m) % m
+        out = [(o + scale * c) % m for o, c in zip(out, num)]
+    return out
+
+
+def construct_intermediate_sets_with_evals(queries):
+    """construct_intermediate_sets on (point, key, eval) queries, as the verifier uses it: -> (commitments, point_sets) with commitments a
+    list of (key, set_index, evals), evals[i] the claimed value at point_sets[set_index][i]"""
+    commitments, point_sets = construct_intermediate_sets([(p, k) for p, k, _ in queries])
+    claimed = {}
+    for p, k, e in queries:
+        claimed.setdefault((k, p), e)
+    return [(k, s, [claimed[(k, p)] for p in point_sets[s]]) for k, s in commitments], point_sets
+
+
+def verify_proof(params, transcript, queries, commitments: dict):
+    """queries: list of (point, key, eval) in the prover's order, canonical ints; commitments[key]: a list of (scalar, point) terms, points
+    as 8-limb affine PODs (a plain commitment is [(1, C)]; h's sum_i x^(n i) h_i rides along as several terms).  Reads what create_proof
+    wrote -- q', the per-set evaluations, then the opening in the order of the oracle's ipa_verify_proof -- from `transcript`
+    (read_point() -> 8-limb POD, read_scalar() -> int, squeeze_challenge_scalar() -> int) and returns the opening's ipa.Guard: the accumulator
+    starts empty.  O(#queries) host integers; the group work is the guard's."""
+    from . import ipa
+    m = _MODULUS[api.SCALAR_FIELD[params.curve]]
+    x1 = transcript.squeeze_challenge_scalar()
+    x2 = transcript.squeeze_challenge_scalar()
+    members, point_sets = construct_intermediate_sets_with_evals(queries)
+    nsets = len(point_sets)
+    q_terms = [[] for _ in range(nsets)]      # q_i = sum_j x1^(len - 1 - j) C_j over the commitments of set i
+    q_eval_sets = [[0] * len(pts) for pts in point_sets]
+    for key, s, evals in members:
+        q_terms[s] = [(c * x1 % m, pt) for c, pt in q_terms[s]] + [(c % m, pt) for c, pt in commitments[key]]
+        q_eval_sets[s] = [(a * x1 + e) % m for a, e in zip(q_eval_sets[s], evals)]
+    q_prime = transcript.read_point()
+    x3 = transcript.squeeze_challenge_scalar()
+    q_evals = [transcript.read_scalar() for _ in range(nsets)]
+    msm_eval = 0
+    for pts, evals, proof_eval in zip(point_sets, q_eval_sets, q_evals):
+        r_eval = 0
+        for c in reversed(lagrange_interpolate(m, pts, evals)):
+            r_eval = (r_eval * x3 + c) % m
+        e = (proof_eval - r_eval) % m
+        for p in pts:
+            e = e * pow((x3 - p) % m, -1, m) % m
+        msm_eval = (msm_eval * x2 + e) % m
+    x4 = transcript.squeeze_challenge_scalar()
+    terms, v = [(1, q_prime)], msm_eval
+    for qt, qe in zip(q_terms, q_evals):
+        terms = [(c * x4 % m, pt) for c, pt in terms] + qt
+        v = (v * x4 + qe) % m
+    s_commitment = transcript.read_point()
+    xi = transcript.squeeze_challenge_scalar()
+    z = transcript.squeeze_challenge_scalar()
+    rounds = []
+    for _ in range(params.k):
+        l_j, r_j = transcript.read_point(), transcript.read_point()
+        rounds.append((l_j, r_j, transcript.squeeze_challenge_scalar()))
+    c = transcript.read_scalar()
+    f = transcript.read_scalar()
+    return ipa.verify_proof(params, terms, v, x3, s_commitment, xi, z, rounds, c, f)

@@ -201,6 +201,21 @@ def grand_products_terms(field: str, k: int, num_rows, den_rows):
     return num
 
 
+def chain_products(field: str, z, link: int, rows: int | None = None):
+    """Links the product columns of consecutive permutation sets in place (trh_product_chain_dev, csrc/scan.hip): z is the (rows, n, 4) output
+    of grand_products_terms, every row starting from one; afterwards row r starts from row r - 1's value at `link` (Argument::commit:
+    z_s[0] = z_(s-1)[u], u = the usable rows).  `rows` limits the chain to the leading rows (the lookup products behind them start from one).
+    No host read: the carries are formed on the device, on the current stream.  Returns z."""
+    import torch
+    assert z.is_contiguous() and z.dim() == 3 and z.shape[2] == 4
+    rows = z.shape[0] if rows is None else rows
+    if not (0 <= rows <= z.shape[0] and 0 <= link < 1 << 63):
+        raise api.TrhError(f"chain_products: rows = {rows}, link = {link}")
+    a = api.ProductChainArgs(z=api._devptr(z), n=z.shape[1], rows=rows, link=link, stream=torch.cuda.current_stream(z.device).cuda_stream)
+    api._check(api.lib().trh_product_chain_dev(api.FIELD_ID[field], ctypes.byref(a)))
+    return z
+
+
 def lookup_product(field: str, k: int, beta: int, gamma: int) -> GrandProduct:
     """columns: ("advice", 0) = compressed input A, 1 = compressed table S, 2 = permuted input A', 3 = permuted table S'"""
     a, s_, ap, sp = (expr.Advice(i, 0) for i in range(4))
