@@ -4,9 +4,14 @@
 // over log_n 12..27 and the block counts in use, and the literal values tests/test_gpu_domain_chunks.py builds its cases on).  The range counts asserted here are the ones the GPU tests expect from trh_stat
 // "msm_host_ranges" (tests/test_gpu_dropin.py, tests/test_gpu_realsize.py).  Then the launch plan of an MSM on the device (msm_route, msm_plan):
 // the invariants the kernels of msm.hip rely on over a sweep of shapes, the routes at their edges and the geometry of named shapes.
+// Then the plan of an IPA opening (ipa_plan): the invariants of every shape the entry accepts (k = 1..26, both set forms, no table and tables of 10..18 bits,
+// the values of option ipa_fold, with and without a window override), the counts tests/test_gpu_realsize.py asserts through trh_stat and the byte
+// size of every scratch buffer at k = 10, 14 and 18 as literals.
 // Plain C++, run by tests/test_hostcombine.py.
 #include <cstdio>
+#include <utility>
 
+#include "../../tiny-ram-halo2_amd/csrc/foldplan.h"
 #include "../../tiny-ram-halo2_amd/csrc/hostplan.h"
 
 int main() {
@@ -229,6 +234,119 @@ int main() {
         // tests/test_gpu_parity.py test_msm_all_same_base_skewed and its twin under the override
         expect(msm_route(MsmShape{5000, 1, 0, 0, 4}, false, false) == MSM_ROUTE_SMALL && msm_route(MsmShape{5000, 1, 0, 8, 4}, false, false) == MSM_ROUTE_PIPELINE,
                "5000 pairs: one launch; the pipeline under a window override", 5000, 8);
+    }
+    // The plan of an IPA opening (ipa_plan): invariants over every shape the entry accepts
+    {
+        const int folds[] = {0, 1, 2, 4, 7, 8, 10}, overrides[] = {0, 12};
+        for (uint32_t k = 1; k <= 26; ++k) for (int with_u = 0; with_u < 2; ++with_u) for (int c = 9; c <= 18; ++c) for (int fold : folds) for (int ov : overrides) {
+            const bool table = c >= 10;  // c = 9 stands for "no table"
+            const size_t n = (size_t)1 << k;
+            const int W = table ? num_windows(c) : 0;
+            const IpaPlan p = ipa_plan(IpaShape{k, n + 1 + with_u, table, table ? c : 0, W, ov, fold, SMALL_MAX_N});
+            const unsigned long long id = (unsigned long long)k * 1000 + with_u * 100 + c, id2 = (unsigned long long)fold * 100 + ov;
+            expect(p.k == k && p.n == n && p.with_u == (with_u != 0), "ipa: the shape", id, id2);
+            // the first MSM
+            const bool tabled = with_u && table, small = n + 2 <= SMALL_MAX_N && ov == 0;
+            expect(p.first_msm == (!tabled ? IPA_MSM_PLAIN : small ? IPA_MSM_SMALL_Z : IPA_MSM_TABLE), "ipa: form of the first MSM", id, id2);
+            expect(p.first_pairs == (tabled ? n + 2 : n + 1), "ipa: pairs of the first MSM", id, id2);
+            if (with_u && n + 2 <= SMALL_MAX_N && ov == 0) expect(p.first_msm != IPA_MSM_TABLE && p.fold_at == 0, "ipa: a set within the small kernel never uses its table and never collapses", id, id2);
+            if (p.first_msm == IPA_MSM_SMALL_Z) expect(msm_route(MsmShape{p.first_pairs, 1, 0, ov, 4}, false, false) == MSM_ROUTE_SMALL, "ipa: small_z is one launch", id, id2);
+            expect(p.bytes.sp >= p.first_pairs * 32 && p.bytes.sp >= (n + 2) * 32, "ipa: s' holds the first MSM's scalars, blind and the scalar of u", id, id2);
+            expect(p.bytes.b >= n * 32 && p.bytes.pp >= n * 32 && p.eval_blocks >= 1 && p.eval_blocks <= 512 && p.bytes.io >= (size_t)p.eval_blocks * 32, "ipa: the evaluation launches", id, id2);
+            // the collapse
+            if (p.fold_at) {
+                const uint32_t r = p.fold_at;
+                expect(with_u && table && k >= 14 && ipa_fold_supported(true, c, W, k, r) && p.first_msm == IPA_MSM_TABLE, "ipa: a collapse needs g || w || u, a table, k >= 14 and a supported shape", id, id2);
+                expect(r == (uint32_t)(fold == 1 ? k - 12 : fold) && r >= 2 && r <= 10 && r + 8 <= k, "ipa: the collapse round is the option's (1: k - 12)", id, r);
+                expect(p.m == n >> r && p.m >= 256 && p.m % 256 == 0, "ipa: whole workgroups of collapsed generators", id, p.m);
+                if (fold == 1) expect(p.m == 4096, "ipa: the library's choice collapses to 2^12 generators", id, p.m);
+                expect(p.fold_w0 + p.fold_w1 == (uint32_t)c && p.fold_w0 >= p.fold_w1 && p.fold_w1 >= 5 && p.fold_w0 <= 9, "ipa: two sub-digits of 5 .. 9 bits per window", id, p.fold_w0);
+                expect(p.fold_nbk == (1u << (p.fold_w0 - 1)) + (1u << (p.fold_w1 - 1)), "ipa: buckets of the collapse", id, p.fold_nbk);
+                expect(p.bytes.fold_buckets == (size_t)(p.fold_nbk + 1) * p.m * 144, "ipa: buckets and the m sums behind them", id, p.bytes.fold_buckets);
+                expect(p.fold_list_words == (size_t)p.fold_nbk + 1 + ((size_t)2 << r) * W, "ipa: offsets + two entries per scalar and window", id, p.fold_list_words);
+                // the stand-alone collapse of the same shape sizes the same buffers and nothing else
+                const IpaPlan q = ipa_collapse_plan(c, W, k, r);
+                expect(q.fold_at == r && q.m == p.m && q.fold_nbk == p.fold_nbk && q.fold_w0 == p.fold_w0 && q.fold_w1 == p.fold_w1 && q.bytes.fold_buckets == p.bytes.fold_buckets &&
+                       q.fold_list_words == p.fold_list_words, "ipa: the collapse alone plans as the opening's", id, id2);
+                expect(q.bytes.b + q.bytes.sp + q.bytes.pp + q.bytes.wgt + q.bytes.lrsc + q.bytes.gwu + q.bytes.gwuz + q.bytes.pp2 + q.bytes.b2 + q.bytes.io == 0, "ipa: the collapse alone has no vectors", id, id2);
+            } else {
+                const uint32_t want = fold == 1 ? (k >= 14 ? k - 12 : 0) : (uint32_t)fold;
+                expect(!(p.first_msm == IPA_MSM_TABLE && k >= 14 && ipa_fold_supported(true, c, W, k, want)), "ipa: a supported collapse is taken", id, id2);
+                expect(p.bytes.fold_buckets == 0 && p.fold_list_words == 0, "ipa: no collapse, no buffers for one", id, id2);
+            }
+            // the rounds' window override: k - 8 for k = 16..18 unless the MSMs run over the table
+            expect(p.round_window == ((p.first_msm != IPA_MSM_TABLE && k >= 16 && k <= 18) ? (int)k - 8 : 0), "ipa: window override of the rounds", id, p.round_window);
+            const int live_ov = ov ? ov : p.round_window;  // what msm_enqueue finds in the context during the rounds (WindowGuard)
+            // own copy of the round bases: the whole set with u appended, or the collapsed generators
+            expect(p.bytes.gwu == (!with_u ? (n + 2) * 64 : p.fold_at ? (p.m + 2) * 64 : 0) && p.bytes.gwuz == 2 * p.bytes.gwu, "ipa: the opening's own round bases", id, p.bytes.gwu);
+            size_t small_msms = p.first_msm == IPA_MSM_SMALL_Z ? 1 : 0;
+            for (uint32_t j = 0; j < k; ++j) {
+                const IpaRound g = p.round(j);
+                const bool folded = p.fold_at && j >= p.fold_at;
+                expect(g.gens == (folded ? p.m : n) && g.stride == g.gens + 2, "ipa round: generators and stride", id, j);
+                expect(g.bit == k - j - 1 && g.half == (size_t)1 << g.bit && 2 * g.half <= g.gens, "ipa round: half", id, j);
+                expect(g.table == (p.first_msm == IPA_MSM_TABLE && !folded), "ipa round: over the table until the collapse", id, j);
+                if (folded) expect(g.gens + 2 == p.m + 2 && g.canon == (ov == 0 && p.m + 2 <= SMALL_MAX_N ? 1 : 0), "ipa round: m + 2 pairs behind a collapse, the small kernel's where they fit", id, j);
+                if (folded && fold == 1 && ov == 0) expect(g.canon == 1, "ipa round: canonical rows behind the library's collapse", id, j);
+                // canon says which kernel takes the MSM: it must be msm_enqueue's own route for the call
+                expect((g.canon != 0) == (msm_route(MsmShape{g.gens + 2, 2, g.table ? c : 0, live_ov, 4}, false, false) == MSM_ROUTE_SMALL), "ipa round: canon is the MSM's route", id, j);
+                small_msms += g.canon ? 1 : 0;
+                expect(g.first == (j == 0) && g.wfresh == (j <= 1 || (p.fold_at && (j == p.fold_at || j == p.fold_at + 1)) ? 1 : 0), "ipa round: flags of the front launch", id, j);
+                expect(g.front_blocks == (g.gens + 255) / 256 && g.sum_blocks >= 1 && g.sum_blocks <= 512 && g.sum_blocks == ((g.half + 255) / 256 < 512 ? (g.half + 255) / 256 : 512),
+                       "ipa round: workgroups", id, j);
+                // every buffer holds the round's use of it
+                expect(p.bytes.wgt >= g.gens * 32, "ipa round: weights", id, j);
+                expect(p.bytes.lrsc >= (g.stride + g.gens + 2) * 32, "ipa round: two scalar rows with their tails", id, j);
+                expect(p.bytes.io >= ((size_t)2 * g.sum_blocks) * 32, "ipa round: partial sums of both sides", id, j);
+                // round j reads p' / b of 2^(k - j) entries (j >= 1: both halves of the previous round's, 2^(k - j + 1)) and writes the folds, 2^(k - j):
+                // rounds 0 and 1 read the first buffers, then the pairs alternate -- odd rounds write the second buffers
+                const size_t reads = j ? 4 * g.half : 2 * g.half, writes = j ? 2 * g.half : 0;
+                const size_t read_buf = (j <= 1 || j % 2 == 1) ? p.bytes.pp : p.bytes.pp2, write_buf = j % 2 == 1 ? p.bytes.pp2 : p.bytes.pp;
+                expect(read_buf >= reads * 32 && write_buf >= writes * 32 && p.bytes.b2 == p.bytes.pp2 && p.bytes.b == p.bytes.pp, "ipa round: the ping-pong pairs", id, j);
+                if (folded || !with_u) expect(p.bytes.gwu >= (g.gens + 2) * 64 && p.bytes.gwuz >= (g.gens + 2) * 128, "ipa round: own bases", id, j);
+            }
+            // the counts tests/test_gpu_realsize.py::_ipa_case asserts through trh_stat "msm_small_launches" and "ipa_generator_collapses"
+            // (for every table that can exist -- W (n + 2) <= 2^24, so k <= 20; from k = 23 the choice k - 12 is beyond the ten rounds a collapse takes)
+            if (tabled && fold == 1 && ov == 0 && msm_fixed_base_fits(n + 2, c)) {
+                expect(small_msms == (k <= 13 ? k + 1 : 12), "ipa: k + 1 small MSMs up to k = 13, the 12 rounds behind the collapse from 14", id, small_msms);
+                expect((p.fold_at != 0) == (k >= 14), "ipa: one collapse from k = 14", id, p.fold_at);
+            }
+            if (ov == 0) expect((p.round_window != 0) == (!tabled && k >= 16 && k <= 18) && (!p.round_window || p.round_window == (int)k - 8), "ipa: k - 8 exactly for untabled k = 16..18", id, p.round_window);
+        }
+        // the bucket count is the one the bucket lists are built with (foldplan.h)
+        for (int c = 10; c <= 18; ++c) {
+            const IpaPlan q = ipa_collapse_plan(c, num_windows(c), 14, 2);
+            std::vector<trh::hostcombine::H> one(4, trh::hostcombine::H{{1, 0, 0, 0}});
+            std::vector<uint32_t> lists;
+            uint32_t nbk = 0;
+            expect(trh::foldplan::fold_plan(one, c, num_windows(c), q.fold_w0, q.fold_w1, lists, nbk) == trh::foldplan::FOLD_PLAN_OK && nbk == q.fold_nbk && lists.size() <= q.fold_list_words,
+                   "ipa: the plan's buckets are the bucket lists'", c, nbk);
+        }
+        // an unsupported collapse alone keeps its (k, r) for the refusal and sizes nothing
+        for (const auto& kr : {std::pair<uint32_t, uint32_t>{10, 1}, {10, 3}, {9, 2}, {10, 11}, {10, 200}}) {
+            const IpaPlan q = ipa_collapse_plan(12, num_windows(12), kr.first, kr.second);
+            expect(q.k == kr.first && q.fold_at == kr.second && q.bytes.fold_buckets == 0 && q.fold_list_words == 0, "ipa: an unsupported collapse sizes nothing", kr.first, kr.second);
+        }
+        expect(ipa_collapse_plan(9, num_windows(9), 10, 2).bytes.fold_buckets == 0, "ipa: a 9-bit table has no collapse", 9, 0);
+        // the byte sizes, restated from the expressions of the opening before the plan existed (n = 2^k):
+        //   b, p', weights n * 32; s' (n + 2) * 32; rows 2 * (n + 2) * 32; second halves n * 16 + 32; partial sums (2 * 512 + 2) * 32;
+        //   own bases (points) * 64 and * 128; buckets (nbk + 1) * m * 144; lists nbk + 1 + (2 << r) * W words
+        const struct { uint32_t k; int with_u, c, W; size_t b, sp, lrsc, pp2, gwu, gwuz, buckets, words; uint32_t fold_at; } rows[] = {
+            {10, 1, 12, 22, 32768, 32832, 65664, 16416, 0, 0, 0, 0, 0},
+            {10, 0, 0, 0, 32768, 32832, 65664, 16416, 65664, 131328, 0, 0, 0},
+            {14, 1, 14, 19, 524288, 524352, 1048704, 262176, 262272, 524544, 76087296, 281, 2},
+            {14, 0, 0, 0, 524288, 524352, 1048704, 262176, 1048704, 2097408, 0, 0, 0},
+            {18, 1, 16, 16, 8388608, 8388672, 16777344, 4194336, 262272, 524544, 151584768, 2305, 6},
+            {18, 1, 15, 18, 8388608, 8388672, 16777344, 4194336, 262272, 524544, 113836032, 2497, 6},
+            {18, 0, 0, 0, 8388608, 8388672, 16777344, 4194336, 16777344, 33554688, 0, 0, 0},
+        };
+        for (const auto& r : rows) {
+            const IpaPlan p = ipa_plan(IpaShape{r.k, ((size_t)1 << r.k) + 1 + r.with_u, r.c != 0, r.c, r.W, 0, 1, SMALL_MAX_N});
+            expect(p.bytes.b == r.b && p.bytes.pp == r.b && p.bytes.wgt == r.b && p.bytes.sp == r.sp && p.bytes.lrsc == r.lrsc && p.bytes.pp2 == r.pp2 && p.bytes.b2 == r.pp2, "ipa sizes: the vectors", r.k, r.c);
+            expect(p.bytes.io == 32832, "ipa sizes: partial sums", r.k, p.bytes.io);
+            expect(p.bytes.gwu == r.gwu && p.bytes.gwuz == r.gwuz, "ipa sizes: own bases", r.k, p.bytes.gwu);
+            expect(p.fold_at == r.fold_at && p.bytes.fold_buckets == r.buckets && p.fold_list_words == r.words, "ipa sizes: the collapse", r.k, p.bytes.fold_buckets);
+        }
     }
     std::printf(bad ? "hostplan: FAILED (%d)\n" : "hostplan: ok\n", bad);
     return bad ? 1 : 0;

@@ -87,7 +87,7 @@ def _check_plan(shape, sc, rc, nbk, plan):
         return False
     assert rc == 0, f"{tag}: refused although every scalar fits"
     assert nbk == nb0 + nb1
-    # size bound: what ipa_fold_reserve sizes the buffers by, (2 << r) * W entries for 2^r scalars
+    # size bound: what hostplan::ipa_collapse_geometry (fold_list_words) sizes the buffers by, (2 << r) * W entries for 2^r scalars
     assert len(plan) <= nbk + 1 + 2 * len(sc) * W, tag
     off, ent = plan[:nbk + 1], plan[nbk + 1:]
     assert off[0] == 0 and off[nbk] == len(ent) and all(a <= b for a, b in zip(off, off[1:])), f"{tag}: offsets"
@@ -121,7 +121,7 @@ def test_fold_plan_reconstructs_every_scalar_exactly():
     1024 scalars for c = 10 and 18 (t up to 1023 in the entry word).  Asserted: each scalar equals, as an integer, the sum over its entries
     of sign * digit * 2^(c j + sub-window shift); offsets start at 0, never decrease and end at the entry count; every entry sits in the
     bucket of the digit an independent recoding gives it; entries of a bucket ascend in (t, j), which tests/test_gpu_ipa_collapse.py relies
-    on; the plan is no longer than ipa_fold_reserve's bound.  Every c * W >= 256 here, so 2^255 - 1 fits and is reconstructed."""
+    on; the plan is no longer than the bound of hostplan::ipa_collapse_geometry (fold_list_words).  Every c * W >= 256 here, so 2^255 - 1 fits and is reconstructed."""
     rng = random.Random(0xF01D)
     cases = [(_shape(c), _scalars(c, rng)) for c in WINDOWS]
     # a table too short for its scalar: c = 16 with 15 windows cannot hold bit 240 and up

@@ -83,7 +83,8 @@ def test_host_range_cuts_and_ntt_pass_plan():
     """csrc/hostplan.h, the host-side shape decisions of the two headline operations: the range boundaries of an MSM with host scalars
     (both modes, sizes on and around the 2^21 and 3 * 2^21 thresholds, a ragged last range, 2^31 - 1), the NTT's pass plan for
     log_n = 1 .. 27 and the transforms per launch set of its lazy passes (hostplan::ntt_lazy_chunk, log_n = 12 .. 27 with and without coset blocks); and the launch plan of an MSM on the device (hostplan::msm_route / msm_plan: invariants over a sweep of shapes, the routes at
-    their edges, the geometry of named shapes); built with address + undefined sanitizers.  The GPU tests assert the same range counts through trh_stat"""
+    their edges, the geometry of named shapes); and the plan of an IPA opening (hostplan::ipa_plan: every shape the entry accepts, the small-MSM and
+    collapse counts the GPU tests read from trh_stat, the byte sizes of the scratch as literals); built with address + undefined sanitizers.  The GPU tests assert the same range counts through trh_stat"""
     src = os.path.join(ROOT, "tests", "native", "hostplan_test.cpp")
     with tempfile.TemporaryDirectory() as tmp:
         exe = os.path.join(tmp, "hostplan_test")

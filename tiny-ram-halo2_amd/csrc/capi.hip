@@ -223,13 +223,12 @@ static void destroy_ctx(Ctx* c) {
             ntt_release_tables();
             encoding_release();
             hashtocurve_release();
-            for (DevBuf& d : c->ipa) d.release();
+            c->ipa.release();
             c->io.release();
             stage_release(*c);
             c->factors.release();
             if (c->pinned_ring) { (void)hipHostFree(c->pinned_ring); c->pinned_ring = nullptr; c->pinned_slot = 0; }
             if (c->pinned_land) { (void)hipHostFree(c->pinned_land); c->pinned_land = nullptr; }
-            if (c->pinned_fold) { (void)hipHostFree(c->pinned_fold); c->pinned_fold = nullptr; c->pinned_fold_cap = 0; }
             c->pfft.release();
             c->scan.release(); c->scan2.release();
             c->last_stream_valid = false;
@@ -1379,7 +1378,7 @@ int trh_stat(const char* name, uint64_t* value) {
         for (u32 k = 0; k < m.sort_flag_count; ++k) *value += flags[k] == 0u;
         return TRH_OK;
     }
-    if (strcmp(name, "ipa_generator_collapses") == 0) { *value = ctx().ipa_collapses; return TRH_OK; }
+    if (strcmp(name, "ipa_generator_collapses") == 0) { *value = ctx().ipa.collapses; return TRH_OK; }
     if (strcmp(name, "lookup_check_probes") == 0) { *value = ctx().lookup_check_probes; return TRH_OK; }
     set_error("trh_stat: unknown counter '%s'", name);
     return TRH_EINVAL;

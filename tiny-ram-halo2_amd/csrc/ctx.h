@@ -24,6 +24,7 @@
 
 struct trh_bases;
 namespace trh { class CopyPool; }
+namespace trh { namespace hostplan { struct IpaPlan; } }  // hostplan.h
 
 namespace trh {
 
@@ -192,6 +193,24 @@ struct Stage {
     std::map<int, std::array<hipEvent_t, NS>> xfer_ev;  // stage_d2d_via_host: "slot filled" events on the source device, per source device
 };
 
+// Scratch of the IPA opening (ipa.hip) and of its generator collapse (ipafold.hip), kept across proofs: a hipMalloc / hipFree pair per vector
+// costs more than several rounds.  Sized by ipa_scratch_reserve from a hostplan::IpaPlan and by nothing else.
+struct IpaScratch {
+    DevBuf b, sp, pp, wgt;      // the powers of x3, s', p', the generators' weights
+    DevBuf lrsc;                // the two scalar rows of a round's MSM
+    DevBuf gwu, gwuz;           // the opening's own round bases (g‖w‖u for a set without u, G''‖w‖u after a collapse): affine and record form
+    DevBuf pp2, b2;             // the second halves of the p' / b ping-pong pairs
+    DevBuf fold_buckets;        // the collapse's buckets, then the m sums between its reduction and its inversion
+    DevBuf fold_lists;          // the collapse's bucket lists
+    void* fold_pinned = nullptr;  // pinned source of the bucket lists
+    size_t fold_pinned_cap = 0;
+    u64 collapses = 0;          // openings that collapsed their generators (tests)
+    void release() {
+        for (DevBuf* d : {&b, &sp, &pp, &wgt, &lrsc, &gwu, &gwuz, &pp2, &b2, &fold_buckets, &fold_lists}) d->release();
+        if (fold_pinned) { (void)hipHostFree(fold_pinned); fold_pinned = nullptr; fold_pinned_cap = 0; }
+    }
+};
+
 struct Ctx {
     std::recursive_mutex mu;  // recursive: an entry point may call another one (and a transcript callback may call host-side helpers)
     bool inited = false;
@@ -209,16 +228,12 @@ struct Ctx {
     DevBuf sqrt_tab[2];     // fieldsqrt.h's table per field (encoding.hip; uploaded at first use, kept like the twiddle tables)
     DevBuf enc_first_bad;   // one word: the smallest invalid index of the last decompression
     DevBuf h2c_u;           // hashtocurve.hip: the field elements between the fused entry's hash and map kernels (one chunk of points)
-    DevBuf ipa[11];  // vectors of the IPA prover (b, s', p', weights, round scalars, g‖w‖u and its lazy copy, the second halves of the p' / b ping-pong pairs,
-                     // the generator fold's buckets and bucket lists -- ipafold.hip), kept across proofs
+    IpaScratch ipa;
     DevBuf factors;  // ring of 16 small factor tables for the scale kernels
     unsigned factor_slot = 0;
     void* pinned_ring = nullptr;  // 64 x 2 KiB of pinned host memory mirroring the factor ring: constants are copied here first, so the
     void* pinned_land = nullptr;  // 4 KiB pinned landing area for the few words the host reads back per IPA round (a pageable target costs a staging copy)
     unsigned pinned_slot = 0;     // asynchronous upload never reads a caller's stack buffer and needs no synchronisation
-    void* pinned_fold = nullptr;  // pinned source of the generator fold's bucket lists (ipafold.hip)
-    size_t pinned_fold_cap = 0;
-    u64 ipa_collapses = 0;      // openings that collapsed their generators (ipafold.hip; tests)
     bool helper_failed = false;
     class HostHelper* helper = nullptr;  // host thread for the second half of a batch's Horners (hosthelper.h; msm_finish)
     std::vector<TwiddleEntry*> twiddles;
@@ -345,10 +360,12 @@ int ntt_prepare(int field, uint32_t log_n, const u64 omega[4], const u64* scale,
 bool ntt_can_fold_scale(uint32_t log_n);
 void ntt_release_tables();
 // ipafold.hip: the IPA's generators after r collapses, from the fixed-base table of g || w || u
-bool ipa_fold_supported(const MsmFixedBase& fb, uint32_t k, uint32_t r);
-int ipa_fold_reserve(const MsmFixedBase& fb, uint32_t k, uint32_t r);
+// (p: the opening's plan or hostplan::ipa_collapse_plan; r = p.fold_at)
+int ipa_fold_generators(int curve, const MsmFixedBase& fb, size_t row, const hostplan::IpaPlan& p, const u64* u_mont, void* out_xy, void* out_z, hipStream_t s);
 int ipa_reserve(int curve, const trh_bases* gw, uint32_t k);  // ipa.hip: the opening's vectors and the collapse's buffers, at setup time
-int ipa_fold_generators(int curve, const MsmFixedBase& fb, size_t row, uint32_t k, uint32_t r, const u64* u_mont, void* out_xy, void* out_z, hipStream_t s);
+// ipa.hip: every buffer of Ctx::ipa and the partial sums in Ctx::io at the plan's sizes.  list_words: the collapse's bucket lists -- the plan's bound
+// (an opening, ipa_reserve) or the exact length of the lists at hand, which is at most that
+int ipa_scratch_reserve(Ctx& c, const hostplan::IpaPlan& p, size_t list_words, hipStream_t s);
 // ipa.hip: out[i] = x^i, i < n (trh_field_powers_dev's kernel, for callers inside an entered context: permutation.hip's omega^row and delta^column tables)
 int field_powers_device(int field, void* out_dev, size_t n, const u64 x_mont[4], hipStream_t s);
 // msm.hip

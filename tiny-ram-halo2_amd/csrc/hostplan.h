@@ -1,7 +1,8 @@
 // Host-side shape decisions of the two headline operations, free of HIP types so that a plain C++ test can check them
 // (tests/native/hostplan_test.cpp): where msm_host_tiled (capi.hip) cuts an MSM with host scalars into ranges, how
-// ntt.hip splits a transform into passes and a batch into launch sets, and the launch plan of an MSM on the device (msm.hip: route, Pippenger geometry,
-// scratch layout) as a pure function of its shape.
+// ntt.hip splits a transform into passes and a batch into launch sets, the launch plan of an MSM on the device (msm.hip: route, Pippenger geometry,
+// scratch layout) as a pure function of its shape, and the plan of an IPA opening (ipa.hip, ipafold.hip: the form of its MSMs, the generator
+// collapse, every round's geometry, the size of every scratch buffer) likewise.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -286,6 +287,139 @@ inline MsmSegments msm_segments_counted(const MsmPlan& p, size_t sum, uint32_t m
     uint32_t nseg = (most + seg_len - 1) / seg_len;  // segments beyond the longest list would find nothing
     if (nseg == 0) nseg = 1;
     return msm_segments(p.Ws, seg_len, nseg);
+}
+
+// ---------------------------------------------------------------------------------------
+// The plan of one IPA opening (ipa.hip; the generator collapse: ipafold.hip): everything trh_ipa_create_proof decides from its shape --
+// the form of its MSMs, the round at which the generators collapse, every round's geometry and the size of every scratch buffer -- as a
+// pure function of that shape.  Same constraints as msm_plan.  IpaScratch (ctx.h) is sized from it and from nothing else.
+// ---------------------------------------------------------------------------------------
+constexpr size_t FE_BYTES = 32;             // a field element
+constexpr size_t AFFINE_BYTES = 64;         // an affine base
+constexpr size_t ZREC_BYTES = 128;          // a base in the accumulation's record format (ctx.h ZREC)
+constexpr unsigned IPA_SUM_BLOCKS = 512;    // workgroups of the opening's evaluation and inner-product launches at most
+
+struct IpaShape {
+    uint32_t k;
+    size_t set_len;           // points of the base set: 2^k + 1 (g || w) or 2^k + 2 (g || w || u)
+    bool table;               // the set has a fixed-base table of fb_W windows of fb_c bits
+    int fb_c, fb_W;
+    int window_override;      // the context's override, 0: none
+    int ipa_fold;             // option ipa_fold
+    size_t small_max;         // the largest MSM msm_small_kernel takes (SMALL_MAX_N)
+};
+
+// two sub-digits of 5 .. 9 bits per table window (sixteen slices of >= 1 bucket); t and the table level share an entry word; whole workgroups of generators
+inline bool ipa_fold_supported(bool table, int c, int W, uint32_t k, uint32_t r) {
+    return table && c >= 10 && c <= 18 && W < 0x8000 && r >= 2 && r <= 10 && k >= r + 8;
+}
+// the round after which the generators are collapsed (0: never -- no table, a small opening, or option ipa_fold = 0).  Option 1 = the measured
+// choice: after six rounds, later where the collapsed set would not fit msm_small_kernel (k = 18: 5 / 6 / 7 / 8 rounds -> 9.3 / 9.0 / 9.2 / 9.6 ms)
+inline uint32_t ipa_fold_level(bool table, int c, int W, uint32_t k, int ipa_fold) {
+    uint32_t r = (uint32_t)ipa_fold;
+    if (r == 1) r = k >= 14 ? k - 12 : 0;  // down to 2^12 generators
+    return (r > 0 && k >= 14 && ipa_fold_supported(table, c, W, k, r)) ? r : 0;
+}
+
+enum IpaFirstMsm {
+    IPA_MSM_TABLE,    // over the table, all 2^k + 2 pairs (the scalar of u is zero)
+    IPA_MSM_SMALL_Z,  // 2^k + 2 pairs through msm_small_kernel, level 0 of the table as its bases: the table is left alone
+    IPA_MSM_PLAIN,    // g || w alone, 2^k + 1 pairs
+};
+struct IpaRound {
+    size_t gens, stride;      // generators of the round's MSM (gens + 2 pairs: then w and u); elements between its two scalar rows
+    size_t half; uint32_t bit;
+    bool table;               // the MSM runs over the set's table
+    int canon;                // the MSM is msm_small_kernel's: the scalar rows leave in canonical form
+    int first, wfresh;        // ipa_round_front_kernel's flags: nothing to fold yet; the weights are all one and not in memory yet
+    unsigned front_blocks, sum_blocks;  // workgroups of the front launch and (per side) of the inner products
+};
+struct IpaPlan {
+    uint32_t k; size_t n;
+    bool with_u;              // the set is g || w || u
+    IpaFirstMsm first_msm; size_t first_pairs;  // the commitment to s'; the rounds before a collapse run over the same bases
+    uint32_t fold_at; size_t m;                 // the generators collapse in front of round fold_at (0: never) to m = 2^(k - fold_at)
+    uint32_t fold_w0, fold_w1, fold_nbk;        // the collapse's two sub-digit widths per table window and its buckets
+    int round_window;         // window override of the rounds where the context has none, 0: none
+    int window_override; size_t small_max;      // (of the shape)
+    unsigned eval_blocks;     // workgroups of the two evaluation launches
+    // ---- scratch: the bytes of every buffer of IpaScratch and of the partial sums in Ctx::io, once
+    struct {
+        size_t b, sp, pp, wgt;   // b = powers of x3, s', p', weights: n elements (s' with the blind and the scalar of u behind it)
+        size_t lrsc;             // the two scalar rows of a round's MSM
+        size_t gwu, gwuz;        // g || w || u where the set lacks u, G'' || w || u after a collapse: affine and record form; else none
+        size_t pp2, b2;          // second halves of the p' / b ping-pong pairs: the folded vectors have at most n / 2 entries
+        size_t io;               // partial sums: two sides of IPA_SUM_BLOCKS and two results
+        size_t fold_buckets;     // the collapse's buckets + the m sums between the reduction and the inversion
+    } bytes;
+    size_t fold_list_words;   // bound on the collapse's bucket lists: offsets, then two entries per scalar and window
+
+    IpaRound round(uint32_t j) const {
+        IpaRound r{};
+        const bool folded = fold_at && j >= fold_at;
+        r.gens = folded ? m : n; r.stride = r.gens + 2;
+        r.bit = k - j - 1; r.half = (size_t)1 << r.bit;
+        r.table = first_msm == IPA_MSM_TABLE && !folded;
+        r.canon = (!r.table && r.gens + 2 <= small_max && window_override == 0) ? 1 : 0;
+        r.first = j == 0 ? 1 : 0;
+        r.wfresh = (j <= 1 || (fold_at && (j == fold_at || j == fold_at + 1))) ? 1 : 0;  // a collapse starts the weights afresh
+        r.front_blocks = (unsigned)((r.gens + 255) / 256);
+        r.sum_blocks = (unsigned)((r.half + 255) / 256);
+        if (r.sum_blocks > IPA_SUM_BLOCKS) r.sum_blocks = IPA_SUM_BLOCKS;
+        return r;
+    }
+};
+
+// the collapse's part of a plan: r rounds at once over a table of W windows of c bits (ipafold.hip); ipa_fold_supported(.., k, r) holds
+inline void ipa_collapse_geometry(IpaPlan& p, int c, int W, uint32_t r) {
+    p.fold_at = r; p.m = (size_t)1 << (p.k - r);
+    p.fold_w0 = (uint32_t)(c + 1) / 2; p.fold_w1 = (uint32_t)c / 2;
+    p.fold_nbk = (1u << (p.fold_w0 - 1)) + (1u << (p.fold_w1 - 1));
+    p.bytes.fold_buckets = (size_t)(p.fold_nbk + 1) * p.m * RAW_POINT_BYTES;
+    p.fold_list_words = (size_t)p.fold_nbk + 1 + ((size_t)2 << r) * W;
+}
+// a collapse alone (trh_ipa_collapse_generators_dev, any supported (k, r)): its own buffers, the generators go to the caller's
+inline IpaPlan ipa_collapse_plan(int c, int W, uint32_t k, uint32_t r) {
+    IpaPlan p{};
+    p.k = k; p.n = (size_t)1 << k; p.fold_at = r;
+    if (ipa_fold_supported(true, c, W, k, r)) ipa_collapse_geometry(p, c, W, r);  // (otherwise ipa_fold_generators refuses the plan)
+    return p;
+}
+
+inline IpaPlan ipa_plan(const IpaShape& sh) {
+    IpaPlan p{};
+    const uint32_t k = p.k = sh.k;
+    const size_t n = p.n = (size_t)1 << k;
+    p.window_override = sh.window_override; p.small_max = sh.small_max;
+    // A base set that holds g || w || u (n + 2 points) with fixed-base tables attached (trh_bases_precompute: Params are fixed for
+    // the life of a proving key) lets every MSM of the opening run in fixed-base mode: one bucket set instead of one per window,
+    // wide windows, no heavy top-window buckets and no Horner over windows on the host between two rounds.
+    p.with_u = sh.set_len == n + 2;
+    const bool tabled = p.with_u && sh.table;
+    // A set small enough for msm_small_kernel does not use its table: one launch + a host Horner beats the fixed-base pipeline's chain of ten
+    // launches (k = 10: 3.3 -> 2.1 ms per opening, k = 13: 5.4 -> 3.7); level 0 of the table is the set in the accumulation's record format
+    const bool small_z = tabled && n + 2 <= sh.small_max && sh.window_override == 0;
+    p.first_msm = !tabled ? IPA_MSM_PLAIN : small_z ? IPA_MSM_SMALL_Z : IPA_MSM_TABLE;
+    p.first_pairs = tabled ? n + 2 : n + 1;
+    // the round MSMs are batches of two with half of the scalars zero: their time is the latency of the sort / reduction chain,
+    // which narrow windows shorten (measured: k = 18 -> c = 10 gives 24.4 ms against 26.7 at the table's 15; k = 14 -> 8);
+    // k = 20: the table's 15 is better again (60 vs 68 ms)
+    p.round_window = (p.first_msm != IPA_MSM_TABLE && k >= 16 && k <= 18) ? (int)k - 8 : 0;
+    p.eval_blocks = (unsigned)((n + 255) / 256);
+    if (p.eval_blocks > IPA_SUM_BLOCKS) p.eval_blocks = IPA_SUM_BLOCKS;
+    p.bytes.b = p.bytes.pp = p.bytes.wgt = n * FE_BYTES;
+    p.bytes.sp = (n + 2) * FE_BYTES;
+    p.bytes.lrsc = 2 * (n + 2) * FE_BYTES;
+    p.bytes.pp2 = p.bytes.b2 = n * (FE_BYTES / 2) + FE_BYTES;
+    p.bytes.io = (size_t)(2 * IPA_SUM_BLOCKS + 2) * FE_BYTES;
+    // Hybrid (ipafold.hip): the first r rounds run over the 2^k original bases with the folds as weights (a full-size fixed-base MSM each); then
+    // the generators are collapsed for real -- r folds at once from the table -- and the remaining k - r rounds are MSMs over m + 2 = 2^(k - r) + 2
+    // points, a fraction of a full-size round each.  Only worth it where a full-size round costs much more than a small one.
+    const uint32_t r = ipa_fold_level(p.first_msm == IPA_MSM_TABLE, sh.fb_c, sh.fb_W, k, sh.ipa_fold);
+    if (r) ipa_collapse_geometry(p, sh.fb_c, sh.fb_W, r);
+    const size_t own = !p.with_u ? n + 2 : r ? p.m + 2 : 0;  // points of the opening's own copy of the round bases
+    p.bytes.gwu = own * AFFINE_BYTES; p.bytes.gwuz = own * ZREC_BYTES;
+    return p;
 }
 
 }  // namespace hostplan

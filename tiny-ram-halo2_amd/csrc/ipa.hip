@@ -12,11 +12,14 @@
 #include <string.h>
 
 #include <chrono>
+#include <initializer_list>
+#include <utility>
 
 #include "ctx.h"
 #include "devmem.h"
 #include "hostcombine.h"
 #include "hosthelper.h"
+#include "hostplan.h"
 
 namespace trh {
 namespace {
@@ -374,238 +377,267 @@ int axpy_t(void* y, const void* x, size_t n, const FeMem& c_mont, hipStream_t s)
 // The whole opening: poly::commitment::prover::create_proof with p', b and G' resident on the
 // device.  Host-side scalar arithmetic uses the shared field code; the transcript and the prover's
 // randomness are callbacks into the caller (BLAKE2b transcript and OsRng on the Rust side).
+// Everything the opening decides from its shape is hostplan::ipa_plan's; the stages below run that plan.
 // ---------------------------------------------------------------------------------------
-// the round after which the generators are collapsed (0: never -- no table, a small opening, or option ipa_fold = 0).  Option 1 = the measured
-// choice: after six rounds, later where the collapsed set would not fit msm_small_kernel (k = 18: 5 / 6 / 7 / 8 rounds -> 9.3 / 9.0 / 9.2 / 9.6 ms)
-uint32_t ipa_fold_level(const MsmFixedBase* fb, uint32_t k) {
-    uint32_t r = (uint32_t)opt().ipa_fold;
-    if (r == 1) r = k >= 14 ? k - 12 : 0;  // down to 2^12 generators
-    return (fb && r > 0 && k >= 14 && ipa_fold_supported(*fb, k, r)) ? r : 0;
+static_assert(hostplan::ZREC_BYTES == ZREC && hostplan::FE_BYTES == sizeof(FeMem) && hostplan::AFFINE_BYTES == sizeof(AffineMem), "hostplan.h sizes the opening's buffers by these");
+
+hostplan::IpaShape ipa_shape(const trh_bases* gw, uint32_t k) {
+    return hostplan::IpaShape{k, gw->n, gw->d_table != nullptr, gw->fb.c, gw->fb.W, ctx().window_override, opt().ipa_fold, msm_small_max_pairs()};
+}
+
+template <class F>
+FeMem fe_mem(const Fe<F>& v) { FeMem m; fe_store(v, m); return m; }
+// up to three constants of a launch, as its kernel argument
+template <class F>
+IpaConsts ipa_consts(std::initializer_list<Fe<F>> v) {
+    IpaConsts k{};
+    int i = 0;
+    for (const Fe<F>& e : v) { const FeMem m = fe_mem(e); memcpy(&k.w[2 * i++], &m, 32); }
+    return k;
+}
+double ipa_now() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// One opening: the plan, the call, and what the rounds hand to each other.
+template <class SF>
+struct IpaRun {
+    hostplan::IpaPlan p;
+    int curve; const trh_bases* gw; hipStream_t s;
+    const trh_transcript_t* tr; trh_rng_scalar_fn rng; void* rng_ctx;
+    Ctx* c; IpaScratch* sc;
+    const MsmFixedBase* fb;              // the set's table while the MSMs run over it: null without one, for a small set, and after the collapse
+    const void* small_z;                 // a small tabled set: level 0 of its table, the bases in record form
+    const void *round_xy, *round_z;      // bases of the round MSMs
+    void *p_cur, *b_cur, *p_nxt, *b_nxt; // p' and b live in ping-pong pairs from round 1 on (a round reads the vectors the previous one left and writes their folds to the other buffer)
+    Fe<SF> z, f, rnd[2], u_prev, u_prev_inv;
+    u64 u_hist[16 * 4];                  // the challenges the collapse needs
+    bool trace; double t_acc[5];         // TRH_TRACE bit 1: where the host's part of a round goes (sums over the rounds, microseconds)
+};
+
+// b = (1, x3, x3^2, ...); s'(X) = s(X) - s(x3), then its commitment over g ‖ w with the blind appended: one pass copies s and forms its value at
+// x3, one workgroup subtracts it from coefficient 0 and appends the blind (and the zero scalar of u) -- no host turn before the MSM
+template <class SF>
+int commit_s_prime(IpaRun<SF>& r, const void* s_poly_dev, const Fe<SF>& s_blind, const Fe<SF>& x3) {
+    const hostplan::IpaPlan& p = r.p; IpaScratch& sc = *r.sc; hipStream_t s = r.s;
+    const FeMem x3m = fe_mem(x3);
+    TRH_TRY((powers_t<SF>(sc.b.p, p.n, (const u64*)&x3m, s)));
+    uint4* const partial = (uint4*)r.c->io.p;
+    hipLaunchKernelGGL((ipa_combine_eval_kernel<SF>), dim3(p.eval_blocks), dim3(256), 0, s, (const uint4*)s_poly_dev, (const uint4*)nullptr, sc.b.as<const uint4>(), sc.sp.as<uint4>(), p.n,
+                       IpaConsts{}, partial);
+    hipLaunchKernelGGL((ipa_fix_constant_kernel<SF>), dim3(1), dim3(256), 0, s, (const uint4*)partial, p.eval_blocks, sc.sp.as<uint4>(), p.n, 1, ipa_consts({s_blind}));
+    TRH_HIP_TRY(hipGetLastError());
+    if (p.first_msm == hostplan::IPA_MSM_TABLE) {  // the scalar of u is zero: the full-range (table) path
+        MsmFlags dense;
+        dense.dense_hint = true;  // s(X) is uniformly random: no sparse classification
+        TRH_TRY(msm_enqueue(r.curve, r.gw->d_xy, r.gw->d_z, sc.sp.p, p.first_pairs, 1, p.first_pairs, 1, s, r.fb, nullptr, dense));
+    } else
+        TRH_TRY(msm_enqueue(r.curve, r.gw->d_xy, r.small_z ? r.small_z : r.gw->d_z, sc.sp.p, p.first_pairs, 1, p.first_pairs, 1, s));
+    u64 pt[12];
+    TRH_TRY(msm_finish(r.curve, s, pt, 1));
+    r.tr->write_point(r.tr->ctx, pt);
+    return TRH_OK;
+}
+
+// p'(X) = p(X) + xi s'(X) - v, v its value at x3: the same two launches
+template <class SF>
+int form_p_prime(IpaRun<SF>& r, const void* p_poly_dev, const Fe<SF>& xi) {
+    const hostplan::IpaPlan& p = r.p; IpaScratch& sc = *r.sc;
+    uint4* const partial = (uint4*)r.c->io.p;
+    hipLaunchKernelGGL((ipa_combine_eval_kernel<SF>), dim3(p.eval_blocks), dim3(256), 0, r.s, (const uint4*)p_poly_dev, sc.sp.as<const uint4>(), sc.b.as<const uint4>(), sc.pp.as<uint4>(), p.n,
+                       ipa_consts({xi}), partial);
+    hipLaunchKernelGGL((ipa_fix_constant_kernel<SF>), dim3(1), dim3(256), 0, r.s, (const uint4*)partial, p.eval_blocks, sc.pp.as<uint4>(), p.n, 0, IpaConsts{});
+    TRH_HIP_TRY(hipGetLastError());
+    return TRH_OK;
+}
+
+// the bases of the round MSMs are g (n points) followed by w and u, so that [rand] W + [value z] U ride in the same MSM as the main sum:
+// the set itself where it holds u, otherwise a copy with u appended
+template <class SF>
+int bind_round_bases(IpaRun<SF>& r, const u64* u_xy) {
+    const size_t n = r.p.n; IpaScratch& sc = *r.sc;
+    r.round_xy = r.gw->d_xy;
+    r.round_z = nullptr;
+    if (!r.p.with_u) {
+        TRH_HIP_TRY(hipMemcpyAsync(sc.gwu.p, r.gw->d_xy, (n + 1) * 64, hipMemcpyDeviceToDevice, r.s));
+        TRH_HIP_TRY(hipMemcpy((char*)sc.gwu.p + (n + 1) * 64, u_xy, 64, hipMemcpyHostToDevice));
+        TRH_TRY(msm_convert_bases(r.curve, sc.gwu.p, sc.gwuz.p, n + 2, r.s));
+        r.round_xy = sc.gwu.p; r.round_z = sc.gwuz.p;
+    } else if (!r.fb) {
+        r.round_z = r.small_z ? r.small_z : r.gw->d_z;  // the handle's converted copy when it has one; otherwise the MSM converts per call
+    }
+    return TRH_OK;
+}
+
+// G'' || w || u from the table, after the challenges of rounds 0 .. r - 1; from here on the rounds are MSMs over m + 2 points
+// (inline: on a stream of its own under the next full-size rounds the collapse gained nothing -- profiles/r06_ipa_fold_overlap_ab.txt)
+template <class SF>
+int collapse_generators(IpaRun<SF>& r) {
+    const size_t n = r.p.n, m = r.p.m; IpaScratch& sc = *r.sc;
+    TRH_TRY(ipa_fold_generators(r.curve, *r.fb, r.gw->n, r.p, r.u_hist, sc.gwu.p, sc.gwuz.p, r.s));
+    TRH_HIP_TRY(hipMemcpyAsync((char*)sc.gwu.p + m * 64, (const char*)r.gw->d_xy + n * 64, 2 * 64, hipMemcpyDeviceToDevice, r.s));
+    TRH_HIP_TRY(hipMemcpyAsync((char*)sc.gwuz.p + m * ZREC, (const char*)r.fb->table + n * ZREC, 2 * ZREC, hipMemcpyDeviceToDevice, r.s));  // level 0 of the table = the bases
+    r.round_xy = sc.gwu.p; r.round_z = sc.gwuz.p; r.fb = nullptr;
+    ++sc.collapses;
+    return TRH_OK;
+}
+
+// per round three launches in front of the MSM (the previous round's folds applied on the fly + the scalar rows; both inner products; the tail
+// scalars -- the round's constants travel as kernel arguments), then the MSM.  No host synchronisation before the MSM: the host
+// never needs value_l / value_r.  (Round 5 had four launches here, the first version 14 small operations.)
+template <class SF>
+int enqueue_round(IpaRun<SF>& r, uint32_t j) {
+    const hostplan::IpaRound g = r.p.round(j);
+    IpaScratch& sc = *r.sc; hipStream_t s = r.s;
+    FeMem tmp;
+    r.rng(r.rng_ctx, (u64*)&tmp); r.rnd[0] = fe_load<SF>(tmp);
+    r.rng(r.rng_ctx, (u64*)&tmp); r.rnd[1] = fe_load<SF>(tmp);
+    hipLaunchKernelGGL((ipa_round_front_kernel<SF>), dim3(g.front_blocks), dim3(256), 0, s, (const uint4*)r.p_cur, (const uint4*)r.b_cur, (uint4*)r.p_nxt, (uint4*)r.b_nxt, sc.wgt.as<uint4>(),
+                       sc.lrsc.as<uint4>(), g.gens, g.half, g.bit, g.stride, g.first, g.wfresh, g.canon, ipa_consts({r.u_prev_inv, r.u_prev}));
+    if (j > 0) { std::swap(r.p_cur, r.p_nxt); std::swap(r.b_cur, r.b_nxt); }
+    // value_l = <p'[half ..], b[.. half]>, value_r = <p'[.. half], b[half ..]> over the folded vectors, then the tail scalars [rand] W, [value z] U
+    uint4* const partial = (uint4*)r.c->io.p;
+    hipLaunchKernelGGL((inner_product2_kernel<SF>), dim3(g.sum_blocks, 2), dim3(256), 0, s, (const uint4*)((const char*)r.p_cur + g.half * 32), (const uint4*)r.b_cur, (const uint4*)r.p_cur,
+                       (const uint4*)((const char*)r.b_cur + g.half * 32), g.half, partial);
+    hipLaunchKernelGGL((ipa_round_tails_kernel<SF>), dim3(2), dim3(256), 0, s, partial, g.sum_blocks, ipa_consts({r.rnd[0], r.rnd[1], r.z}), sc.lrsc.as<uint4>(), g.gens, g.stride, g.canon);
+    TRH_HIP_TRY(hipGetLastError());
+    MsmFlags dense;
+    dense.dense_hint = true;  // p' . w: full-size values on half the rows
+    return msm_enqueue(r.curve, r.round_xy, r.round_z, sc.lrsc.p, g.gens + 2, 2, g.stride, g.canon ? 0 : 1, s, r.fb, nullptr, dense);
+}
+
+// L_j and R_j to the transcript, the challenge u_j and its inverse; t_round0: when the round began (trace)
+template <class SF>
+int finish_round(IpaRun<SF>& r, uint32_t j, double t_round0) {
+    const double t_enq = r.trace ? ipa_now() : 0;
+    u64 lrb[24];
+    TRH_TRY(msm_finish(r.curve, r.s, lrb, 2));
+    const double t_fin = r.trace ? ipa_now() : 0;
+    FeMem tmp;
+    r.tr->write_point(r.tr->ctx, lrb);
+    r.tr->write_point(r.tr->ctx, lrb + 12);
+    r.tr->squeeze_challenge_scalar(r.tr->ctx, (u64*)&tmp);
+    const double t_tr = r.trace ? ipa_now() : 0;
+    const Fe<SF> u_j = fe_load<SF>(tmp);
+    if (fe_is_zero(u_j)) { set_error("ipa_create_proof: round %u challenge is zero (the Rust prover's u_j.invert().unwrap() panics here)", j); return TRH_EINVAL; }
+    // u_j^-1 on the host's 4 x 64-bit Montgomery code (hostcombine.h): the nine-limb form the device code uses costs the host three times as much
+    hostcombine::H uh;
+    memcpy(&uh, &tmp, 32);
+    const hostcombine::H uih = hostcombine::inv<SF>(uh);
+    FeMem uim;
+    memcpy(&uim, &uih, 32);
+    const Fe<SF> u_inv = fe_load<SF>(uim);
+    if (j < 16) memcpy(r.u_hist + 4 * j, &tmp, 32);
+    r.u_prev = u_j; r.u_prev_inv = u_inv;  // folded into the next round's front launch (or by the launch behind the loop)
+    r.f = fe_add(r.f, fe_add(fe_mul(r.rnd[0], u_inv), fe_mul(r.rnd[1], u_j)));
+    if (r.trace) {
+        const double t_end = ipa_now();
+        r.t_acc[0] += t_enq - t_round0; r.t_acc[1] += t_fin - t_enq; r.t_acc[2] += t_tr - t_fin; r.t_acc[3] += t_end - t_tr; r.t_acc[4] += t_end - t_round0;
+    }
+    return TRH_OK;
+}
+
+// the last round's fold: p'[0] += u^-1 p'[1] (b and the weights are not read again, the kernel folds them too); then c = p'[0] and f leave
+template <class SF>
+int final_fold(IpaRun<SF>& r, u64* out_c, u64* out_f) {
+    const uint32_t k = r.p.k;
+    if (k > 0) {
+        const size_t ncur = r.p.round(k - 1).gens;
+        hipLaunchKernelGGL((ipa_round_update_kernel<SF>), dim3((unsigned)((ncur + 255) / 256)), dim3(256), 0, r.s, (uint4*)r.p_cur, (uint4*)r.b_cur, (uint4*)r.sc->wgt.p, ncur, (size_t)1, 0u,
+                           ipa_consts({r.u_prev_inv, r.u_prev}));
+        TRH_HIP_TRY(hipGetLastError());
+    }
+    if (r.trace)
+        fprintf(stderr, "[trh ipa] k = %u, per round (us): enqueue %.1f, wait for the MSM (sync + host combine) %.1f, transcript callbacks %.1f, inversion + update launch %.1f, round %.1f\n",
+                k, r.t_acc[0] / k, r.t_acc[1] / k, r.t_acc[2] / k, r.t_acc[3] / k, r.t_acc[4] / k);
+    TRH_HIP_TRY(hipStreamSynchronize(r.s));
+    FeMem cm;
+    TRH_HIP_TRY(hipMemcpy(&cm, r.p_cur, 32, hipMemcpyDeviceToHost));
+    const FeMem fm = fe_mem(r.f);
+    r.tr->write_scalar(r.tr->ctx, (const u64*)&cm);
+    r.tr->write_scalar(r.tr->ctx, (const u64*)&fm);
+    if (out_c) memcpy(out_c, &cm, 32);
+    if (out_f) memcpy(out_f, &fm, 32);
+    return TRH_OK;
 }
 
 template <class SF, class BF>
 int ipa_create_proof_t(int curve, const trh_bases* gw, const u64* u_xy, uint32_t k, const void* p_poly_dev, const u64* p_blind_m, const u64* x3_m,
                        const void* s_poly_dev, const u64* s_blind_m, const trh_transcript_t* tr, trh_rng_scalar_fn rng, void* rng_ctx,
                        hipStream_t s, u64* out_c, u64* out_f) {
-    const size_t n = (size_t)1 << k;
     auto ld = [](const u64* p) { FeMem m; memcpy(&m, p, 32); return fe_load<SF>(m); };
-    auto stm = [](const Fe<SF>& v) { FeMem m; fe_store(v, m); return m; };
     const Fe<SF> x3 = ld(x3_m), p_blind = ld(p_blind_m), s_blind = ld(s_blind_m);
+    Ctx& c = ctx();
+    IpaRun<SF> r{};
+    r.p = hostplan::ipa_plan(ipa_shape(gw, k));
+    r.curve = curve; r.gw = gw; r.s = s; r.tr = tr; r.rng = rng; r.rng_ctx = rng_ctx; r.c = &c; r.sc = &c.ipa;
+    r.fb = r.p.first_msm == hostplan::IPA_MSM_TABLE ? &gw->fb : nullptr;
+    r.small_z = r.p.first_msm == hostplan::IPA_MSM_SMALL_Z ? gw->fb.table : nullptr;
+    r.trace = (opt().trace & 2) != 0;
+    c.msm.lean_off_n = 0;  // a shape whose lean sort overflowed keeps the fallback launches for the rest of ITS opening only (msm.hip lean_sort)
+    TRH_TRY(ipa_scratch_reserve(c, r.p, r.p.fold_list_words, s));
 
-    ctx().msm.lean_off_n = 0;  // a shape whose lean sort overflowed keeps the fallback launches for the rest of ITS opening only (msm.hip lean_sort)
-    // scratch kept in the context: a hipMalloc / hipFree pair per vector costs more than several rounds
-    DevBuf* sc = ctx().ipa;
-    DevBuf &b = sc[0], &sp = sc[1], &pp = sc[2], &wgt = sc[3], &lrsc = sc[4], &gwu = sc[5], &gwuz = sc[6], &pp2 = sc[7], &b2 = sc[8];
-    // A base set that holds g || w || u (n + 2 points) with fixed-base tables attached (trh_bases_precompute: Params are fixed for
-    // the life of a proving key) lets every MSM of the opening run in fixed-base mode: one bucket set instead of one per window,
-    // wide windows, no heavy top-window buckets and no Horner over windows on the host between two rounds.
-    const bool with_u = gw->n == n + 2;
-    const MsmFixedBase* fb = (with_u && gw->d_table) ? &gw->fb : nullptr;
-    // A set small enough for msm_small_kernel does not use its table: one launch + a host Horner beats the fixed-base pipeline's chain of ten
-    // launches (k = 10: 3.3 -> 2.1 ms per opening, k = 13: 5.4 -> 3.7); level 0 of the table is the set in the accumulation's record format
-    const void* small_z = nullptr;
-    if (fb && n + 2 <= msm_small_max_pairs() && ctx().window_override == 0) { small_z = fb->table; fb = nullptr; }
-    TRH_TRY(b.ensure(n * 32)); TRH_TRY(sp.ensure((n + 2) * 32)); TRH_TRY(pp.ensure(n * 32)); TRH_TRY(wgt.ensure(n * 32)); TRH_TRY(lrsc.ensure(2 * (n + 2) * 32));
-    TRH_TRY(pp2.ensure(n * 16 + 32)); TRH_TRY(b2.ensure(n * 16 + 32));  // the folded vectors have at most n / 2 entries
-    if (!with_u) { TRH_TRY(gwu.ensure((n + 2) * 64)); TRH_TRY(gwuz.ensure((n + 2) * ZREC)); }
-    FeMem x3m = stm(x3);
-    TRH_TRY((powers_t<SF>(b.p, n, (const u64*)&x3m, s)));
-    // s'(X) = s(X) - s(x3), then its commitment over g ‖ w with the blind appended: one pass copies s and forms its value at x3, one workgroup
-    // subtracts it from coefficient 0 and appends the blind (and the zero scalar of u) -- no host turn before the MSM
+    TRH_TRY(commit_s_prime(r, s_poly_dev, s_blind, x3));
     FeMem tmp;
-    unsigned eblocks = (unsigned)((n + 255) / 256);
-    if (eblocks > 512) eblocks = 512;
-    TRH_TRY(ctx().io.ensure((size_t)(2 * 512 + 2) * 32));
-    {
-        IpaConsts k0{};
-        hipLaunchKernelGGL((ipa_combine_eval_kernel<SF>), dim3(eblocks), dim3(256), 0, s, (const uint4*)s_poly_dev, (const uint4*)nullptr, (const uint4*)b.p, (uint4*)sp.p, n, k0,
-                           ctx().io.as<uint4>());
-        FeMem sbm = stm(s_blind);
-        IpaConsts kb{};
-        memcpy(&kb, &sbm, 32);
-        hipLaunchKernelGGL((ipa_fix_constant_kernel<SF>), dim3(1), dim3(256), 0, s, (const uint4*)ctx().io.as<uint4>(), eblocks, (uint4*)sp.p, n, 1, kb);
-        TRH_HIP_TRY(hipGetLastError());
-    }
-    u64 pt[12];
-    if (fb) {  // the scalar of u is zero: the full-range (table) path
-        MsmFlags dense;
-        dense.dense_hint = true;  // s(X) is uniformly random: no sparse classification
-        TRH_TRY(msm_enqueue(curve, gw->d_xy, gw->d_z, sp.p, n + 2, 1, n + 2, 1, s, fb, nullptr, dense));
-    } else if (small_z)
-    TRH_TRY(msm_enqueue(curve, gw->d_xy, small_z, sp.p, n + 2, 1, n + 2, 1, s));
-    else
-    TRH_TRY(msm_enqueue(curve, gw->d_xy, gw->d_z, sp.p, n + 1, 1, n + 1, 1, s));
-    TRH_TRY(msm_finish(curve, s, pt, 1));
-    tr->write_point(tr->ctx, pt);
     tr->squeeze_challenge_scalar(tr->ctx, (u64*)&tmp);
     const Fe<SF> xi = fe_load<SF>(tmp);
     tr->squeeze_challenge_scalar(tr->ctx, (u64*)&tmp);
-    const Fe<SF> z = fe_load<SF>(tmp);
-    // p'(X) = p(X) + xi s'(X) - v, v its value at x3: the same two launches
-    {
-        FeMem xim = stm(xi);
-        IpaConsts kx{};
-        memcpy(&kx, &xim, 32);
-        hipLaunchKernelGGL((ipa_combine_eval_kernel<SF>), dim3(eblocks), dim3(256), 0, s, (const uint4*)p_poly_dev, (const uint4*)sp.p, (const uint4*)b.p, (uint4*)pp.p, n, kx,
-                           ctx().io.as<uint4>());
-        IpaConsts k0{};
-        hipLaunchKernelGGL((ipa_fix_constant_kernel<SF>), dim3(1), dim3(256), 0, s, (const uint4*)ctx().io.as<uint4>(), eblocks, (uint4*)pp.p, n, 0, k0);
-        TRH_HIP_TRY(hipGetLastError());
-    }
-    Fe<SF> f = fe_add(fe_mul(s_blind, xi), p_blind);
-    // weights of the original generators inside the (virtual) folded ones; the bases of the round MSMs are
-    // g (n points) followed by w and u, so that [rand] W + [value z] U ride in the same MSM as the main sum
-    // (all ones at first: the front launch of round 0 takes them as such and round 1's writes them -- no fill)
-    const void* round_xy = gw->d_xy;
-    const void* round_z = nullptr;
-    if (!with_u) {
-        TRH_HIP_TRY(hipMemcpyAsync(gwu.p, gw->d_xy, (n + 1) * 64, hipMemcpyDeviceToDevice, s));
-        TRH_HIP_TRY(hipMemcpy((char*)gwu.p + (n + 1) * 64, u_xy, 64, hipMemcpyHostToDevice));
-        TRH_TRY(msm_convert_bases(curve, gwu.p, gwuz.p, n + 2, s));
-        round_xy = gwu.p; round_z = gwuz.p;
-    } else if (!fb) {
-        round_z = small_z ? small_z : gw->d_z;  // the handle's converted copy when it has one; otherwise the MSM converts per call
-    }
-    size_t stride = n + 2;
-    // Hybrid (round 6, ipafold.hip): the first r rounds run over the 2^k original bases with the folds as weights (a full-size fixed-base MSM each);
-    // then the generators are collapsed for real -- r folds at once from the table -- and the remaining k - r rounds are MSMs over m + 2 = 2^(k - r) + 2
-    // points, a fraction of a full-size round each.  Only worth it where a full-size round costs much more than a small one.
-    const uint32_t fold_at = ipa_fold_level(fb, k);
-    const MsmFixedBase* round_fb = fb;
-    size_t ncur = n;  // generators of the round MSMs
-    u64 u_hist[16 * 4];  // the challenges the collapse needs
+    r.z = fe_load<SF>(tmp);
+    TRH_TRY(form_p_prime(r, p_poly_dev, xi));
+    r.f = fe_add(fe_mul(s_blind, xi), p_blind);
+    // the generators' weights inside the (virtual) folded ones are all ones at first: the front launch of round 0 takes them as such and round 1's writes them -- no fill
+    TRH_TRY(bind_round_bases(r, u_xy));
+    r.p_cur = c.ipa.pp.p; r.b_cur = c.ipa.b.p;
+    r.p_nxt = c.ipa.pp2.p; r.b_nxt = c.ipa.b2.p;
+    r.u_prev = fe_one<SF>(); r.u_prev_inv = fe_one<SF>();
 
-    // the round MSMs are batches of two with half of the scalars zero: their time is the latency of the sort / reduction chain,
-    // which narrow windows shorten (measured: k = 18 -> c = 10 gives 24.4 ms against 26.7 at the table's 15; k = 14 -> 8)
     struct WindowGuard {
         int& slot; int saved;
         WindowGuard(int& s_, int v) : slot(s_), saved(s_) { if (!saved) slot = v; }
         ~WindowGuard() { slot = saved; }
-    } window_guard(ctx().window_override, (!fb && k >= 16 && k <= 18) ? (int)k - 8 : 0);  // k = 20: the table's 15 is better again (60 vs 68 ms)
+    } window_guard(c.window_override, r.p.round_window);
 
-    // per round three launches in front of the MSM (the previous round's folds applied on the fly + the scalar rows; both inner products; the tail
-    // scalars -- the round's constants travel as kernel arguments), the MSM, the transcript.  No host synchronisation before the MSM: the host
-    // never needs value_l / value_r.  (Round 5 had four launches here, the first version 14 small operations.)
-    FeMem zm = stm(z);
-    // TRH_TRACE bit 1: where the host's part of a round goes (averages over the rounds, microseconds, to stderr)
-    const bool ipa_trace = (opt().trace & 2) != 0;
-    double tr_acc[6] = {0, 0, 0, 0, 0, 0};
-    auto tnow = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    unsigned fblocks = (unsigned)((n + 255) / 256);
-    uint4* const partial = ctx().io.as<uint4>();
-    // p' and b live in ping-pong pairs from round 1 on (a round reads the vectors the previous one left and writes their folds to the other buffer)
-    void* p_cur = pp.p; void* b_cur = b.p;
-    void* p_nxt = pp2.p; void* b_nxt = b2.p;
-    Fe<SF> u_prev = fe_one<SF>(), u_prev_inv = fe_one<SF>();
     for (uint32_t j = 0; j < k; ++j) {
-        const double t_round0 = ipa_trace ? tnow() : 0;
-        const size_t half = (size_t)1 << (k - j - 1);
-        const u32 bit = k - j - 1;
-        Fe<SF> rnd[2];
-        rng(rng_ctx, (u64*)&tmp); rnd[0] = fe_load<SF>(tmp);
-        rng(rng_ctx, (u64*)&tmp); rnd[1] = fe_load<SF>(tmp);
-        if (fold_at && j == fold_at) {  // G'' || w || u from the table, after the challenges of rounds 0 .. r - 1; from here on the rounds are MSMs over m + 2 points
-            // (inline: on a stream of its own under the next full-size rounds the collapse gained nothing -- profiles/r06_ipa_fold_overlap_ab.txt)
-            const size_t m = (size_t)1 << (k - fold_at);
-            TRH_TRY(gwu.ensure((m + 2) * 64)); TRH_TRY(gwuz.ensure((m + 2) * ZREC));
-            TRH_TRY(ipa_fold_generators(curve, *fb, gw->n, k, fold_at, u_hist, gwu.p, gwuz.p, s));
-            TRH_HIP_TRY(hipMemcpyAsync((char*)gwu.p + m * 64, (const char*)gw->d_xy + n * 64, 2 * 64, hipMemcpyDeviceToDevice, s));
-            TRH_HIP_TRY(hipMemcpyAsync((char*)gwuz.p + m * ZREC, (const char*)fb->table + n * ZREC, 2 * ZREC, hipMemcpyDeviceToDevice, s));  // level 0 of the table = the bases
-            ncur = m; stride = m + 2; fblocks = (unsigned)((m + 255) / 256);
-            round_xy = gwu.p; round_z = gwuz.p; round_fb = nullptr;
-            ++ctx().ipa_collapses;
-        }
-        const int canon = (!round_fb && ncur + 2 <= msm_small_max_pairs() && ctx().window_override == 0) ? 1 : 0;  // this round's MSM is msm_small_kernel's
-        {
-            FeMem cst[2] = {stm(u_prev_inv), stm(u_prev)};
-            IpaConsts kc{};
-            memcpy(&kc, cst, sizeof(cst));
-            hipLaunchKernelGGL((ipa_round_front_kernel<SF>), dim3(fblocks), dim3(256), 0, s, (const uint4*)p_cur, (const uint4*)b_cur, (uint4*)p_nxt, (uint4*)b_nxt, (uint4*)wgt.p, (uint4*)lrsc.p,
-                               ncur, half, bit, stride, j == 0 ? 1 : 0, (j <= 1 || (fold_at && j - fold_at <= 1)) ? 1 : 0, canon, kc);
-            if (j > 0) { void* t = p_cur; p_cur = p_nxt; p_nxt = t; t = b_cur; b_cur = b_nxt; b_nxt = t; }
-            // value_l = <p'[half ..], b[.. half]>, value_r = <p'[.. half], b[half ..]> over the folded vectors, then the tail scalars [rand] W, [value z] U
-            unsigned blocks = (unsigned)((half + 255) / 256);
-            if (blocks > 512) blocks = 512;
-            hipLaunchKernelGGL((inner_product2_kernel<SF>), dim3(blocks, 2), dim3(256), 0, s, (const uint4*)((const char*)p_cur + half * 32), (const uint4*)b_cur, (const uint4*)p_cur,
-                               (const uint4*)((const char*)b_cur + half * 32), half, partial);
-            FeMem cst3[3] = {stm(rnd[0]), stm(rnd[1]), zm};
-            IpaConsts kt{};
-            memcpy(&kt, cst3, sizeof(cst3));
-            hipLaunchKernelGGL((ipa_round_tails_kernel<SF>), dim3(2), dim3(256), 0, s, partial, blocks, kt, (uint4*)lrsc.p, ncur, stride, canon);
-            TRH_HIP_TRY(hipGetLastError());
-        }
-        u64 lrb[24], lr[2][12];
-        MsmFlags dense;
-        dense.dense_hint = true;  // p' . w: full-size values on half the rows
-        TRH_TRY(msm_enqueue(curve, round_xy, round_z, lrsc.p, ncur + 2, 2, stride, canon ? 0 : 1, s, round_fb, nullptr, dense));
-        const double t_enq = ipa_trace ? tnow() : 0;
-        TRH_TRY(msm_finish(curve, s, lrb, 2));
-        const double t_fin = ipa_trace ? tnow() : 0;
-        memcpy(lr[0], lrb, 96); memcpy(lr[1], lrb + 12, 96);
-        tr->write_point(tr->ctx, lr[0]);
-        tr->write_point(tr->ctx, lr[1]);
-        tr->squeeze_challenge_scalar(tr->ctx, (u64*)&tmp);
-        const double t_tr = ipa_trace ? tnow() : 0;
-        const Fe<SF> u_j = fe_load<SF>(tmp);
-        if (fe_is_zero(u_j)) { set_error("ipa_create_proof: round %u challenge is zero (the Rust prover's u_j.invert().unwrap() panics here)", j); return TRH_EINVAL; }
-        // u_j^-1 on the host's 4 x 64-bit Montgomery code (hostcombine.h): the nine-limb form the device code uses costs the host three times as much
-        hostcombine::H uh;
-        memcpy(&uh, &tmp, 32);
-        const hostcombine::H uih = hostcombine::inv<SF>(uh);
-        FeMem uim;
-        memcpy(&uim, &uih, 32);
-        const Fe<SF> u_inv = fe_load<SF>(uim);
-        if (j < 16) memcpy(u_hist + 4 * j, &tmp, 32);
-        u_prev = u_j; u_prev_inv = u_inv;  // folded into the next round's front launch (or by the launch behind the loop)
-        f = fe_add(f, fe_add(fe_mul(rnd[0], u_inv), fe_mul(rnd[1], u_j)));
-        if (ipa_trace) {
-            const double t_end = tnow();
-            tr_acc[0] += t_enq - t_round0; tr_acc[1] += t_fin - t_enq; tr_acc[2] += t_tr - t_fin; tr_acc[3] += t_end - t_tr; tr_acc[4] += t_end - t_round0;
-        }
+        const double t_round0 = r.trace ? ipa_now() : 0;
+        if (r.p.fold_at && j == r.p.fold_at) TRH_TRY(collapse_generators(r));
+        TRH_TRY(enqueue_round(r, j));
+        TRH_TRY(finish_round(r, j, t_round0));
     }
-    if (k > 0) {  // the last round's fold: p'[0] += u^-1 p'[1] (b and the weights are not read again, the kernel folds them too)
-        FeMem cst[2] = {stm(u_prev_inv), stm(u_prev)};
-        IpaConsts kc{};
-        memcpy(&kc, cst, sizeof(cst));
-        hipLaunchKernelGGL((ipa_round_update_kernel<SF>), dim3((unsigned)((ncur + 255) / 256)), dim3(256), 0, s, (uint4*)p_cur, (uint4*)b_cur, (uint4*)wgt.p, ncur, (size_t)1, 0u, kc);
-        TRH_HIP_TRY(hipGetLastError());
-    }
-    if (ipa_trace)
-        fprintf(stderr, "[trh ipa] k = %u, per round (us): enqueue %.1f, wait for the MSM (sync + host combine) %.1f, transcript callbacks %.1f, inversion + update launch %.1f, round %.1f\n",
-                k, tr_acc[0] / k, tr_acc[1] / k, tr_acc[2] / k, tr_acc[3] / k, tr_acc[4] / k);
-    TRH_HIP_TRY(hipStreamSynchronize(s));
-    TRH_HIP_TRY(hipMemcpy(&tmp, p_cur, 32, hipMemcpyDeviceToHost));
-    FeMem fm = stm(f);
-    tr->write_scalar(tr->ctx, (const u64*)&tmp);
-    tr->write_scalar(tr->ctx, (const u64*)&fm);
-    if (out_c) memcpy(out_c, &tmp, 32);
-    if (out_f) memcpy(out_f, &fm, 32);
-    return TRH_OK;
+    return final_fold(r, out_c, out_f);
 }
 
 }  // namespace
 
+int ipa_scratch_reserve(Ctx& c, const hostplan::IpaPlan& p, size_t list_words, hipStream_t s) {
+    IpaScratch& sc = c.ipa;
+    TRH_TRY(sc.b.ensure(p.bytes.b)); TRH_TRY(sc.sp.ensure(p.bytes.sp)); TRH_TRY(sc.pp.ensure(p.bytes.pp)); TRH_TRY(sc.wgt.ensure(p.bytes.wgt)); TRH_TRY(sc.lrsc.ensure(p.bytes.lrsc));
+    TRH_TRY(sc.pp2.ensure(p.bytes.pp2)); TRH_TRY(sc.b2.ensure(p.bytes.b2));
+    TRH_TRY(sc.gwu.ensure(p.bytes.gwu)); TRH_TRY(sc.gwuz.ensure(p.bytes.gwuz));
+    TRH_TRY(c.io.ensure(p.bytes.io));
+    if (!p.fold_at) return TRH_OK;
+    TRH_TRY(sc.fold_buckets.ensure(p.bytes.fold_buckets));
+    TRH_TRY(sc.fold_lists.ensure(list_words * 4));
+    if (sc.fold_pinned_cap < list_words * 4) {
+        if (sc.fold_pinned) { TRH_HIP_TRY(hipStreamSynchronize(s)); (void)hipHostFree(sc.fold_pinned); sc.fold_pinned = nullptr; sc.fold_pinned_cap = 0; }
+        const size_t want = list_words * 4 + 4096;
+        TRH_HIP_TRY(hipHostMalloc(&sc.fold_pinned, want, hipHostMallocDefault));
+        sc.fold_pinned_cap = want;
+    }
+    return TRH_OK;
+}
+
 // what an opening over this base set allocates, at setup time (trh_bases_reserve): the first proof of a process then finds its vectors, the
 // collapse's buckets and the small MSM's landing area in place
 int ipa_reserve(int curve, const trh_bases* gw, uint32_t k) {
-    const size_t n = (size_t)1 << k;
     Ctx& c = ctx();
-    DevBuf* sc = c.ipa;
-    TRH_TRY(sc[0].ensure(n * 32)); TRH_TRY(sc[1].ensure((n + 2) * 32)); TRH_TRY(sc[2].ensure(n * 32)); TRH_TRY(sc[3].ensure(n * 32)); TRH_TRY(sc[4].ensure(2 * (n + 2) * 32));
-    TRH_TRY(sc[7].ensure(n * 16 + 32)); TRH_TRY(sc[8].ensure(n * 16 + 32));
-    TRH_TRY(c.io.ensure((size_t)(2 * 512 + 2) * 32));
-    const MsmFixedBase* fb = gw->d_table ? &gw->fb : nullptr;
-    const uint32_t fold_at = ipa_fold_level(fb, k);
-    if (!fold_at) return TRH_OK;
-    const size_t m = (size_t)1 << (k - fold_at);
-    TRH_TRY(sc[5].ensure((m + 2) * 64)); TRH_TRY(sc[6].ensure((m + 2) * ZREC));
-    TRH_TRY(ipa_fold_reserve(*fb, k, fold_at));
+    const hostplan::IpaPlan p = hostplan::ipa_plan(ipa_shape(gw, k));
+    TRH_TRY(ipa_scratch_reserve(c, p, p.fold_list_words, nullptr));
+    if (!p.fold_at) return TRH_OK;
     if (!c.helper && !c.helper_failed) {  // msm_finish's second Horner thread
         try { c.helper = new HostHelper(); } catch (...) { c.helper_failed = true; }
     }
+    const hostplan::IpaRound g = p.round(p.fold_at);  // the rounds behind the collapse
     MsmFlags reserve;
     reserve.reserve_only = true;
-    return msm_enqueue(curve, sc[5].p, sc[6].p, sc[4].p, m + 2, 2, m + 2, 1, nullptr, nullptr, nullptr, reserve);
+    return msm_enqueue(curve, c.ipa.gwu.p, c.ipa.gwuz.p, c.ipa.lrsc.p, g.gens + 2, 2, g.stride, 1, nullptr, nullptr, nullptr, reserve);
 }
 
 int field_powers_device(int field, void* out_dev, size_t n, const u64 x_mont[4], hipStream_t s) {
@@ -626,8 +658,6 @@ int trh_poly_eval_batch_dev(int field, const void* polys_dev, size_t n, size_t b
     if (!n) { memset(out, 0, batch * 32); return TRH_OK; }
     TRH_ENTER(stream);
     Range range("trh_poly_eval_batch_dev");
-    Ctx& c = ctx();
-    (void)c;
     return with_field(field, [&](auto f) { return eval_batch_t<decltype(f)>(polys_dev, n, batch, point, (hipStream_t)stream, out); });
 }
 
@@ -637,8 +667,6 @@ int trh_field_inner_product_dev(int field, const void* a_dev, const void* b_dev,
     if (!out || (n && (!a_dev || !b_dev))) { set_error("inner_product: null pointer"); return TRH_EINVAL; }
     TRH_ENTER(stream);
     Range range("trh_field_inner_product_dev");
-    Ctx& c = ctx();
-    (void)c;
     return with_field(field, [&](auto f) { return inner_product_t<decltype(f)>(a_dev, b_dev, n, (hipStream_t)stream, out); });
 }
 
@@ -649,8 +677,6 @@ int trh_field_axpy_dev(int field, void* y_dev, const void* x_dev, size_t n, cons
     if (!n) return TRH_OK;
     TRH_ENTER(stream);
     Range range("trh_field_axpy_dev");
-    Ctx& c = ctx();
-    (void)c;
     FeMem cm;
     memcpy(&cm, c_mont, 32);
     return with_field(field, [&](auto f) { return axpy_t<decltype(f)>(y_dev, x_dev, n, cm, (hipStream_t)stream); });
@@ -663,8 +689,6 @@ int trh_field_powers_dev(int field, void* out_dev, size_t n, const uint64_t x_mo
     if (!n) return TRH_OK;
     TRH_ENTER(stream);
     Range range("trh_field_powers_dev");
-    Ctx& c = ctx();
-    (void)c;
     return with_field(field, [&](auto f) { return powers_t<decltype(f)>(out_dev, n, x_mont, (hipStream_t)stream); });
 }
 
@@ -675,8 +699,6 @@ int trh_bases_fold_dev(int curve, void* g_lo_dev, const void* g_hi_dev, size_t h
     if (!half) return TRH_OK;
     TRH_ENTER(stream);
     Range range("trh_bases_fold_dev");
-    Ctx& c = ctx();
-    (void)c;
     return with_curve(curve, [&](auto cv) { return bases_fold_t<typename decltype(cv)::Scalar, typename decltype(cv)::Base>(g_lo_dev, g_hi_dev, half, u_mont, (hipStream_t)stream); });
 }
 

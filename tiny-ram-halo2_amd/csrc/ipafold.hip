@@ -22,6 +22,7 @@
 #include "devmem.h"
 #include "foldplan.h"
 #include "hostcombine.h"
+#include "hostplan.h"
 
 namespace trh {
 namespace {
@@ -182,28 +183,16 @@ __global__ void __launch_bounds__(64) ipa_fold_affine_kernel(const XYZZzMem* __r
     z[7] = make_uint4(0u, 0u, 0u, 0u);
 }
 
-// buckets (+ the m sums between the reduction and the inversion), the bucket lists and their pinned source
-int fold_buffers(Ctx& c, const MsmFixedBase& fb, uint32_t k, uint32_t r, size_t plan_words, hipStream_t s) {
-    const size_t m = (size_t)1 << (k - r);
-    const u32 nbk = (1u << ((fb.c + 1) / 2 - 1)) + (1u << (fb.c / 2 - 1));
-    TRH_TRY(c.ipa[9].ensure((size_t)(nbk + 1) * m * sizeof(XYZZzMem)));
-    TRH_TRY(c.ipa[10].ensure(plan_words * 4));
-    if (c.pinned_fold_cap < plan_words * 4) {
-        if (c.pinned_fold) { TRH_HIP_TRY(hipStreamSynchronize(s)); (void)hipHostFree(c.pinned_fold); c.pinned_fold = nullptr; c.pinned_fold_cap = 0; }
-        const size_t want = plan_words * 4 + 4096;
-        TRH_HIP_TRY(hipHostMalloc(&c.pinned_fold, want, hipHostMallocDefault));
-        c.pinned_fold_cap = want;
-    }
-    return TRH_OK;
-}
+static_assert(hostplan::RAW_POINT_BYTES == sizeof(XYZZzMem) && hostplan::ZREC_BYTES == ZREC, "hostplan.h sizes the collapse's buffers by these");
 
 template <class SF, class BF>
-int ipa_fold_t(const MsmFixedBase& fb, size_t row, uint32_t k, uint32_t r, const u64* u_mont, void* out_xy, void* out_z, hipStream_t s) {
+int ipa_fold_t(const MsmFixedBase& fb, size_t row, const hostplan::IpaPlan& p, const u64* u_mont, void* out_xy, void* out_z, hipStream_t s) {
     using hostcombine::H;
     Ctx& c = ctx();
-    const u32 log_m = k - r;
-    const size_t m = (size_t)1 << log_m;
-    const u32 w0 = (u32)(fb.c + 1) / 2, w1 = (u32)fb.c / 2;
+    const uint32_t r = p.fold_at;
+    const u32 log_m = p.k - r;
+    const size_t m = p.m;
+    const u32 w0 = p.fold_w0, w1 = p.fold_w1, nbk = p.fold_nbk;
     // s_t (Montgomery) by doubling the set of indices: bit (r - 1 - j) of t <-> u_j
     std::vector<H> sc((size_t)1 << r);
     sc[0] = hostcombine::consts<SF>().one;
@@ -216,22 +205,22 @@ int ipa_fold_t(const MsmFixedBase& fb, size_t row, uint32_t k, uint32_t r, const
     }
     const H one_plain = {{1, 0, 0, 0}};
     for (H& v : sc) v = hostcombine::mul<SF>(v, one_plain);  // out of the Montgomery form: canonical words
-    std::vector<u32> plan;
-    u32 nbk = 0;
-    if (foldplan::fold_plan(sc, fb.c, fb.W, w0, w1, plan, nbk) != foldplan::FOLD_PLAN_OK) {
+    std::vector<u32> lists;
+    u32 listed = 0;  // the buckets the lists were made for: the plan's (tests/native/hostplan_test.cpp holds the two rules together)
+    if (foldplan::fold_plan(sc, fb.c, fb.W, w0, w1, lists, listed) != foldplan::FOLD_PLAN_OK) {
         set_error("ipa fold: a fold scalar does not fit the table's %d windows of %d bits", fb.W, fb.c);
         return TRH_EINVAL;
     }
-    DevBuf& buckets = c.ipa[9];
-    DevBuf& dplan = c.ipa[10];
-    TRH_TRY(fold_buffers(c, fb, k, r, plan.size(), s));
-    XYZZzMem* const sums = (XYZZzMem*)buckets.p + (size_t)nbk * m;
+    TRH_TRY(ipa_scratch_reserve(c, p, lists.size(), s));
+    IpaScratch& sc_dev = c.ipa;
+    XYZZzMem* const buckets = sc_dev.fold_buckets.as<XYZZzMem>();
+    XYZZzMem* const sums = buckets + (size_t)nbk * m;
     // (the previous opening's copy out of this buffer completed before that opening returned: it ends with a stream synchronisation)
-    memcpy(c.pinned_fold, plan.data(), plan.size() * 4);
-    TRH_HIP_TRY(hipMemcpyAsync(dplan.p, c.pinned_fold, plan.size() * 4, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL((ipa_fold_accumulate_kernel<BF>), dim3((unsigned)(m / 256), nbk), dim3(256), 0, s, (const uint4*)fb.table, row, log_m, (const u32*)dplan.p, nbk,
-                       (XYZZzMem*)buckets.p);
-    hipLaunchKernelGGL((ipa_fold_reduce_kernel<BF>), dim3((unsigned)(m / 8)), dim3(256), 0, s, (const XYZZzMem*)buckets.p, log_m, w0, w1, sums);
+    memcpy(sc_dev.fold_pinned, lists.data(), lists.size() * 4);
+    TRH_HIP_TRY(hipMemcpyAsync(sc_dev.fold_lists.p, sc_dev.fold_pinned, lists.size() * 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL((ipa_fold_accumulate_kernel<BF>), dim3((unsigned)(m / 256), nbk), dim3(256), 0, s, (const uint4*)fb.table, row, log_m, sc_dev.fold_lists.as<const u32>(), nbk,
+                       buckets);
+    hipLaunchKernelGGL((ipa_fold_reduce_kernel<BF>), dim3((unsigned)(m / 8)), dim3(256), 0, s, (const XYZZzMem*)buckets, log_m, w0, w1, sums);
     hipLaunchKernelGGL((ipa_fold_affine_kernel<BF>), dim3((unsigned)((m + 63) / 64)), dim3(64), 0, s, (const XYZZzMem*)sums, m, (uint4*)out_xy, (uint4*)out_z);
     TRH_HIP_TRY(hipGetLastError());
     return TRH_OK;
@@ -239,23 +228,11 @@ int ipa_fold_t(const MsmFixedBase& fb, size_t row, uint32_t k, uint32_t r, const
 
 }  // namespace
 
-bool ipa_fold_supported(const MsmFixedBase& fb, uint32_t k, uint32_t r) {
-    // two sub-digits of 5 .. 9 bits per table window (sixteen slices of >= 1 bucket); t and the table level share an entry word; whole workgroups of generators
-    return fb.table && fb.c >= 10 && fb.c <= 18 && fb.W < 0x8000 && r >= 2 && r <= 10 && k >= r + 8;
-}
-
-// setup-time sizing of what ipa_fold_generators allocates (trh_bases_reserve over an opening's base set)
-int ipa_fold_reserve(const MsmFixedBase& fb, uint32_t k, uint32_t r) {
-    if (!ipa_fold_supported(fb, k, r)) return TRH_OK;
-    const u32 nbk = (1u << ((fb.c + 1) / 2 - 1)) + (1u << (fb.c / 2 - 1));
-    return fold_buffers(ctx(), fb, k, r, (size_t)nbk + 1 + ((size_t)2 << r) * fb.W, nullptr);
-}
-
 // G''[i] (i < 2^(k - r)) from the table of a base set with `row` points per level, after the r challenges u_mont (Montgomery words, round order):
 // out_xy = m affine points (64-byte records), out_z = the same in the accumulation's 128-byte form.  Enqueued on s; the caller holds the context.
-int ipa_fold_generators(int curve, const MsmFixedBase& fb, size_t row, uint32_t k, uint32_t r, const u64* u_mont, void* out_xy, void* out_z, hipStream_t s) {
-    if (!ipa_fold_supported(fb, k, r)) { set_error("ipa fold: unsupported shape (table window %d, k = %u, r = %u)", fb.c, k, r); return TRH_EINVAL; }
-    return with_curve(curve, [&](auto cv) { return ipa_fold_t<typename decltype(cv)::Scalar, typename decltype(cv)::Base>(fb, row, k, r, u_mont, out_xy, out_z, s); });
+int ipa_fold_generators(int curve, const MsmFixedBase& fb, size_t row, const hostplan::IpaPlan& p, const u64* u_mont, void* out_xy, void* out_z, hipStream_t s) {
+    if (!hostplan::ipa_fold_supported(fb.table != nullptr, fb.c, fb.W, p.k, p.fold_at)) { set_error("ipa fold: unsupported shape (table window %d, k = %u, r = %u)", fb.c, p.k, p.fold_at); return TRH_EINVAL; }
+    return with_curve(curve, [&](auto cv) { return ipa_fold_t<typename decltype(cv)::Scalar, typename decltype(cv)::Base>(fb, row, p, u_mont, out_xy, out_z, s); });
 }
 
 }  // namespace trh
@@ -273,7 +250,7 @@ int trh_ipa_collapse_generators_dev(trh_bases_t bases, uint32_t k, uint32_t r, c
     TRH_ENTER(stream);
     Range range("trh_ipa_collapse_generators_dev");
     if (bases->owner && bases->owner->device != ctx().device) { set_error("ipa_collapse_generators: the base set lives on another device than the calling context"); return TRH_EINVAL; }
-    TRH_TRY(ipa_fold_generators(bases->curve, bases->fb, bases->n, k, r, (const u64*)u_mont, out_xy_dev, out_rec_dev, (hipStream_t)stream));
+    TRH_TRY(ipa_fold_generators(bases->curve, bases->fb, bases->n, hostplan::ipa_collapse_plan(bases->fb.c, bases->fb.W, k, r), (const u64*)u_mont, out_xy_dev, out_rec_dev, (hipStream_t)stream));
     // the bucket lists go up from ONE pinned buffer, which the next collapse overwrites: like an opening, the call ends with the stream drained
     TRH_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return TRH_OK;
