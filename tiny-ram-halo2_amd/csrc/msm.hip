@@ -46,56 +46,100 @@ constexpr u32 SIGN_BIT = 0x80000000u;
 //    (bucket 0 = nothing to add) and a histogram over level-1 bins
 //    bin = (bucket - 1) >> k2, accumulated in LDS and flushed once per workgroup.
 // ---------------------------------------------------------------------------------------
-template <class SF>
-__global__ void __launch_bounds__(256) msm_recode_kernel(const uint4* __restrict__ scalars, size_t n, int mont, int c, int W,
-                                                         u32* __restrict__ digits, u32* __restrict__ bin_counts, int k2, u32 nbins, int use_lds, size_t sstride,
-                                                         int one_row /* fixed-base mode: all windows share one histogram */,
+//    The launch's mode is compiled in: C = window bits (15, 16, 17: every digit is cut from the one or two words that hold it, the window loop
+//    is straight-line; 0: any width, the value is shifted window by window), ONE_ROW / USE_LDS / FLAGS as the arguments of the same name
+//    were.  The digit and histogram addresses advance by n and nbins per window, and the next scalar of the grid-stride loop is in flight
+//    while the current one is recoded.  2^24 pairs, c = 17: 700 -> 444 VALU instructions per scalar and wave (SQ_INSTS_VALU), 421 -> 292 us
+//    against 1.5 GB / 6.0 TB/s = 250 us for its bytes (NOTEBOOK round 13, profiles/r08_*).
+constexpr int RECODE_THREADS_MAX = 1024;
+template <class SF, int C, bool ONE_ROW /* fixed-base mode: all windows share one histogram */, bool USE_LDS,
+          bool FLAGS /* fixed-base mode: tile_flags[item][tile] = 1 when the partition tile holds an entry */>
+__global__ void __launch_bounds__(RECODE_THREADS_MAX) msm_recode_kernel(const uint4* __restrict__ scalars, size_t n, int mont, int c_arg, int W,
+                                                         u32* __restrict__ digits, u32* __restrict__ bin_counts, int k2, u32 nbins, size_t sstride,
                                                          const uint4* __restrict__ tails /* or null: scalar n - 1 of item z is tails[z] (the commitment blind) */,
-                                                         unsigned char* __restrict__ tile_flags /* or null; fixed-base mode: [item][tile] = 1 when the partition tile holds an entry */,
-                                                         u32 tile_log, u32 tiles) {
+                                                         unsigned char* __restrict__ tile_flags, u32 tile_log, u32 tiles) {
     const size_t z = blockIdx.z;  // batch item
-    const u32 rows = one_row ? 1u : (u32)W;
+    const u32 rows = ONE_ROW ? 1u : (u32)W;
     scalars += z * sstride * 2; digits += z * (size_t)W * n; bin_counts += z * (size_t)rows * nbins;
-    extern __shared__ u32 lhist[];  // rows * nbins counters when use_lds
+    extern __shared__ u32 lhist[];  // rows * nbins counters when USE_LDS
     const u32 total = rows * nbins;
-    if (use_lds) {
+    if (USE_LDS) {
         for (u32 k = threadIdx.x; k < total; k += blockDim.x) lhist[k] = 0;
         __syncthreads();
     }
+    const int c = C ? C : c_arg;
     const u32 mask = (1u << c) - 1u, half = 1u << (c - 1);
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
+    if (i < n) {
         const uint4* src = (tails && i == n - 1) ? tails + 2 * z : scalars + 2 * i;
-        uint4 lo = src[0], hi = src[1];
+        lo = src[0]; hi = src[1];
+        // the first scalar is waited for here: with its load still counted as in flight at the loop's head, the wait for it there (all but the
+        // two loads just issued) would also wait for the sixteen digit stores of the turn before, every turn.  It only steers where the
+        // compiler puts its waits; to check it after a compiler change, build this file to assembly (-S --cuda-device-only) and look at
+        // msm_recode_kernel<Fq, 17, false, true, false>: the grid-stride loop must hold ONE s_waitcnt vmcnt, vmcnt(16) in front of the copy
+        // of the next scalar at its end, and none between the two global_load_dwordx4 at its head and the first digit's store
+        // (without the statement there is an s_waitcnt vmcnt(2) behind those loads; profiles/r08_recode_isa.md)
+        asm volatile("" : "+v"(lo.x), "+v"(lo.y), "+v"(lo.z), "+v"(lo.w), "+v"(hi.x), "+v"(hi.y), "+v"(hi.z), "+v"(hi.w));
+    }
+    while (i < n) {
         u32 w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        {   // the next scalar (the last turn reads its own again: a conditional load would merge old and new registers)
+            const size_t nx = i + stride < n ? i + stride : i;
+            const uint4* src = (tails && nx == n - 1) ? tails + 2 * z : scalars + 2 * nx;
+            lo = src[0]; hi = src[1];
+        }
         if (mont) fe_store(fe_from_mont(fe_load<SF>(w)), w);
         u32 carry = 0;
-        for (int j = 0; j < W; ++j) {
-            u32 raw = (w[0] & mask) + carry;
-            // shift the 256-bit value right by c (static register indexing)
-#pragma unroll
-            for (int k = 0; k < 7; ++k) w[k] = (w[k] >> c) | (w[k + 1] << (32 - c));
-            w[7] >>= c;
+        u32* dg = digits + i;  // digits[j][i], one window further after every digit
+        u32 row = 0;           // first counter of the window's histogram row
+        size_t slot = i;
+        auto emit = [&](u32 raw) {
+            raw += carry;
             u32 bucket, sign = 0;
             if (raw > half) { bucket = (1u << c) - raw; carry = 1; sign = SIGN_BIT; }  // digit raw - 2^c
             else { bucket = raw; carry = 0; }
-            digits[(size_t)j * n + i] = bucket ? (bucket | sign) : 0u;
-            if (tile_flags) {  // witness columns leave most tiles of the flat W x n digit space empty: the partition skips those
+            *dg = bucket ? (bucket | sign) : 0u;
+            if (FLAGS) {  // witness columns leave most tiles of the flat W x n digit space empty: the partition skips those
                 // one store per wave and window, no load: the lowest lane with an entry marks its tile; a lane within the first 64 slots of a
                 // tile marks it too (the wave's lowest entry may lie in the tile before)
                 const unsigned long long nz = __ballot(bucket != 0);
-                const size_t slot = (size_t)j * n + i;
                 const u32 lane = threadIdx.x & 63u;
                 if (bucket && ((nz & ((1ull << lane) - 1ull)) == 0ull || (slot & (((size_t)1 << tile_log) - 1)) < 64))
                     tile_flags[z * tiles + (slot >> tile_log)] = 1;
+                slot += n;
             }
             if (bucket) {
-                const u32 bin = (bucket - 1u) >> k2, row = one_row ? 0u : (u32)j;
-                if (use_lds) atomicAdd(&lhist[row * nbins + bin], 1u);
-                else atomicAdd(&bin_counts[(size_t)row * nbins + bin], 1u);
+                const u32 bin = (bucket - 1u) >> k2;
+                if (USE_LDS) atomicAdd(&lhist[row + bin], 1u);
+                else atomicAdd(&bin_counts[(size_t)row + bin], 1u);
+            }
+            dg += n;
+            if (!ONE_ROW) row += nbins;
+        };
+        if constexpr (C != 0) {
+            constexpr int WC = 255 / C + 1;  // num_windows(C): the launch checks W against it
+#pragma unroll
+            for (int j = 0; j < WC; ++j) {
+                // bits [j C, j C + C) lie in word k from bit s on and, past its end, in word k + 1; beyond bit 255 the value is zero
+                const int b = j * C, k = b >> 5, s = b & 31;
+                const u32 a0 = k < 8 ? w[k < 8 ? k : 7] : 0u, a1 = (s + C > 32 && k + 1 < 8) ? w[k + 1 < 8 ? k + 1 : 7] : 0u;
+                emit((s ? (a0 >> s) | (a1 << ((32 - s) & 31)) : a0) & mask);
+            }
+        } else {
+            for (int j = 0; j < W; ++j) {
+                const u32 raw = w[0] & mask;
+                // shift the 256-bit value right by c (static register indexing)
+#pragma unroll
+                for (int k = 0; k < 7; ++k) w[k] = (w[k] >> c) | (w[k + 1] << (32 - c));
+                w[7] >>= c;
+                emit(raw);
             }
         }
+        i += stride;
     }
-    if (use_lds) {
+    if (USE_LDS) {
         __syncthreads();
         for (u32 k = threadIdx.x; k < total; k += blockDim.x) {
             const u32 v = lhist[k];
@@ -1560,6 +1604,27 @@ int reserve_scratch(const MsmRun& r) {
     return TRH_OK;
 }
 
+template <class SF, int C, bool FB, bool USE_LDS>
+void launch_recode_mode(const MsmRun& r, const MsmChunk& ch, unsigned gb, const uint4* sc) {
+    const hostplan::MsmPlan& p = r.p; MsmLane& L = *r.L;
+    // a full grid (2048 x 256 threads, from 2^19 pairs) with the histogram in the LDS runs as 512 workgroups of 1024: the same threads and the same
+    // scalars per thread, but at c = 17 the 64 KB histogram leaves room for two workgroups per CU -- 8 waves instead of 32 -- and every
+    // workgroup flushes its histogram with one global atomic per counter
+    unsigned threads = 256;
+    if (USE_LDS && gb == 2048) { threads = RECODE_THREADS_MAX; gb = 2048 * 256 / RECODE_THREADS_MAX; }
+    hipLaunchKernelGGL((msm_recode_kernel<SF, C, FB, USE_LDS, FB>), dim3(gb, 1, ch.nb), dim3(threads), USE_LDS ? p.recode_lds : 0, r.a.s, sc, p.n, r.a.mont, p.c, p.W,
+                       L.digits.as<u32>(), L.counts.as<u32>(), p.k2, p.nbins, r.a.stride,
+                       r.a.tails_dev ? (const uint4*)r.a.tails_dev + 2 * ch.b0 : nullptr, r.tile_flags, 14u, p.part_tiles);
+}
+// fixed-base mode (one histogram row and tile flags: r.tile_flags is set exactly then; hostplan gives such a plan Ws = 1 and at most 2^11 bins,
+// so recode_use_lds always holds and there is no form without the LDS) or one row per window, in the LDS where the rows fit
+template <class SF, int C>
+void launch_recode(const MsmRun& r, const MsmChunk& ch, unsigned gb, const uint4* sc) {
+    if (r.p.fb) launch_recode_mode<SF, C, true, true>(r, ch, gb, sc);
+    else if (r.p.recode_use_lds) launch_recode_mode<SF, C, false, true>(r, ch, gb, sc);
+    else launch_recode_mode<SF, C, false, false>(r, ch, gb, sc);
+}
+
 template <class SF>
 int stage_recode(const MsmRun& r, const MsmChunk& ch) {
     const hostplan::MsmPlan& p = r.p; MsmLane& L = *r.L; hipStream_t s = r.a.s;
@@ -1584,9 +1649,11 @@ int stage_recode(const MsmRun& r, const MsmChunk& ch) {
     const uint4* sc = (const uint4*)((const char*)r.a.scalars_dev + ch.b0 * r.a.stride * 32);
     unsigned gb = (unsigned)((p.n + 255) / 256);
     if (gb > 2048) gb = 2048;
-    hipLaunchKernelGGL((msm_recode_kernel<SF>), dim3(gb, 1, ch.nb), dim3(256), p.recode_use_lds ? p.recode_lds : 0, s, sc, p.n, r.a.mont, p.c, p.W,
-                       L.digits.as<u32>(), L.counts.as<u32>(), p.k2, p.nbins, p.recode_use_lds, r.a.stride, p.fb ? 1 : 0,
-                       r.a.tails_dev ? (const uint4*)r.a.tails_dev + 2 * ch.b0 : nullptr, r.tile_flags, 14u, p.part_tiles);
+    // the window widths the large shapes run at (hostplan::choose_window_bits from 2^18 pairs) have a straight-line form
+    if (p.c == 17 && p.W == num_windows(17)) launch_recode<SF, 17>(r, ch, gb, sc);
+    else if (p.c == 16 && p.W == num_windows(16)) launch_recode<SF, 16>(r, ch, gb, sc);
+    else if (p.c == 15 && p.W == num_windows(15)) launch_recode<SF, 15>(r, ch, gb, sc);
+    else launch_recode<SF, 0>(r, ch, gb, sc);
     static_assert(PART_TILE == 1 << 14, "tile_log of msm_recode_kernel");
     return TRH_OK;
 }
