@@ -3,6 +3,10 @@ arithmetic, evaluate_expression, ipa_verify_proof): it reads the recorded proof 
 0.2.0 (plonk/verifier.rs, poly/multiopen/verifier.rs, poly/commitment/verifier.rs, as recalled) itself.  It imports neither the package's plonk
 nor its multiopen module; what it shares with them is the protocol.
 
+The group work -- sums of scalar * point, and the opening's final equation -- has a second implementation over the C++ oracle (verify's
+group="cpp": cpu_ref.best_multiexp, common.ipa_verify_fast) for 2^10 rows and more, where the Python one would take minutes; everything else
+is the same integers for both.  tests/test_plonk_model.py holds the two against each other.
+
 A proof is the list of items a Writer recorded: ("P", affine point or None) and ("S", canonical integer), in the order they were written.
 Writer / Reader speak limbs (the device side's interface), ModelReader speaks integers; all three absorb the same bytes and so squeeze the same
 challenges, which they keep in `squeezes`.
@@ -257,14 +261,73 @@ def combine(cv, terms):
     return acc
 
 
-def verify(curve, k, g, g_lagrange, w, u, system, fixed_commitments, sigma_commitments, transcript_repr, instances, items):
-    """-> (accepted, squeezes).  g, g_lagrange: lists of n affine points; w, u: points; the commitments of the key as affine points; instances:
-    one list of integers per instance column; items: the recorded proof"""
+# ---- the group work of the verifier: two operations, two implementations -------------------------------------------------------------------
+class PythonGroup:
+    """points are the oracle's affine tuples (None: the identity), the arithmetic is oracle/pasta.py's Python integers: 7 ms for a scalar
+    multiplication, so for 2^5 rows"""
+
+    def __init__(self, curve: str):
+        self.curve, self.cv = curve, o.CURVES[curve]
+
+    def lift(self, pt):
+        """a proof item's point (affine tuple) in this group's form"""
+        return pt
+
+    def affine(self, pt):
+        """-> the affine tuple the transcript absorbs"""
+        return pt
+
+    def combine(self, terms):
+        """sum of scalar * point over (scalar, point) terms"""
+        return combine(self.cv, terms)
+
+    def opening_holds(self, k, g, w, u, commitment, x3, v, s_commitment, xi, z, rounds, challenges, c, f):
+        """the final equation of the opening (poly/commitment/verifier.rs)"""
+        return o.ipa_verify_proof(self.cv, k, g, w, u, commitment, x3, v, s_commitment, xi, z, rounds, challenges, c, f)
+
+
+class CppGroup:
+    """points are 8-limb affine rows (all zero: the identity) as the device hands them out, so g and g_lagrange stay the (n, 8) arrays they
+    were downloaded as; the arithmetic is the C++ oracle's (cpu_ref.best_multiexp, common.ipa_verify_fast): 2^14 pairs in a tenth of a second"""
+
+    def __init__(self, curve: str):
+        self.curve, self.cv = curve, o.CURVES[curve]
+
+    def lift(self, pt):
+        return np.array(self.cv.affine_limbs(pt), dtype=np.uint64)
+
+    def affine(self, pt):
+        return self.cv.affine_from_limbs([int(v) for v in np.asarray(pt).reshape(8)])
+
+    def combine(self, terms):
+        import cpu_ref
+        f = self.cv.scalar
+        scalars = np.array([f.limbs(s % f.m) for s, _ in terms], dtype=np.uint64)
+        points = np.stack([np.asarray(pt, dtype=np.uint64).reshape(8) for _, pt in terms])
+        return cpu_ref.to_affine(self.curve, cpu_ref.best_multiexp(self.curve, scalars, points, threads=4))
+
+    def opening_holds(self, k, g, w, u, commitment, x3, v, s_commitment, xi, z, rounds, challenges, c, f):
+        from common import ipa_verify_fast
+        return ipa_verify_fast(self.curve, k, np.asarray(g, dtype=np.uint64).reshape(1 << k, 8), w, u, commitment, x3, v, s_commitment, xi, z, rounds, challenges, c, f)
+
+
+GROUPS = {"python": PythonGroup, "cpp": CppGroup}
+REFUSALS = ("instance values", "vanishing identity", "transcript", "opening")
+
+
+def verify(curve, k, g, g_lagrange, w, u, system, fixed_commitments, sigma_commitments, transcript_repr, instances, items, group="python"):
+    """-> (accepted, squeezes, refused): refused is None or the one of REFUSALS that names the check which said no -- too many instance values,
+    the vanishing identity at x, a transcript that the proof does not exhaust, the opening.  g, g_lagrange: n points; w, u: points; the
+    commitments of the key: all in the form of `group` (affine tuples for "python", 8-limb rows for "cpp"); instances: one list of integers
+    per instance column; items: the recorded proof.  Only the sums of scalar * point and the opening's final equation go through the group;
+    the transcript, the vanishing identity, the intermediate sets and the interpolation are integers here for both."""
+    grp = GROUPS[group](curve)
     cv = o.CURVES[curve]
     f = cv.scalar
     m, n = f.m, 1 << k
     omega = f.omega(k)
     tr = ModelReader(curve, items)
+    read_point = lambda: grp.lift(tr.read_point())  # noqa: E731
     bf, sets, chunk = system.blinding_factors(), system.n_sets(), system.chunk_len()
     usable, last = n - (bf + 1), -(bf + 1)
     n_lookups, n_perm, pieces_count = len(system.lookups), len(system.permutation_columns), system.degree() - 1
@@ -272,24 +335,24 @@ def verify(curve, k, g, g_lagrange, w, u, system, fixed_commitments, sigma_commi
     tr.common_scalar(transcript_repr)
     for i, values in enumerate(instances):
         if len(values) > usable:
-            return False, tr.squeezes
-        pt = combine(cv, [(1, w)] + [(v, g_lagrange[row]) for row, v in enumerate(values)])  # commit_lagrange with Blind::default() = 1
-        tr.common_point(pt)
+            return False, tr.squeezes, REFUSALS[0]
+        pt = grp.combine([(1, w)] + [(v, g_lagrange[row]) for row, v in enumerate(values)])  # commit_lagrange with Blind::default() = 1
+        tr.common_point(grp.affine(pt))
         com[(("instance", i))] = [(1, pt)]
     for i in range(system.num_advice):
-        com[("advice", i)] = [(1, tr.read_point())]
+        com[("advice", i)] = [(1, read_point())]
     theta = tr.squeeze_challenge_scalar()
     for l in range(n_lookups):
-        com[("A'", l)] = [(1, tr.read_point())]
-        com[("S'", l)] = [(1, tr.read_point())]
+        com[("A'", l)] = [(1, read_point())]
+        com[("S'", l)] = [(1, read_point())]
     beta, gamma = tr.squeeze_challenge_scalar(), tr.squeeze_challenge_scalar()
     for s in range(sets):
-        com[("Zp", s)] = [(1, tr.read_point())]
+        com[("Zp", s)] = [(1, read_point())]
     for l in range(n_lookups):
-        com[("Zl", l)] = [(1, tr.read_point())]
-    com["random"] = [(1, tr.read_point())]
+        com[("Zl", l)] = [(1, read_point())]
+    com["random"] = [(1, read_point())]
     y = tr.squeeze_challenge_scalar()
-    h_pieces = [tr.read_point() for _ in range(pieces_count)]
+    h_pieces = [read_point() for _ in range(pieces_count)]
     x = tr.squeeze_challenge_scalar()
     xn = pow(x, n, m)
     com["h"] = [(pow(xn, i, m), pt) for i, pt in enumerate(h_pieces)]
@@ -350,7 +413,7 @@ def verify(curve, k, g, g_lagrange, w, u, system, fixed_commitments, sigma_commi
     for e in exprs:
         folded = (folded * y + e) % m
     if (folded - h_eval * (xn - 1)) % m:
-        return False, tr.squeezes
+        return False, tr.squeezes, REFUSALS[1]
 
     # the queries, in the prover's order
     rot = lambda r: x * pow(omega, r % n, m) % m  # noqa: E731
@@ -376,7 +439,7 @@ def verify(curve, k, g, g_lagrange, w, u, system, fixed_commitments, sigma_commi
     for key, s in members:
         q_com[s] = [(c * x1 % m, pt) for c, pt in q_com[s]] + com[key]
         q_evals_claimed[s] = [(acc * x1 + claimed[(key, p)]) % m for acc, p in zip(q_evals_claimed[s], point_sets[s])]
-    q_prime = tr.read_point()
+    q_prime = read_point()
     x3 = tr.squeeze_challenge_scalar()
     q_evals = [tr.read_scalar() for _ in point_sets]
     expected = 0
@@ -390,14 +453,14 @@ def verify(curve, k, g, g_lagrange, w, u, system, fixed_commitments, sigma_commi
     for terms, q_eval in zip(q_com, q_evals):
         final = [(c * x4 % m, pt) for c, pt in final] + terms
         v = (v * x4 + q_eval) % m
-    s_commitment = tr.read_point()
+    s_commitment = read_point()
     xi, z = tr.squeeze_challenge_scalar(), tr.squeeze_challenge_scalar()
     rounds, challenges = [], []
     for _ in range(k):
-        rounds.append((tr.read_point(), tr.read_point()))
+        rounds.append((read_point(), read_point()))
         challenges.append(tr.squeeze_challenge_scalar())
     c, f_ = tr.read_scalar(), tr.read_scalar()
     if not tr.finished():
-        return False, tr.squeezes
-    ok = o.ipa_verify_proof(cv, k, g, w, u, combine(cv, final), x3, v, s_commitment, xi, z, rounds, challenges, c, f_)
-    return ok, tr.squeezes
+        return False, tr.squeezes, REFUSALS[2]
+    ok = grp.opening_holds(k, g, w, u, grp.combine(final), x3, v, s_commitment, xi, z, rounds, challenges, c, f_)
+    return ok, tr.squeezes, None if ok else REFUSALS[3]

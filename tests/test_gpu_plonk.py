@@ -2,8 +2,13 @@
 _should_fail twin, judged by two verifiers: the package's own (plonk.verify_proof + single_verify, group work on the device) and
 tests/plonk_model.py (Python integers over the oracle, written without the package's plonk / multiopen modules).
 
-Circuits (tests/plonk_circuits.py), k = 5:  A on Pallas -- three permutation sets, copies across advice and instance cells, gates with
+Circuits (tests/plonk_circuits.py):  A on Pallas -- three permutation sets, copies across advice and instance cells, gates with
 Rotation(+1) at the last usable row and Rotation(-1), a one-column and a two-column lookup;  B on Vesta -- the logic chip.
+
+Every test of this file runs at k = 5 (32 rows, 26 usable): one workgroup per launch, one block per scan, msm_small_kernel for every MSM, an
+opening without the generator collapse.  That is the size for what does not depend on n -- the exhaustive tamper sweep, the smallest shapes,
+the integer model's own group arithmetic.  tests/test_gpu_plonk_sizes.py takes the same circuits, through the Setup of this file, to
+k = 10, 13 and 14, where the kernels of the chain leave their first level.
 
   honest          both verifiers accept and squeeze the same challenges; ipa.batch_verify over two proofs accepts
   should_fail     an instance value changed at verification only: both refuse
@@ -43,44 +48,54 @@ def to_dev(field, columns):
 
 
 class Setup:
-    """one circuit with its keys, a satisfying witness, and the parameters as the model wants them"""
+    """one circuit at 2^k rows with its keys, a satisfying witness, and the parameters as the model wants them: affine tuples for its Python
+    group (the default, for k = 5), the downloaded limb rows for group="cpp".  `params`: Params.new(curve, k) made elsewhere, to share them"""
 
-    def __init__(self, name):
-        self.name, self.curve = name, {**CASES, **SMALL}[name]
+    def __init__(self, name, k=K, group="python", params=None):
+        self.name, self.curve, self.k, self.group = name, {**CASES, **SMALL}[name], k, group
         self.cv = o.CURVES[self.curve]
         self.field = api.SCALAR_FIELD[self.curve]
-        self.params = poly.Params.new(self.curve, K)
-        n = 1 << K
+        self.params = params if params is not None else poly.Params.new(self.curve, k)
+        assert (self.params.curve, self.params.k) == (self.curve, k)
+        n = 1 << k
         if name == "A":
             self.circuit = pc.circuit_a(self.field)
-            self.witness = pc.WitnessA(self.field)
+            self.witness = pc.WitnessA(self.field, k)
             self.advice, self.fixed, self.copies, self.instances = self.witness.advice, self.witness.fixed, self.witness.copies, [self.witness.instance]
         elif name == "G":
             self.circuit = pc.circuit_gates_only(self.field)
-            self.advice, self.fixed = pc.witness_gates_only(self.field)
+            self.advice, self.fixed = pc.witness_gates_only(self.field, k)
             self.copies, self.instances = [], []
         elif name == "P":
             self.circuit = pc.circuit_copies_only(self.field)
-            self.advice, self.copies = pc.witness_copies_only(self.field)
+            self.advice, self.copies = pc.witness_copies_only(self.field, k)
             self.fixed, self.instances = [], []
         else:
-            from test_gpu_logic_chip import ADV, witness
-            assert ADV == pc.ADV_B
             self.circuit = pc.circuit_b(self.field)
-            cols, s_table, table = witness(n, 20, 0x10B)
-            self.advice, self.fixed, self.copies, self.instances = [cols[name_] for name_ in ADV], [s_table, table], [], []
-            self.names = ADV
+            self.advice, self.fixed = pc.witness_b(self.field, k, used=20 if k == K else None)
+            self.copies, self.instances = [], []
+            self.names = pc.ADV_B
         self.cs = self.circuit.system()
         self.vk, self.pk = plonk.keygen(self.params, self.cs, to_dev(self.field, self.fixed) if self.fixed else None, self.copies)
         g, gl = self.params._g.download(), self.params._g_lagrange.download()
-        pts = lambda rows: [self.cv.affine_from_limbs(r) for r in rows]  # noqa: E731
-        self.g, self.g_lagrange, self.w = pts(g[:n]), pts(gl[:n]), self.cv.affine_from_limbs(g[n])
-        self.u = self.cv.affine_from_limbs(np.asarray(self.params.u, dtype=np.uint64).reshape(8))
+        # the model's points: rows of limbs as they are for the C++ group, affine tuples for the Python one
+        self.pts = (lambda rows: np.asarray(rows, dtype=np.uint64).reshape(-1, 8)) if group == "cpp" else (lambda rows: [self.cv.affine_from_limbs(r) for r in rows])
+        self.g, self.g_lagrange, self.w = self.pts(g[:n]), self.pts(gl[:n]), self.pts(g[n:n + 1])[0]
+        self.u = self.pts(np.asarray(self.params.u, dtype=np.uint64).reshape(1, 8))[0]
         self.model = self.circuit.model()
+        self._honest_advice = None
+
+    def honest_advice(self):
+        """the satisfying witness on the device, sent there once; create_proof works on a copy"""
+        if self._honest_advice is None:
+            self._honest_advice = to_dev(self.field, self.advice)
+        return self._honest_advice
 
     def prove(self, advice=None, seed=7, layout="blocks", strict_lookups=True):
+        """advice: lists of integers or a device tensor; None: the honest witness"""
         tr = pm.Writer(self.curve)
-        plonk.create_proof(self.params, self.pk, self.instances, to_dev(self.field, advice or self.advice), api.Rng(bytes([seed]) * 32), tr,
+        advice = self.honest_advice() if advice is None else advice if torch.is_tensor(advice) else to_dev(self.field, advice)
+        plonk.create_proof(self.params, self.pk, self.instances, advice, api.Rng(bytes([seed]) * 32), tr,
                            layout=layout, strict_lookups=strict_lookups)
         return tr.items, tr.squeezes
 
@@ -97,9 +112,10 @@ class Setup:
         return g is not None and tr.finished() and plonk.single_verify(self.params, g)
 
     def model_verify(self, items, instances=None):
-        return pm.verify(self.curve, K, self.g, self.g_lagrange, self.w, self.u, self.model, [self.cv.affine_from_limbs(r) for r in self.vk.fixed_commitments],
-                         [self.cv.affine_from_limbs(r) for r in self.vk.sigma_commitments], self.vk.transcript_repr,
-                         self.instances if instances is None else instances, items)
+        """-> (accepted, squeezes, the refusing check or None)"""
+        return pm.verify(self.curve, self.k, self.g, self.g_lagrange, self.w, self.u, self.model, self.pts(self.vk.fixed_commitments),
+                         self.pts(self.vk.sigma_commitments), self.vk.transcript_repr, self.instances if instances is None else instances, items,
+                         group=self.group)
 
 
 @functools.lru_cache(maxsize=None)
@@ -120,8 +136,8 @@ def test_an_honest_proof_is_accepted_by_both_verifiers(name):
     g, tr = s.guard(items)
     assert g is not None and tr.finished()
     assert plonk.single_verify(s.params, g)
-    ok, model_squeezes = s.model_verify(items)
-    assert ok
+    ok, model_squeezes, refused = s.model_verify(items)
+    assert ok and refused is None
     assert tr.squeezes == model_squeezes == prover_squeezes and len(set(model_squeezes)) == len(model_squeezes) >= 11 + K
 
 
