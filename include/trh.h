@@ -653,6 +653,10 @@ int trh_stream_synchronize(void* stream);
  * bin sort (0 when that MSM did not use it; synchronises the device, for tests);
  * "msm_small_launches": MSMs that ran as ONE launch (up to 8448 pairs, batches of up to four); "ipa_generator_collapses": openings that
  * collapsed their generators from the fixed-base table (option ipa_fold);
+ * "msm_chunks": the launch sets every pipeline MSM on this context ran as so far (cumulative): a batch goes through one set of launches
+ * `chunk` items at a time -- at most 64, fewer where option msm_chunk_gb cuts it -- so a batch adds ceil(batch / chunk), a one-launch MSM none;
+ * "msm_unit_chunks": of those, the chunks over a fixed-base table whose columns were still unanimously flag-like after their entries were
+ * emitted and which therefore took the unit path (cumulative);
  * "msm_host_ranges": the ranges the last MSM with host scalars (trh_best_multiexp_*, trh_msm) on this context was cut into -- host bases: one up
  * to 2^21 pairs, equal ranges of about 2^20 above; resident bases: one up to 3 * 2^21 pairs, then 2^21, 2^22 and the rest;
  * "msm_range_tiles": the tiles of the last MSM enqueue on this context that ran as range tiles of at most 2^25 pairs (0 when it did not);

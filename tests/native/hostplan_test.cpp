@@ -194,6 +194,50 @@ int main() {
             expect(p.use_bin_shape == r.use_bin, "named shape: LDS bin sort", r.n, r.batch);
         }
     }
+    // chunk shapes: the batches tests/test_gpu_msm_chunks.py runs past one launch set.  chunk = min(batch, 64, floor((chunk_gb << 30) / per_item))
+    // with per_item = W * n * 12 + 1; the GPU tests assert ceil(batch / chunk) through trh_stat "msm_chunks" and build their items on the
+    // window width, the adaptive flag and (the read-back of size_segments, msm.hip) on whether nb * Ws * 4 fits the 4 KiB landing area.
+    {
+        const struct { size_t n, batch; int fc; unsigned gb; int c, W, Ws; size_t chunk, chunks; bool adaptive, use_bin, sparse_ok; } rows[] = {
+            // 32 windows of 8 bits, per_item = 32 * 1500 * 12 + 1 = 576001: the budget allows 7456 items, the cap of 64 cuts
+            {1500, 65, 0, 4, 8, 32, 32, 64, 2, true, false, false},
+            {1500, 96, 0, 4, 8, 32, 32, 64, 2, true, false, false},
+            {1500, 97, 0, 4, 8, 32, 32, 64, 2, true, false, false},
+            {1500, 129, 0, 4, 8, 32, 32, 64, 3, true, false, false},
+            // 64 windows of 4 bits; 256 is the last batch whose Horners msm_finish_t splits with the helper thread, 257 the first beyond
+            {300, 256, 0, 4, 4, 64, 64, 64, 4, true, false, false},
+            {300, 257, 0, 4, 4, 64, 64, 64, 5, true, false, false},
+            // one GiB: per_item = 18 * 2^18 * 12 + 1 = 56623105, floor(2^30 / 56623105) = 18 -> 18 + 2; four GiB hold all 20
+            {(size_t)1 << 18, 20, 0, 1, 15, 18, 18, 18, 2, true, false, false},
+            {(size_t)1 << 18, 20, 0, 4, 15, 18, 18, 20, 1, true, false, false},
+            // per_item = 16 * 2^20 * 12 + 1 = 201326593, floor(2^30 / 201326593) = 5 -> 5 + 1, not adaptive (fused zeroing), LDS bin sort
+            {(size_t)1 << 20, 6, 0, 1, 16, 16, 16, 5, 2, false, true, false},
+            {(size_t)1 << 20, 6, 0, 4, 16, 16, 16, 6, 1, false, true, false},
+            // the table trh_bases_precompute(0) attaches to 2^14 + 1 bases has 12-bit windows (capi.hip: floor(log2 n) - 2, a COPY of that rule: the
+            // GPU test asserts the width the entry returns): one bucket set, the sampler is asked
+            {((size_t)1 << 14) + 1, 70, 12, 4, 12, 22, 1, 64, 2, true, true, true},
+        };
+        for (const auto& r : rows) {
+            const MsmShape sh{r.n, r.batch, r.fc, 0, r.gb};
+            const MsmPlan p = msm_plan(sh);
+            expect(msm_route(sh, false, false) == MSM_ROUTE_PIPELINE, "chunk shape: the pipeline", r.n, r.batch);
+            expect(p.c == r.c && p.W == r.W && p.Ws == r.Ws, "chunk shape: window bits, windows, bucket sets", r.n, r.batch);
+            const size_t per_item = (size_t)p.W * r.n * 12 + 1, cap = ((size_t)r.gb << 30) / per_item;
+            expect(p.chunk == r.chunk && p.chunk == (r.batch < 64 ? (r.batch < cap ? r.batch : cap) : (cap < 64 ? cap : 64)), "chunk shape: items per launch set", r.n, p.chunk);
+            expect((r.batch + p.chunk - 1) / p.chunk == r.chunks, "chunk shape: launch sets", r.n, r.batch);
+            expect(p.adaptive == r.adaptive && p.use_bin_shape == r.use_bin && p.sparse_shape_ok == r.sparse_ok, "chunk shape: adaptive, LDS bin sort, sampler", r.n, r.batch);
+            expect(!r.fc || msm_fixed_base_fits(r.n, r.fc), "chunk shape: the table fits", r.n, r.fc);
+        }
+        // the 4 KiB landing area of the adaptive read-back at c = 8 (Ws = 32): a chunk of 32 fills it to its last byte, 33 is one item over, 64 twice over
+        const MsmPlan p8 = msm_plan(MsmShape{1500, 97, 0, 0, 4});
+        expect((size_t)32 * p8.Ws * 4 == 4096 && (size_t)33 * p8.Ws * 4 > 4096 && (size_t)64 * p8.Ws * 4 == 8192, "chunk shape: 32 items x 32 windows x 4 B == 4096", p8.Ws, 0);
+        // all scalars of an item equal: one bucket of 1500 entries per window, ceil(1500 / 16) = 94 segments -- beyond HEAVY_PIECES; at 300 pairs no bucket can be
+        expect(p8.seg_len0 == 16 && p8.nseg0 == 94 && p8.nseg0 - 1 > HEAVY_PIECES, "chunk shape: a 1500-entry bucket is heavy", p8.nseg0, HEAVY_PIECES);
+        expect(msm_plan(MsmShape{300, 256, 0, 0, 4}).nseg0 == 19, "chunk shape: 300 pairs are 19 segments", 300, 0);
+        // what a lone item and a last chunk of up to four items run as when they are sent on their own
+        expect(msm_route(MsmShape{1500, 1, 0, 0, 4}, false, false) == MSM_ROUTE_SMALL && msm_route(MsmShape{1500, 32, 0, 0, 4}, false, false) == MSM_ROUTE_PIPELINE &&
+               msm_route(MsmShape{300, 64, 0, 0, 4}, false, false) == MSM_ROUTE_PIPELINE, "chunk shape: a lone item is one launch, a last chunk alone the pipeline", 1500, 1);
+    }
     // collision shapes: the plan numbers tests/msm_collision_cases.py (SHAPES) builds the cases of tests/test_gpu_msm_collisions.py on -- which
     // segment offset a bucket starts at, how many pieces the combine adds with how many lanes, which buckets share a reduce slice, which
     // slices meet in a workgroup's tree.  A plan change that fails here means those cases no longer aim where their names say.

@@ -6,26 +6,19 @@ bins 0 and 255 to a uniform draw over the 254 bins between, then put exactly K d
 (one under the capacity, at it -- every register slot of the sort filled -- or one over it), bin 255 is empty, and every other bin stays
 far under the capacity (checked on the digits themselves).  The short top window of 254-bit scalars is oversize in every case (its
 bins hold twice the average), so one launch mixes windows sorted in LDS with windows that took the chunked passes; trh_stat
-"msm_bin_sorted_windows" tells which path every window took.
+"msm_bin_sorted_windows" tells which path every window took.  The generator of the scalars is tests/msm_sort_cases.py.
 """
 import numpy as np
 import pytest
 
 import cpu_ref
 import pasta as o
+from msm_sort_cases import BIN_CAP, LOG_N, canonical as _canonical, lds_windows as _lds_windows
 from tiny_ram_halo2_amd import api, synth
 
 pytestmark = pytest.mark.gpu
 
 CURVE = "pallas"
-LOG_N = 20
-BIN_CAP = 5120  # msm.hip: (avg + avg / 16 + 512) rounded up to 1024 with avg = 2^20 / 256
-WINDOWS = 16    # 255 // 16 + 1; the last (bits 240 ..) is the short top window
-
-
-def _lds_windows(k):
-    """windows of one item that the LDS sort takes: all but the top one, and window 0 only when its bin 0 fits"""
-    return WINDOWS - 1 - (k > BIN_CAP)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -37,30 +30,6 @@ def _init():
 @pytest.fixture(scope="module")
 def bases():
     return api.Bases.generate(CURVE, synth.BASE_S0, synth.BASE_D, 1 << LOG_N)
-
-
-def _window0_bins(can):
-    """level-1 bin of every window-0 digit (signed base-2^16 recoding; -1: digit 0)"""
-    raw = (can[:, 0] & np.uint64(0xFFFF)).astype(np.int64)
-    bucket = np.where(raw > 1 << 15, (1 << 16) - raw, raw)
-    return np.where(bucket > 0, (bucket - 1) >> 7, -1)
-
-
-def _canonical(seed, k, one_bucket=False):
-    """uniform canonical scalars < 2^254 whose window-0 digits miss bins 0 and 255, except the first k: bucket 1 + (i mod 128), or
-    all bucket 5 (one bucket holding k entries)"""
-    n = 1 << LOG_N
-    rng = np.random.default_rng(seed)
-    can = rng.integers(0, 1 << 63, (n, 4), dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, (n, 4), dtype=np.uint64)
-    can[:, 3] &= np.uint64((1 << 62) - 1)
-    edge = np.isin(_window0_bins(can), (0, 255))
-    moved = rng.integers(129, 32641, int(edge.sum())).astype(np.uint64)  # buckets of bins 1 .. 254, positive digits
-    can[edge, 0] = (can[edge, 0] & ~np.uint64(0xFFFF)) | moved
-    sub = np.full(k, 5, np.uint64) if one_bucket else (np.arange(k, dtype=np.uint64) % np.uint64(128)) + np.uint64(1)
-    can[:k, 0] = (can[:k, 0] & ~np.uint64(0xFFFF)) | sub
-    hist = np.bincount(_window0_bins(can) + 1, minlength=257)[1:]
-    assert hist[0] == k and hist[255] == 0 and hist[1:255].max() < BIN_CAP - 512
-    return can
 
 
 def _want(can):

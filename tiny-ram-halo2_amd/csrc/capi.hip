@@ -1365,6 +1365,8 @@ int trh_stat(const char* name, uint64_t* value) {
     TRH_ENTER(0);
     if (strcmp(name, "msm_lean_retries") == 0) { *value = ctx().msm.lean_retries; return TRH_OK; }
     if (strcmp(name, "msm_small_launches") == 0) { *value = ctx().msm.small_launches; return TRH_OK; }
+    if (strcmp(name, "msm_chunks") == 0) { *value = ctx().msm.chunks; return TRH_OK; }
+    if (strcmp(name, "msm_unit_chunks") == 0) { *value = ctx().msm.unit_chunks; return TRH_OK; }
     if (strcmp(name, "msm_host_ranges") == 0) { *value = ctx().msm.host_ranges; return TRH_OK; }
     if (strcmp(name, "msm_range_tiles") == 0) { *value = ctx().msm.range_tiles; return TRH_OK; }
     if (strcmp(name, "ntt_tableless_passes") == 0) { *value = ctx().ntt_tableless_passes; return TRH_OK; }

@@ -146,6 +146,8 @@ struct MsmScratch {
     struct { const void *bases_dev, *bases_z, *scalars_dev, *tails_dev; size_t n, batch, stride; int mont; bool has_fb; MsmFixedBase fb; MsmFlags flags; } retry{};
     unsigned lean_retries = 0;  // how often that happened on this context (tests)
     u64 small_launches = 0;     // MSMs that ran as one msm_small_kernel launch (tests: the path was taken, not fallen back from)
+    u64 chunks = 0;             // launch sets of the pipeline: one per iteration of enqueue_pipeline's chunk loop (tests: a batch ran as that many chunks)
+    u64 unit_chunks = 0;        // of those, the fixed-base chunks whose vote held after the emit (sparse_chunk's unit path)
     const u32* sort_flags = nullptr;  // the last MSM's last chunk: its per-window "a bin did not fit the LDS" flags (null: no bin sort), for trh_stat
     u32 sort_flag_count = 0;
     size_t lean_off_n = 0; int lean_off_c = 0;  // the shape (pairs, window bits) whose lean sort last overflowed: the fallback launches are queued for it again

@@ -1582,7 +1582,7 @@ int reserve_scratch(const MsmRun& r) {
     TRH_TRY(L.parted.ensure(p.entries_bytes()));
     TRH_TRY(L.sorted.ensure(p.entries_bytes()));
     TRH_TRY(L.counts.ensure(p.counts_bytes()));
-    if (p.adaptive && !r.c->pinned_land) TRH_HIP_TRY(hipHostMalloc(&r.c->pinned_land, 4096, hipHostMallocDefault));  // (>= SP_MAX_CHUNK x 16 windows x 4 B)
+    if (p.adaptive && !r.c->pinned_land) TRH_HIP_TRY(hipHostMalloc(&r.c->pinned_land, 4096, hipHostMallocDefault));  // (size_segments reads a chunk's entry totals back only where nb x Ws x 4 B fit it)
     TRH_TRY(L.bin_starts.ensure(p.bins_bytes(p.chunk)));
     TRH_TRY(L.starts.ensure(p.ranges_bytes(p.chunk)));
     TRH_TRY(L.bucket_cnt.ensure(p.ranges_bytes(p.chunk) + 16));
@@ -1865,6 +1865,7 @@ int sparse_chunk(const MsmRun& r, size_t b0, unsigned nb) {
     TRH_HIP_TRY(hipMemcpyAsync(hvotes, sp_count + SP_VOTES, 4, hipMemcpyDeviceToHost, s));
     TRH_HIP_TRY(hipStreamSynchronize(s));
     const int unit_mode = *hvotes == nb;
+    if (unit_mode) ++m.unit_chunks;
     size_t sum = 0;
     u32 most = 0, n_general = 0, n_neutral = 0, n_dense = 0;
     for (unsigned z = 0; z < nb; ++z) {
@@ -1946,6 +1947,7 @@ int enqueue_pipeline(const MsmCall& a, const hostplan::MsmShape& sh) {
     }
     for (size_t b0 = 0; n && b0 < batch; b0 += p.chunk) {
         const unsigned nb = (unsigned)(b0 + p.chunk <= batch ? p.chunk : batch - b0);
+        ++m.chunks;
         if (r.sparse_ok) TRH_TRY((sparse_chunk<SF, BF>(r, b0, nb)));
         else TRH_TRY((run_chunk<SF, BF>(r, b0, nb, PIPE_PLAIN, 0, 0)));
     }
