@@ -7,9 +7,9 @@ CSRC := $(PKG)/csrc
 BUILD_ID := $(shell cat $(CSRC)/*.hip $(CSRC)/*.h include/trh.h | sha1sum | cut -c1-12)
 HIPFLAGS ?= -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -Wall -Wno-unused-function -Wno-unused-result
 OBJS := $(CSRC)/capi.o $(CSRC)/msm.o $(CSRC)/ntt.o $(CSRC)/ipa.o $(CSRC)/ipafold.o $(CSRC)/ipaverify.o $(CSRC)/pointfft.o $(CSRC)/domain.o $(CSRC)/scan.o $(CSRC)/expr.o $(CSRC)/lookup.o $(CSRC)/hostio.o $(CSRC)/selftest.o $(CSRC)/encoding.o $(CSRC)/random.o $(CSRC)/permutation.o $(CSRC)/hashtocurve.o $(CSRC)/mockcheck.o $(CSRC)/quotient.o
-HDRS := $(CSRC)/field.h $(CSRC)/fieldsqrt.h $(CSRC)/chacha.h $(CSRC)/blake2b.h $(CSRC)/hashtocurve.h $(CSRC)/hashtocurve_consts.h $(CSRC)/curve.h $(CSRC)/curve_q4.h $(CSRC)/devmem.h $(CSRC)/dispatch.h $(CSRC)/ctx.h $(CSRC)/hostcombine.h $(CSRC)/hosthelper.h $(CSRC)/hostplan.h $(CSRC)/foldplan.h $(CSRC)/copypool.h $(CSRC)/devpool.h $(CSRC)/permkeygen.h $(CSRC)/tuplehash.h $(CSRC)/selftest_kat.h include/trh.h
+HDRS := $(CSRC)/field.h $(CSRC)/fieldsqrt.h $(CSRC)/chacha.h $(CSRC)/blake2b.h $(CSRC)/transcript.h $(CSRC)/hashtocurve.h $(CSRC)/hashtocurve_consts.h $(CSRC)/curve.h $(CSRC)/curve_q4.h $(CSRC)/devmem.h $(CSRC)/dispatch.h $(CSRC)/ctx.h $(CSRC)/hostcombine.h $(CSRC)/hosthelper.h $(CSRC)/hostplan.h $(CSRC)/foldplan.h $(CSRC)/copypool.h $(CSRC)/devpool.h $(CSRC)/permkeygen.h $(CSRC)/tuplehash.h $(CSRC)/selftest_kat.h include/trh.h
 
-all: $(PKG)/libtrh.so oracle examples/replay tests/native/multi_ctx_test tests/native/libtrh_q4broken.so tests/native/lazy29_dev_test tests/native/lazy29_alias_test tests/native/lazy29_segment_test tests/native/params_io_test tests/native/rng_fill_test tests/native/foldplan_test tests/native/perm_assembly_test tests/native/permkeygen_test tests/native/hashtocurve_vec_test tests/native/params_new_test tests/native/mock_check_test tests/native/quotient_test
+all: $(PKG)/libtrh.so oracle examples/replay tests/native/multi_ctx_test tests/native/libtrh_q4broken.so tests/native/lazy29_dev_test tests/native/lazy29_alias_test tests/native/lazy29_segment_test tests/native/params_io_test tests/native/rng_fill_test tests/native/foldplan_test tests/native/perm_assembly_test tests/native/permkeygen_test tests/native/hashtocurve_vec_test tests/native/params_new_test tests/native/mock_check_test tests/native/quotient_test tests/native/transcript_test
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -89,11 +89,17 @@ tests/native/mock_check_test: tests/native/mock_check_test.cpp include/trh.hpp i
 tests/native/quotient_test: tests/native/quotient_test.cpp include/trh.hpp include/trh.h $(PKG)/libtrh.so
 	g++ -O1 -std=c++17 -Wall -Iinclude $< -o $@ -L$(PKG) -ltrh -pthread -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
 
+# csrc/blake2b.h with a personalisation, csrc/transcript.h (the proof transcript) and trh::Blake2bWrite / Blake2bRead of include/trh.hpp on
+# the host, under address + undefined sanitizers; the program defines the trh_tr_* entries itself (transcript_abi.cpp) and never loads libtrh;
+# run by tests/test_transcript_host.py (which checks it against hashlib and tests/transcript_model.py)
+tests/native/transcript_test: tests/native/transcript_test.cpp tests/native/transcript_abi.cpp include/trh.hpp include/trh.h $(CSRC)/transcript.h $(CSRC)/blake2b.h $(CSRC)/chacha.h $(CSRC)/fieldsqrt.h $(CSRC)/curve.h $(CSRC)/dispatch.h $(CSRC)/field.h
+	g++ -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -fsanitize=address,undefined -fno-sanitize-recover=all tests/native/transcript_test.cpp tests/native/transcript_abi.cpp -o $@
+
 oracle:
 	$(MAKE) -s -C oracle libtrh_oracle.so
 
 clean:
-	rm -f $(OBJS) $(CSRC)/*.q4b.o $(PKG)/libtrh.so tests/native/libtrh_q4broken.so examples/replay tests/native/multi_ctx_test tests/native/lazy29_dev_test tests/native/lazy29_alias_test tests/native/lazy29_segment_test tests/native/params_io_test tests/native/rng_fill_test tests/native/foldplan_test tests/native/perm_assembly_test tests/native/permkeygen_test tests/native/hashtocurve_vec_test tests/native/params_new_test tests/native/mock_check_test tests/native/quotient_test
+	rm -f $(OBJS) $(CSRC)/*.q4b.o $(PKG)/libtrh.so tests/native/libtrh_q4broken.so examples/replay tests/native/multi_ctx_test tests/native/lazy29_dev_test tests/native/lazy29_alias_test tests/native/lazy29_segment_test tests/native/params_io_test tests/native/rng_fill_test tests/native/foldplan_test tests/native/perm_assembly_test tests/native/permkeygen_test tests/native/hashtocurve_vec_test tests/native/params_new_test tests/native/mock_check_test tests/native/quotient_test tests/native/transcript_test
 	$(MAKE) -s -C oracle clean
 
 .PHONY: all oracle clean

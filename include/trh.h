@@ -627,6 +627,41 @@ int trh_map_to_curve_dev(int curve_id, const void* u_dev, size_t n, int per_poin
  * Params::new for tag 0 */
 int trh_hash_to_curve_indexed_dev(int curve_id, const char* prefix, uint8_t tag, uint32_t first, size_t n, void* xy_dev, void* stream);
 
+/* ---- the proof transcript: `Blake2bWrite` / `Blake2bRead` with `Challenge255` (halo2_proofs 0.2.0 src/transcript.rs) -- what turns the items
+ *      create_proof writes into the `Vec<u8>` that `transcript.finalize()` returns and `BatchVerifier::add_proof` takes -----------------------
+ * State: BLAKE2b, 64-byte digest, no key, personalisation "Halo2-Transcript".  common_point absorbs 01 || x || y (32 bytes each, little endian,
+ * canonical, base field; the identity is refused), common_scalar 02 || s (32 bytes, scalar field); write_* do the same and append the 32-byte
+ * compressed point (trh_point_to_bytes' encoding) / the 32 bytes of s to the proof; squeeze_challenge_scalar absorbs 00, finalises a COPY of the
+ * state and reduces the 64 bytes, read as a little-endian integer, modulo the scalar field's order; read_point takes 32 bytes, decodes them
+ * (trh_point_from_bytes' rules, and the identity is refused) and absorbs the point, read_scalar takes 32 bytes, refuses a value >= the modulus
+ * and absorbs it.  That the Rust crate produces these very bytes is recalled, not pinned (csrc/transcript.h).
+ * Points go in as 12-word Jacobian (any Z != 0) and come out as the 8-word affine POD; scalars are 4 Montgomery words, fully reduced.
+ * ERRORS LATCH: after the first refused operation (TRH_EINVAL) every later one does nothing, returns that code again and leaves its output
+ * zero; trh_tr_status / trh_tr_message give the first error's code and text -- the callbacks of trh_transcript_t return void, so inside
+ * trh_ipa_create_proof that is the only way an error is seen: ask for the status when the opening has returned.
+ * The handle is HOST memory, like trh_rng_t: every entry works without a device and before trh_init, starts no device work and takes only the
+ * handle's own lock, so the callbacks may run with the context locked.  curve_id is TRH_PALLAS / TRH_VESTA, any other value is refused as
+ * everywhere else.                                                                                                                         */
+typedef struct trh_tr* trh_tr_t;
+int trh_tr_create_writer(int curve_id, trh_tr_t* out);
+int trh_tr_create_reader(int curve_id, const uint8_t* proof, size_t len, trh_tr_t* out);   /* the bytes are copied; len = 0 is an empty proof */
+void trh_tr_destroy(trh_tr_t t);
+int trh_tr_common_point(trh_tr_t t, const uint64_t xyz[12]);
+int trh_tr_common_scalar(trh_tr_t t, const uint64_t s_mont[4]);
+int trh_tr_write_point(trh_tr_t t, const uint64_t xyz[12]);                                /* a writer's */
+int trh_tr_write_scalar(trh_tr_t t, const uint64_t s_mont[4]);                             /* a writer's */
+int trh_tr_read_point(trh_tr_t t, uint64_t out_xy[8]);                                     /* a reader's */
+int trh_tr_read_scalar(trh_tr_t t, uint64_t out_mont[4]);                                  /* a reader's */
+int trh_tr_squeeze_challenge_scalar(trh_tr_t t, uint64_t out_mont[4]);
+/* *out = the writer as trh_ipa_create_proof's transcript: ctx and three functions of the library, so that the opening's round loop never
+ * leaves it; valid while the handle lives */
+int trh_tr_callbacks(trh_tr_t t, trh_transcript_t* out);
+int trh_tr_status(trh_tr_t t);                              /* TRH_OK, or the latched error's code (its text goes to trh_last_error() too) */
+int trh_tr_message(trh_tr_t t, char* out, size_t cap);      /* the latched error's text, empty while there is none; truncated to cap - 1 */
+int trh_tr_bytes_len(trh_tr_t t, size_t* len);              /* a writer: the bytes written so far; a reader: the length of its proof */
+int trh_tr_bytes(trh_tr_t t, uint8_t* out, size_t cap);     /* copies them out; cap below the length is TRH_EINVAL */
+int trh_tr_remaining(trh_tr_t t, size_t* len);              /* a reader: the bytes not yet taken */
+
 /* ---- element-wise field / group ops on device memory (parity tests of the device arithmetic;
  *      op: 0 add, 1 sub, 2 mul, 3 sqr, 4 neg, 5 inv, 6 to_mont, 7 from_mont) ------------------ */
 int trh_field_op_dev(int field, int op, const void* a_dev, const void* b_dev, void* out_dev, size_t n, void* stream);

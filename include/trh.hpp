@@ -13,6 +13,7 @@
 //   trh::IpaMsm                             poly::commitment::msm::MSM + Guard::use_challenges (the verifier's accumulator)
 //   trh::Rng                                `C::Scalar::random(rng)` for whole vectors: a ChaCha20 seed expanded on the device
 //   trh::PermutationAssembly                plonk::permutation::keygen::Assembly { copy, build_vk, build_pk } (+ the copy-constraint check)
+//   trh::Blake2bWrite / trh::Blake2bRead    transcript::{Blake2bWrite, Blake2bRead} with Challenge255: the proof as bytes (host only)
 //
 // Reference call sites of all of these: /root/reference/src/test_utils.rs:21-49, 89-104 (through keygen_* and
 // create_proof of the halo2_proofs crate pinned at /root/reference/Cargo.lock:619-621).
@@ -670,8 +671,60 @@ private:
     trh_perm_t p_ = nullptr;
 };
 
+// ---- transcript::{Blake2bWrite, Blake2bRead} with Challenge255 (trh_tr_*): the proof as bytes ---------------------------------------------
+// Host memory, like Rng: usable without a device.  Points go in as normalised Jacobian and come out affine, scalars are Montgomery limbs.
+// The handle latches its first error (trh.h); here every call that meets one throws trh::Error, and throw_if_failed() does after an
+// opening that ran through callbacks(), where the C callbacks had no way to report it.
+namespace detail {
+class TranscriptHandle {
+public:
+    TranscriptHandle(const TranscriptHandle&) = delete;
+    TranscriptHandle& operator=(const TranscriptHandle&) = delete;
+    TranscriptHandle(TranscriptHandle&& o) noexcept : curve(o.curve), t_(o.t_) { o.t_ = nullptr; }
+    TranscriptHandle& operator=(TranscriptHandle&& o) noexcept { std::swap(curve, o.curve); std::swap(t_, o.t_); return *this; }
+    ~TranscriptHandle() { if (t_) trh_tr_destroy(t_); }
+    trh_tr_t handle() const { return t_; }
+    void common_point(const Point& p) { check(trh_tr_common_point(t_, (const uint64_t*)&p), "transcript common_point"); }
+    void common_scalar(const Limbs& s) { check(trh_tr_common_scalar(t_, s.data()), "transcript common_scalar"); }
+    Limbs squeeze_challenge_scalar() { Limbs c; check(trh_tr_squeeze_challenge_scalar(t_, c.data()), "transcript squeeze_challenge_scalar"); return c; }
+    void throw_if_failed() const { check(trh_tr_status(t_), "transcript"); }
+    Curve curve;
+protected:
+    explicit TranscriptHandle(Curve c) : curve(c) {}
+    trh_tr_t t_ = nullptr;
+};
+}  // namespace detail
+
+class Blake2bWrite : public detail::TranscriptHandle {
+public:
+    explicit Blake2bWrite(Curve c) : TranscriptHandle(c) { check(trh_tr_create_writer((int)c, &t_), "Blake2bWrite::init"); }
+    void write_point(const Point& p) { check(trh_tr_write_point(t_, (const uint64_t*)&p), "transcript write_point"); }
+    void write_scalar(const Limbs& s) { check(trh_tr_write_scalar(t_, s.data()), "transcript write_scalar"); }
+    // the transcript argument of ipa_create_proof: the library's own functions over this writer; call throw_if_failed() when it has returned
+    trh_transcript_t callbacks() const { trh_transcript_t cb; check(trh_tr_callbacks(t_, &cb), "transcript callbacks"); return cb; }
+    // Blake2bWrite::finalize: the proof so far
+    std::vector<uint8_t> bytes() const {
+        size_t len = 0;
+        check(trh_tr_bytes_len(t_, &len), "transcript bytes");
+        std::vector<uint8_t> out(len);
+        check(trh_tr_bytes(t_, out.data(), out.size()), "transcript bytes");
+        return out;
+    }
+};
+
+class Blake2bRead : public detail::TranscriptHandle {
+public:
+    Blake2bRead(Curve c, const uint8_t* proof, size_t len) : TranscriptHandle(c) { check(trh_tr_create_reader((int)c, proof, len, &t_), "Blake2bRead::init"); }
+    Blake2bRead(Curve c, const std::vector<uint8_t>& proof) : Blake2bRead(c, proof.data(), proof.size()) {}
+    Affine read_point() { Affine p; check(trh_tr_read_point(t_, (uint64_t*)&p), "transcript read_point"); return p; }
+    Limbs read_scalar() { Limbs s; check(trh_tr_read_scalar(t_, s.data()), "transcript read_scalar"); return s; }
+    size_t remaining() const { size_t len = 0; check(trh_tr_remaining(t_, &len), "transcript remaining"); return len; }
+    bool finished() const { return remaining() == 0; }  // the proof has no byte left over
+};
+
 // ---- poly::commitment::create_proof (IPA opening) -------------------------------------------------------------------
-// transcript / rng are the caller's (BLAKE2b transcript and OsRng in the reference): plain C callbacks as in trh.h
+// transcript / rng are the caller's (BLAKE2b transcript and OsRng in the reference): plain C callbacks as in trh.h; a Blake2bWrite's
+// callbacks() keeps the transcript inside the library
 inline std::pair<Limbs, Limbs> ipa_create_proof(const Params& params, const DeviceBuffer& p_poly, const Limbs& p_blind, const Limbs& x3, const DeviceBuffer& s_poly,
                                                 const Limbs& s_blind, const trh_transcript_t& transcript, trh_rng_scalar_fn rng, void* rng_ctx, void* stream = nullptr) {
     require(p_poly.size() >= params.n * 32 && s_poly.size() >= params.n * 32, "px.len() == params.n");

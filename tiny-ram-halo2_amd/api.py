@@ -230,6 +230,22 @@ _SIGNATURES = {
     "trh_hash_to_field_indexed_dev": ([ctypes.c_int, ctypes.c_char_p, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_size_t, _vp, _vp], ctypes.c_int),
     "trh_map_to_curve_dev": ([ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp], ctypes.c_int),
     "trh_hash_to_curve_indexed_dev": ([ctypes.c_int, ctypes.c_char_p, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_size_t, _vp, _vp], ctypes.c_int),
+    "trh_tr_create_writer": ([ctypes.c_int, ctypes.POINTER(_vp)], ctypes.c_int),
+    "trh_tr_create_reader": ([ctypes.c_int, _vp, ctypes.c_size_t, ctypes.POINTER(_vp)], ctypes.c_int),
+    "trh_tr_destroy": ([_vp], None),
+    "trh_tr_common_point": ([_vp, _u64p], ctypes.c_int),
+    "trh_tr_common_scalar": ([_vp, _u64p], ctypes.c_int),
+    "trh_tr_write_point": ([_vp, _u64p], ctypes.c_int),
+    "trh_tr_write_scalar": ([_vp, _u64p], ctypes.c_int),
+    "trh_tr_read_point": ([_vp, _u64p], ctypes.c_int),
+    "trh_tr_read_scalar": ([_vp, _u64p], ctypes.c_int),
+    "trh_tr_squeeze_challenge_scalar": ([_vp, _u64p], ctypes.c_int),
+    "trh_tr_callbacks": ([_vp, ctypes.POINTER(Transcript)], ctypes.c_int),
+    "trh_tr_status": ([_vp], ctypes.c_int),
+    "trh_tr_message": ([_vp, _vp, ctypes.c_size_t], ctypes.c_int),
+    "trh_tr_bytes_len": ([_vp, ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+    "trh_tr_bytes": ([_vp, _vp, ctypes.c_size_t], ctypes.c_int),
+    "trh_tr_remaining": ([_vp, ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
     "trh_set_timing": ([ctypes.c_int], ctypes.c_int),
     "trh_last_timing": ([ctypes.POINTER(Timing)], ctypes.c_int),
 }

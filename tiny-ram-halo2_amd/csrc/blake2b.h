@@ -1,5 +1,6 @@
-// BLAKE2b (RFC 7693) with a 64-byte digest, no key, no salt and an all-zero personalisation: the hash under hash_to_curve's expand_message
-// (csrc/hashtocurve.h), for one message per lane.
+// BLAKE2b (RFC 7693) with a 64-byte digest, no key and no salt.  With an all-zero personalisation it is the hash under hash_to_curve's
+// expand_message (csrc/hashtocurve.h), one message per lane; with the 16 bytes "Halo2-Transcript" it is the sponge of the proof transcript
+// (csrc/transcript.h, host only).
 //
 // The compression function works on 64-bit words with add / xor / rotate right by 32, 24, 16 and 63.  gfx950's vector ALU is 32 bits wide: an
 // add is an add plus an add-with-carry, a xor two xors, and the rotations cost what their amount allows -- 32 swaps the two halves (no
@@ -69,6 +70,15 @@ TRH_HD void blake2b_init(u64 (&h)[8]) {
     h[4] = Blake2bIv<4>::v; h[5] = Blake2bIv<5>::v; h[6] = Blake2bIv<6>::v; h[7] = Blake2bIv<7>::v;
 }
 
+// the same with a 16-byte personalisation: bytes 48 .. 63 of the parameter block (section 2.5) are its words 6 and 7, little endian
+inline void blake2b_init_personal(u64 (&h)[8], const uint8_t person[16]) {
+    blake2b_init(h);
+    u64 p0 = 0, p1 = 0;
+    for (int i = 0; i < 8; ++i) { p0 |= (u64)person[i] << (8 * i); p1 |= (u64)person[8 + i] << (8 * i); }
+    h[6] ^= p0;
+    h[7] ^= p1;
+}
+
 // F of section 3.2: m the block's sixteen little-endian words, t the number of bytes hashed up to and including this block (below 2^64:
 // the high counter word stays zero), last for the final block
 TRH_HD void blake2b_compress(u64 (&h)[8], const u64 (&m)[16], u64 t, bool last) {
@@ -90,13 +100,15 @@ inline void blake2b_block_words(const uint8_t* in, size_t len, u64 (&m)[16]) {
 }
 
 // Incremental form for byte strings (host side).  A full buffer is compressed only when more input follows: the last block -- a full one
-// when the length is a positive multiple of 128 -- must carry the final flag.
+// when the length is a positive multiple of 128 -- must carry the final flag.  finish() ends the state it is called on: a sponge that goes
+// on absorbing after a digest calls it on a COPY, so the struct stays trivially copyable.
 struct Blake2b {
     u64 h[8];
     u64 t = 0;
     uint8_t buf[BLAKE2B_BLOCK];
     size_t fill = 0;
     Blake2b() { blake2b_init(h); }
+    explicit Blake2b(const uint8_t person[16]) { blake2b_init_personal(h, person); }
     void update(const uint8_t* in, size_t len) {
         while (len) {
             if (fill == BLAKE2B_BLOCK) {

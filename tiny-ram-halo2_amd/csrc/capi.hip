@@ -16,6 +16,8 @@
 #include "hosthelper.h"
 #include "curve_q4.h"
 #include "devpool.h"
+#define TRH_TRANSCRIPT_ABI  // the trh_tr_* entries (host only) are defined by the header itself
+#include "transcript.h"
 
 #ifndef TRH_BUILD_ID
 #define TRH_BUILD_ID "unknown"

@@ -17,6 +17,7 @@ import numpy as np
 
 from . import api
 from .poly import _MODULUS, _mont, _stream
+from .transcript import Blake2bWrite
 
 
 def _canon(field: str, limbs) -> int:
@@ -49,7 +50,9 @@ class RngScalarFn:
 def create_proof_native(params, rng, transcript, p_poly, p_blind: int, x3: int, s_poly, s_blind: int):
     """The same opening through the single C entry point `trh_ipa_create_proof` (csrc/ipa.hip): the round loop
     and all host-side scalar arithmetic run in C++, the transcript and randomness are callbacks.  rng: a callable returning canonical ints, or
-    an RngScalarFn (the library's own stream); s_poly: host limbs (uploaded here) or a device tensor (one filled by api.Rng.fill, say)."""
+    an RngScalarFn (the library's own stream); s_poly: host limbs (uploaded here) or a device tensor (one filled by api.Rng.fill, say).
+    transcript: a transcript.Blake2bWrite hands the library its own three functions, so the round loop never enters the interpreter (its
+    latched error, if any, is raised when the call has returned); any other writer is called through three closures."""
     import ctypes
 
     import torch
@@ -64,11 +67,15 @@ def create_proof_native(params, rng, transcript, p_poly, p_blind: int, x3: int, 
         for i in range(4):
             ptr[i] = int(limbs[i])
 
-    wp = api.WRITE_POINT_FN(lambda ctx, p: transcript.write_point(limbs_of(p, 12)))
-    ws = api.WRITE_SCALAR_FN(lambda ctx, p: transcript.write_scalar(limbs_of(p, 4)))
-    sq = api.SQUEEZE_FN(lambda ctx, out: put(out, _mont(sf, transcript.squeeze_challenge_scalar())))
+    native = isinstance(transcript, Blake2bWrite)
+    if native:
+        tr = transcript.callbacks()
+    else:
+        wp = api.WRITE_POINT_FN(lambda ctx, p: transcript.write_point(limbs_of(p, 12)))
+        ws = api.WRITE_SCALAR_FN(lambda ctx, p: transcript.write_scalar(limbs_of(p, 4)))
+        sq = api.SQUEEZE_FN(lambda ctx, out: put(out, _mont(sf, transcript.squeeze_challenge_scalar())))
+        tr = api.Transcript(None, wp, ws, sq)
     rn = rng.fn if isinstance(rng, RngScalarFn) else api.RNG_FN(lambda ctx, out: put(out, _mont(sf, rng())))
-    tr = api.Transcript(None, wp, ws, sq)
     # (np.require copies only when s_poly is not already contiguous and writable: an unconditional .copy() of the 8 MiB was 1 ms of every k = 18 opening)
     s_dev = s_poly if isinstance(s_poly, torch.Tensor) else torch.from_numpy(np.require(s_poly, dtype=np.uint64, requirements=["C", "W"]).view(np.int64)).to(p_poly.device)
     out_c, out_f = np.zeros(4, np.uint64), np.zeros(4, np.uint64)
@@ -79,6 +86,8 @@ def create_proof_native(params, rng, transcript, p_poly, p_blind: int, x3: int, 
                                               api._p(out_c), api._p(out_f)))
     if isinstance(rng, RngScalarFn) and rng.error:
         raise api.TrhError(rng.error)
+    if native:
+        transcript.raise_if_failed()
     return _canon(sf, out_c), _canon(sf, out_f)
 
 

@@ -1,12 +1,16 @@
 """keygen, create_proof and verify_proof of halo2_proofs 0.2.0 (plonk/{circuit, keygen, prover, verifier}.rs, as recalled; the reference reaches
 them from gen_proofs_and_verify, src/test_utils.rs:21-68 of the reference) put together from the device entries of this package: one circuit
-per proof, selectors as plain fixed columns, the transcript an object.
+per proof, selectors as plain fixed columns, the proof a byte string or -- for tests that record items -- whatever a transcript object keeps.
 
     cs = ConstraintSystem(field, num_fixed, num_advice, num_instance, gates, lookups, permutation_columns, minimum_degree=None)
     vk, pk = keygen(params, cs, fixed_columns, copies)
     create_proof(params, pk, instances, advice, rng, transcript)              transcript: a writer
     guard = verify_proof(params, vk, instances, transcript)                    transcript: a reader; raises VerifyError
     single_verify(params, guard)                                               the guard's MSM is the identity
+    proof = create_proof_bytes(params, pk, instances, advice, rng)             Blake2bWrite::init(vec![]) .. transcript.finalize()
+    guard = verify_proof_bytes(params, vk, instances, proof)                   Blake2bRead::init(&proof[..]); raises VerifyError
+    BatchVerifier().add_proof(instances, proof) .. .finalize(params, vk)       plonk::BatchVerifier
+    gen_proofs_and_verify(params, vk, pk, inputs, rng)                         the reference's harness, restated
 
 Every operation on a column-sized vector is a libtrh entry on the current stream (commitments, transforms, expr.GateEvaluator,
 permutation.grand_products_terms / chain_products / lookup_permute_batch, quotient.QuotientTerms, api.poly_eval_batch_dev, multiopen); the host does
@@ -14,7 +18,9 @@ O(#columns) integer work and nothing per row.
 
 A writer has common_point(jacobian12), common_scalar(limbs4), write_point(jacobian12), write_scalar(limbs4) and squeeze_challenge_scalar() -> int;
 a reader has read_point() -> the 8-limb affine POD and read_scalar() -> int in place of the writes.  Limbs are Montgomery words, as everywhere
-at the ABI.  The byte format of upstream's BLAKE2b transcript is not modelled.
+at the ABI.  transcript.Blake2bWrite / Blake2bRead are the writer and the reader of upstream's byte format (BLAKE2b, Challenge255), kept
+inside libtrh.so; the *_bytes functions use them.  The bytes are upstream's ENCODING of this module's item order (next paragraph), so a proof
+made by upstream does not verify here, nor the other way round.
 
 Deviations from upstream, all on purpose: the evaluation h(x) of the folded quotient pieces is written in front of the random polynomial's, so
 that the verifier can test the vanishing identity on scalars and refuse (VerifyError) before any group work; the blinding scalars are drawn
@@ -24,10 +30,12 @@ verifier accepts."""
 from __future__ import annotations
 
 import hashlib
+import secrets
 
 import numpy as np
 
 from . import api, expr, ipa, multiopen, permutation, quotient
+from .transcript import Blake2bRead, Blake2bWrite, TranscriptError
 from .poly import _MODULUS, EvaluationDomain, _mont
 
 
@@ -531,3 +539,93 @@ def single_verify(params, guard: ipa.Guard) -> bool:
     ok, _ = msm.eval()
     msm.destroy()
     return ok
+
+
+# ---- proofs as bytes -----------------------------------------------------------------------------------------------------------------------
+def create_proof_bytes(params, pk: ProvingKey, instances, advice, rng: api.Rng, layout: str = "blocks", strict_lookups: bool = True) -> bytes:
+    """create_proof into a Blake2bWrite, finalized: 32 bytes per item, points compressed, in the order create_proof writes them"""
+    transcript = Blake2bWrite(params.curve)
+    try:
+        create_proof(params, pk, instances, advice, rng, transcript, layout=layout, strict_lookups=strict_lookups)
+        return transcript.finalize()
+    finally:
+        transcript.destroy()
+
+
+def verify_proof_bytes(params, vk: VerifyingKey, instances, proof: bytes) -> ipa.Guard:
+    """verify_proof out of a Blake2bRead over `proof`.  VerifyError for bytes that are no point or no scalar where one is due, a proof that
+    ends early, a proof with bytes left over, and whatever verify_proof refuses"""
+    transcript = Blake2bRead(params.curve, proof)
+    try:
+        guard = verify_proof(params, vk, instances, transcript)
+        if not transcript.finished():
+            raise VerifyError(f"{transcript.remaining()} bytes of the proof are left over")
+        return guard
+    except TranscriptError as e:
+        raise VerifyError(str(e)) from e
+    finally:
+        transcript.destroy()
+
+
+def _random_weight(m: int) -> int:
+    return 1 + secrets.randbelow(m - 1)  # upstream: Scalar::random(OsRng)
+
+
+class BatchVerifier:
+    """plonk::BatchVerifier for the proofs of one verifying key: add_proof(instances, proof), then finalize(params, vk) -> bool.  Every proof
+    is read into its guard (a VerifyError makes the batch false) and the guards are folded by ipa.batch_verify, one random non-zero weight
+    per proof.  weight_source(modulus) -> int replaces the default draw (the secrets module; upstream: OsRng), for tests."""
+
+    def __init__(self, weight_source=None):
+        self.items = []
+        self.weight_source = weight_source or _random_weight
+
+    def add_proof(self, instances, proof: bytes) -> None:
+        self.items.append((instances, bytes(proof)))
+
+    def finalize(self, params, vk: VerifyingKey) -> bool:
+        m = _MODULUS[vk.cs.field]
+        guards = []
+        for instances, proof in self.items:
+            try:
+                guards.append(verify_proof_bytes(params, vk, instances, proof))
+            except VerifyError:
+                return False
+        if not guards:
+            return True
+        weights = [self.weight_source(m) % m for _ in guards]
+        if not all(weights):
+            raise ValueError("a batch weight is zero")
+        return ipa.batch_verify(params, guards, weights)
+
+
+def verify_proofs(params, vk: VerifyingKey, instances_list, proofs, weight_source=None) -> None:
+    """the verifying half of gen_proofs_and_verify: the batch first; when it fails, every proof alone (verify_proof_bytes + single_verify),
+    and VerifyError names the first that fails in its text and in its `index`"""
+    batch = BatchVerifier(weight_source)
+    for instances, proof in zip(instances_list, proofs):
+        batch.add_proof(instances, proof)
+    if batch.finalize(params, vk):
+        return
+    for i, (instances, proof) in enumerate(zip(instances_list, proofs)):
+        try:
+            if single_verify(params, verify_proof_bytes(params, vk, instances, proof)):
+                continue
+            reason = "its opening does not hold"
+        except VerifyError as e:
+            reason = str(e)
+        err = VerifyError(f"proof {i} of {len(proofs)} does not verify: {reason}")
+        err.index = i
+        raise err
+    err = VerifyError("the batch does not verify although every proof does alone")
+    err.index = None
+    raise err
+
+
+def gen_proofs_and_verify(params, vk: VerifyingKey, pk: ProvingKey, inputs, rng: api.Rng):
+    """the reference's harness (src/test_utils.rs:21-68): a proof for every (instances, advice) of `inputs`, all from the one rng stream, then
+    verify_proofs over them.  -> the proofs; VerifyError as verify_proofs raises it"""
+    inputs = list(inputs)
+    proofs = [create_proof_bytes(params, pk, instances, advice, rng) for instances, advice in inputs]
+    verify_proofs(params, vk, [instances for instances, _ in inputs], proofs)
+    return proofs
