@@ -6,10 +6,10 @@ CSRC := $(PKG)/csrc
 # build id = hash of the library's sources (trh_version() reports it)
 BUILD_ID := $(shell cat $(CSRC)/*.hip $(CSRC)/*.h include/trh.h | sha1sum | cut -c1-12)
 HIPFLAGS ?= -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -Wall -Wno-unused-function -Wno-unused-result
-OBJS := $(CSRC)/capi.o $(CSRC)/msm.o $(CSRC)/ntt.o $(CSRC)/ipa.o $(CSRC)/ipafold.o $(CSRC)/ipaverify.o $(CSRC)/pointfft.o $(CSRC)/domain.o $(CSRC)/scan.o $(CSRC)/expr.o $(CSRC)/lookup.o $(CSRC)/hostio.o $(CSRC)/selftest.o $(CSRC)/encoding.o $(CSRC)/random.o $(CSRC)/permutation.o $(CSRC)/hashtocurve.o $(CSRC)/mockcheck.o $(CSRC)/quotient.o
-HDRS := $(CSRC)/field.h $(CSRC)/fieldsqrt.h $(CSRC)/chacha.h $(CSRC)/blake2b.h $(CSRC)/transcript.h $(CSRC)/hashtocurve.h $(CSRC)/hashtocurve_consts.h $(CSRC)/curve.h $(CSRC)/curve_q4.h $(CSRC)/devmem.h $(CSRC)/dispatch.h $(CSRC)/ctx.h $(CSRC)/hostcombine.h $(CSRC)/hosthelper.h $(CSRC)/hostplan.h $(CSRC)/foldplan.h $(CSRC)/copypool.h $(CSRC)/devpool.h $(CSRC)/permkeygen.h $(CSRC)/tuplehash.h $(CSRC)/selftest_kat.h include/trh.h
+OBJS := $(CSRC)/capi.o $(CSRC)/msm.o $(CSRC)/ntt.o $(CSRC)/ipa.o $(CSRC)/ipafold.o $(CSRC)/ipaverify.o $(CSRC)/pointfft.o $(CSRC)/domain.o $(CSRC)/scan.o $(CSRC)/expr.o $(CSRC)/lookup.o $(CSRC)/hostio.o $(CSRC)/selftest.o $(CSRC)/encoding.o $(CSRC)/random.o $(CSRC)/permutation.o $(CSRC)/hashtocurve.o $(CSRC)/mockcheck.o $(CSRC)/quotient.o $(CSRC)/witness.o
+HDRS := $(CSRC)/field.h $(CSRC)/fieldsqrt.h $(CSRC)/chacha.h $(CSRC)/blake2b.h $(CSRC)/transcript.h $(CSRC)/hashtocurve.h $(CSRC)/hashtocurve_consts.h $(CSRC)/curve.h $(CSRC)/curve_q4.h $(CSRC)/devmem.h $(CSRC)/dispatch.h $(CSRC)/ctx.h $(CSRC)/hostcombine.h $(CSRC)/hosthelper.h $(CSRC)/hostplan.h $(CSRC)/foldplan.h $(CSRC)/copypool.h $(CSRC)/devpool.h $(CSRC)/permkeygen.h $(CSRC)/tuplehash.h $(CSRC)/witness.h $(CSRC)/selftest_kat.h include/trh.h
 
-all: $(PKG)/libtrh.so oracle examples/replay tests/native/multi_ctx_test tests/native/libtrh_q4broken.so tests/native/lazy29_dev_test tests/native/lazy29_alias_test tests/native/lazy29_segment_test tests/native/params_io_test tests/native/rng_fill_test tests/native/foldplan_test tests/native/perm_assembly_test tests/native/permkeygen_test tests/native/hashtocurve_vec_test tests/native/params_new_test tests/native/mock_check_test tests/native/quotient_test tests/native/transcript_test
+all: $(PKG)/libtrh.so oracle examples/replay tests/native/multi_ctx_test tests/native/libtrh_q4broken.so tests/native/lazy29_dev_test tests/native/lazy29_alias_test tests/native/lazy29_segment_test tests/native/params_io_test tests/native/rng_fill_test tests/native/foldplan_test tests/native/perm_assembly_test tests/native/permkeygen_test tests/native/hashtocurve_vec_test tests/native/params_new_test tests/native/mock_check_test tests/native/quotient_test tests/native/transcript_test tests/native/witness_vec_test tests/native/witness_test
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -95,11 +95,20 @@ tests/native/quotient_test: tests/native/quotient_test.cpp include/trh.hpp inclu
 tests/native/transcript_test: tests/native/transcript_test.cpp tests/native/transcript_abi.cpp include/trh.hpp include/trh.h $(CSRC)/transcript.h $(CSRC)/blake2b.h $(CSRC)/chacha.h $(CSRC)/fieldsqrt.h $(CSRC)/curve.h $(CSRC)/dispatch.h $(CSRC)/field.h
 	g++ -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -fsanitize=address,undefined -fno-sanitize-recover=all tests/native/transcript_test.cpp tests/native/transcript_abi.cpp -o $@
 
+# csrc/witness.h (integers to field elements, the even-bits decomposition) on the host, under address + undefined sanitizers: reads cases,
+# prints limbs; never loads libtrh; run by tests/test_witness_host.py (which checks it against Python integers)
+tests/native/witness_vec_test: tests/native/witness_vec_test.cpp $(CSRC)/witness.h $(CSRC)/field.h
+	g++ -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -fsanitize=address,undefined -fno-sanitize-recover=all $< -o $@
+
+# trh::columns_from_ints, trh::even_odd_split and trh::even_bits_table over include/trh.hpp; run by tests/test_gpu_witness.py
+tests/native/witness_test: tests/native/witness_test.cpp include/trh.hpp include/trh.h $(PKG)/libtrh.so
+	g++ -O1 -std=c++17 -Wall -Iinclude $< -o $@ -L$(PKG) -ltrh -pthread -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
+
 oracle:
 	$(MAKE) -s -C oracle libtrh_oracle.so
 
 clean:
-	rm -f $(OBJS) $(CSRC)/*.q4b.o $(PKG)/libtrh.so tests/native/libtrh_q4broken.so examples/replay tests/native/multi_ctx_test tests/native/lazy29_dev_test tests/native/lazy29_alias_test tests/native/lazy29_segment_test tests/native/params_io_test tests/native/rng_fill_test tests/native/foldplan_test tests/native/perm_assembly_test tests/native/permkeygen_test tests/native/hashtocurve_vec_test tests/native/params_new_test tests/native/mock_check_test tests/native/quotient_test tests/native/transcript_test
+	rm -f $(OBJS) $(CSRC)/*.q4b.o $(PKG)/libtrh.so tests/native/libtrh_q4broken.so examples/replay tests/native/multi_ctx_test tests/native/lazy29_dev_test tests/native/lazy29_alias_test tests/native/lazy29_segment_test tests/native/params_io_test tests/native/rng_fill_test tests/native/foldplan_test tests/native/perm_assembly_test tests/native/permkeygen_test tests/native/hashtocurve_vec_test tests/native/params_new_test tests/native/mock_check_test tests/native/quotient_test tests/native/transcript_test tests/native/witness_vec_test tests/native/witness_test
 	$(MAKE) -s -C oracle clean
 
 .PHONY: all oracle clean

@@ -662,6 +662,53 @@ int trh_tr_bytes_len(trh_tr_t t, size_t* len);              /* a writer: the byt
 int trh_tr_bytes(trh_tr_t t, uint8_t* out, size_t cap);     /* copies them out; cap below the length is TRH_EINVAL */
 int trh_tr_remaining(trh_tr_t t, size_t* len);              /* a reader: the bytes not yet taken */
 
+/* ---- packed witness intake: columns from machine integers and flag bits, expanded on the device ------------------------------------------
+ * A host that knows its trace as machine words (any TinyRAM host does, before it wraps them in `F::from(u64)`) hands over the words and
+ * bitmaps; the device makes the columns: 1 .. 8 bytes or one bit per cell cross the link instead of 32 bytes.
+ * The source is n_cols columns, column c starting src_stride ELEMENTS (u32 words for TRH_INT_BITS) behind column c - 1, each with live_rows
+ * live rows; the destination is n_cols columns of n stored elements (4 x u64 canonical Montgomery words, fully reduced, bit-exact) back to
+ * back.  Row r < live_rows of column c is
+ *   TRH_INT_BITS               bit r & 31 of the u32 word src[c * src_stride + (r >> 5)]: R mod m for a set bit, zero for a clear one; bits of
+ *                              the last word at positions >= live_rows are ignored
+ *   TRH_INT_U8 .. TRH_INT_U64  the element's value
+ *   TRH_INT_I32, TRH_INT_I64   the element's value, m - |v| for v < 0
+ * and rows live_rows .. n - 1 are WRITTEN as zero (nothing is loaded for them).  The source needs the natural alignment of its elements and
+ * nothing more (a column may start at an odd element offset); the last column need not extend beyond its live rows.
+ * trh_columns_from_ints_dev:  src is device memory.  Asynchronous on args->stream (the stream travels in the struct, as in
+ *   trh_quotient_args_t), ordered behind the context's previous call; no host read, no synchronisation.
+ * trh_columns_from_ints_host: src is ANY host memory, pageable included.  The packed bytes go through the context's pinned upload ring into
+ *   context scratch, whole columns at a time -- as many as fit 64 MiB, one if a single packed column is larger, which bounds the scratch by
+ *   max(64 MiB, one packed column) -- and the same kernel runs; it returns when the source has been read.  Counted by trh_io_stats.
+ * trh_even_odd_split_dev:     kinds TRH_INT_U8 .. TRH_INT_U64, device src: dst takes w & 0x5555.. and dst_odd (w & 0xAAAA..) >> 1 of every
+ *   word w, the two halves of the reference's even-bits decomposition (even + 2 odd = w, both with bits at even positions only); the
+ *   halves need not cross the link once their word is on the device.
+ * trh_even_bits_table_dev:    dst[i] = sum_j bit_j(i) 4^j for i < 2^(word_bits / 2), zero from there to n: the even-bits lookup table.
+ *   TRH_EINVAL for an odd word_bits, word_bits outside 2 .. 64, 2^(word_bits / 2) > n, a null or misaligned dst.
+ * n_cols == 0 or n == 0 succeeds and does nothing.  TRH_EINVAL, with nothing written: an unknown field or kind, src_stride too small for
+ * live_rows, live_rows > n, a null or misaligned dst, a misaligned src; for the split also a signed or TRH_INT_BITS kind and a null or
+ * misaligned dst_odd.                                                                                                                    */
+enum { TRH_INT_BITS = 0, TRH_INT_U8, TRH_INT_U16, TRH_INT_U32, TRH_INT_U64, TRH_INT_I32, TRH_INT_I64 };
+typedef struct trh_ints_args {
+    int kind;
+    const void* src;      /* device memory for *_dev, any host memory (pageable allowed) for *_host */
+    size_t src_stride;    /* elements between consecutive columns (u32 words for BITS); >= live_rows (BITS: >= ceil(live_rows / 32)) */
+    size_t n_cols, live_rows;
+    void*  dst;           /* device, n_cols x n x 4 u64, 16-byte aligned: canonical Montgomery words */
+    void*  dst_odd;       /* trh_even_odd_split_dev only: the odd halves, same shape; dst takes the even halves */
+    size_t n;             /* rows per destination column, >= live_rows; rows live_rows .. n - 1 are WRITTEN as zero */
+    void*  stream;
+} trh_ints_args_t;
+typedef struct trh_even_bits_table_args {
+    uint32_t word_bits;   /* even, 2 .. 64 */
+    void*  dst;           /* device, n x 4 u64, 16-byte aligned */
+    size_t n;             /* >= 2^(word_bits / 2) */
+    void*  stream;
+} trh_even_bits_table_args_t;
+int trh_columns_from_ints_dev(int field_id, const trh_ints_args_t* args);
+int trh_columns_from_ints_host(int field_id, const trh_ints_args_t* args);
+int trh_even_odd_split_dev(int field_id, const trh_ints_args_t* args);
+int trh_even_bits_table_dev(int field_id, const trh_even_bits_table_args_t* args);
+
 /* ---- element-wise field / group ops on device memory (parity tests of the device arithmetic;
  *      op: 0 add, 1 sub, 2 mul, 3 sqr, 4 neg, 5 inv, 6 to_mont, 7 from_mont) ------------------ */
 int trh_field_op_dev(int field, int op, const void* a_dev, const void* b_dev, void* out_dev, size_t n, void* stream);

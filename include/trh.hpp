@@ -28,6 +28,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -609,6 +610,39 @@ struct RngScalarFn {
         if (trh_rng_next_scalar(s->rng.handle(), (int)s->field, out_mont) != TRH_OK) { s->failed = true; for (int i = 0; i < 4; ++i) out_mont[i] = 0; }
     }
 };
+
+// ---- packed witness intake (trh_columns_from_ints_*, trh_even_odd_split_dev, trh_even_bits_table_dev): `F::from(u64)` for whole columns --
+// A host that keeps its trace as machine words hands over words and bitmaps; the device expands them into columns of n stored elements,
+// zero behind the live rows.  IntKind names the source's element type; Bits is a bitmap of u32 words, bit r & 31 of word r >> 5 for row r.
+enum class IntKind : int { Bits = TRH_INT_BITS, U8 = TRH_INT_U8, U16 = TRH_INT_U16, U32 = TRH_INT_U32, U64 = TRH_INT_U64, I32 = TRH_INT_I32, I64 = TRH_INT_I64 };
+template <class T> constexpr IntKind int_kind_of() {
+    static_assert(std::is_integral<T>::value && (sizeof(T) == 1 ? std::is_unsigned<T>::value : sizeof(T) == 2 ? std::is_unsigned<T>::value : sizeof(T) == 4 || sizeof(T) == 8),
+                  "u8, u16, u32, u64, i32 or i64");
+    return sizeof(T) == 1 ? IntKind::U8 : sizeof(T) == 2 ? IntKind::U16 : sizeof(T) == 4 ? (std::is_signed<T>::value ? IntKind::I32 : IntKind::U32)
+                                                                                           : (std::is_signed<T>::value ? IntKind::I64 : IntKind::U64);
+}
+// src: n_cols columns of live_rows elements, src_stride elements apart; dst_dev: n_cols x n elements.  src_on_host: any host memory
+// (staged through the context's pinned ring), else device memory
+inline void columns_from_ints(Field f, IntKind kind, const void* src, bool src_on_host, size_t src_stride, size_t n_cols, size_t live_rows, void* dst_dev, size_t n,
+                              void* stream = nullptr) {
+    trh_ints_args_t a{(int)kind, src, src_stride, n_cols, live_rows, dst_dev, nullptr, n, stream};
+    check(src_on_host ? trh_columns_from_ints_host((int)f, &a) : trh_columns_from_ints_dev((int)f, &a), "columns_from_ints");
+}
+// one column from a host vector of machine integers
+template <class T> inline void columns_from_ints(Field f, const std::vector<T>& values, void* dst_dev, size_t n, void* stream = nullptr) {
+    columns_from_ints(f, int_kind_of<T>(), values.data(), true, values.size(), 1, values.size(), dst_dev, n, stream);
+}
+// the even-bits decomposition of resident words (unsigned kinds): even_dev takes w & 0x5555.., odd_dev (w & 0xAAAA..) >> 1
+inline void even_odd_split(Field f, IntKind kind, const void* src_dev, size_t src_stride, size_t n_cols, size_t live_rows, void* even_dev, void* odd_dev, size_t n,
+                           void* stream = nullptr) {
+    trh_ints_args_t a{(int)kind, src_dev, src_stride, n_cols, live_rows, even_dev, odd_dev, n, stream};
+    check(trh_even_odd_split_dev((int)f, &a), "even_odd_split");
+}
+// the even-bits lookup table of word_bits-bit words: 2^(word_bits / 2) rows, zero from there to n
+inline void even_bits_table(Field f, uint32_t word_bits, void* dst_dev, size_t n, void* stream = nullptr) {
+    trh_even_bits_table_args_t a{word_bits, dst_dev, n, stream};
+    check(trh_even_bits_table_dev((int)f, &a), "even_bits_table");
+}
 
 // ---- plonk::permutation::keygen::Assembly (trh_perm_*): the copy constraints of the equality-enabled columns, the sigma columns they
 // induce -- made on the device -- and what keygen_vk / keygen_pk derive from them ---------------------------------------------------------

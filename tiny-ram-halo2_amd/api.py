@@ -77,6 +77,17 @@ class ProductChainArgs(ctypes.Structure):
     _fields_ = [("z", ctypes.c_void_p), ("n", ctypes.c_size_t), ("rows", ctypes.c_size_t), ("link", ctypes.c_size_t), ("stream", ctypes.c_void_p)]
 
 
+class IntsArgs(ctypes.Structure):
+    """trh_ints_args_t"""
+    _fields_ = [("kind", ctypes.c_int), ("src", ctypes.c_void_p), ("src_stride", ctypes.c_size_t), ("n_cols", ctypes.c_size_t), ("live_rows", ctypes.c_size_t),
+                ("dst", ctypes.c_void_p), ("dst_odd", ctypes.c_void_p), ("n", ctypes.c_size_t), ("stream", ctypes.c_void_p)]
+
+
+class EvenBitsTableArgs(ctypes.Structure):
+    """trh_even_bits_table_args_t"""
+    _fields_ = [("word_bits", ctypes.c_uint32), ("dst", ctypes.c_void_p), ("n", ctypes.c_size_t), ("stream", ctypes.c_void_p)]
+
+
 _SIGNATURES = {
     "trh_init": ([ctypes.c_int], ctypes.c_int),
     "trh_shutdown": ([], None),
@@ -246,6 +257,10 @@ _SIGNATURES = {
     "trh_tr_bytes_len": ([_vp, ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
     "trh_tr_bytes": ([_vp, _vp, ctypes.c_size_t], ctypes.c_int),
     "trh_tr_remaining": ([_vp, ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+    "trh_columns_from_ints_dev": ([ctypes.c_int, ctypes.POINTER(IntsArgs)], ctypes.c_int),
+    "trh_columns_from_ints_host": ([ctypes.c_int, ctypes.POINTER(IntsArgs)], ctypes.c_int),
+    "trh_even_odd_split_dev": ([ctypes.c_int, ctypes.POINTER(IntsArgs)], ctypes.c_int),
+    "trh_even_bits_table_dev": ([ctypes.c_int, ctypes.POINTER(EvenBitsTableArgs)], ctypes.c_int),
     "trh_set_timing": ([ctypes.c_int], ctypes.c_int),
     "trh_last_timing": ([ctypes.POINTER(Timing)], ctypes.c_int),
 }

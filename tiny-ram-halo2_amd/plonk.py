@@ -34,7 +34,7 @@ import secrets
 
 import numpy as np
 
-from . import api, expr, ipa, multiopen, permutation, quotient
+from . import api, expr, ipa, multiopen, permutation, quotient, witness
 from .transcript import Blake2bRead, Blake2bWrite, TranscriptError
 from .poly import _MODULUS, EvaluationDomain, _mont
 
@@ -261,10 +261,21 @@ def _instance_columns(cs, n, instances, dev):
     u = cs.usable_rows(n)
     if len(instances) != cs.num_instance:
         raise ValueError(f"{len(instances)} instance columns, the circuit has {cs.num_instance}")
-    cols = np.zeros((cs.num_instance, n, 4), dtype=np.uint64)
     for i, values in enumerate(instances):
         if len(values) > u:
             raise ValueError(f"instance column {i}: {len(values)} values, {u} usable rows")
+    is_words = [isinstance(values, np.ndarray) and values.dtype.kind == "u" for values in instances]
+    if any(is_words):
+        # columns given as machine words are expanded on the device (witness.columns_from_ints): no big integer per value on the host
+        out = torch.zeros((cs.num_instance, n, 4), dtype=torch.int64, device=dev)
+        for i, values in enumerate(instances):
+            if is_words[i]:
+                witness.columns_from_ints(cs.field, values.reshape(-1), n, out=out[i])
+            elif len(values):
+                out[i, :len(values)] = torch.from_numpy(multiopen._limbs_many(cs.field, list(values)).view(np.int64)).to(dev)
+        return out
+    cols = np.zeros((cs.num_instance, n, 4), dtype=np.uint64)
+    for i, values in enumerate(instances):
         if len(values):
             cols[i, :len(values)] = multiopen._limbs_many(cs.field, list(values))
     return torch.from_numpy(cols.view(np.int64)).to(dev)
@@ -275,7 +286,8 @@ def _rotated(x: int, omega: int, omega_inv: int, r: int, m: int) -> int:
 
 
 def create_proof(params, pk: ProvingKey, instances, advice, rng: api.Rng, transcript, layout: str = "blocks", strict_lookups: bool = True) -> None:
-    """plonk::create_proof for one circuit.  instances: one list of integers per instance column; advice: device tensor (num_advice, n, 4) of
+    """plonk::create_proof for one circuit.  instances: per instance column a list of integers or a numpy array of unsigned machine words (the
+    array is expanded on the device: witness.columns_from_ints); advice: device tensor (num_advice, n, 4) of
     Lagrange values, whose rows behind the usable ones are ignored (a copy gets the blinding rows); rng: the trh_rng stream every random
     scalar comes from; layout: "blocks" (coset blocks) or "flat" for the extended domain h(X) is built on -- the proofs are identical."""
     import torch
