@@ -6,27 +6,39 @@ CSRC := $(PKG)/csrc
 # build id = hash of the library's sources (trh_version() reports it)
 BUILD_ID := $(shell cat $(CSRC)/*.hip $(CSRC)/*.h include/trh.h | sha1sum | cut -c1-12)
 HIPFLAGS ?= -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -Wall -Wno-unused-function -Wno-unused-result
-OBJS := $(CSRC)/capi.o $(CSRC)/msm.o $(CSRC)/ntt.o $(CSRC)/ipa.o $(CSRC)/ipafold.o $(CSRC)/ipaverify.o $(CSRC)/pointfft.o $(CSRC)/domain.o $(CSRC)/scan.o $(CSRC)/expr.o $(CSRC)/lookup.o $(CSRC)/hostio.o $(CSRC)/selftest.o $(CSRC)/encoding.o $(CSRC)/random.o $(CSRC)/permutation.o $(CSRC)/hashtocurve.o $(CSRC)/mockcheck.o $(CSRC)/quotient.o $(CSRC)/witness.o
-HDRS := $(CSRC)/field.h $(CSRC)/fieldsqrt.h $(CSRC)/chacha.h $(CSRC)/blake2b.h $(CSRC)/transcript.h $(CSRC)/hashtocurve.h $(CSRC)/hashtocurve_consts.h $(CSRC)/curve.h $(CSRC)/curve_q4.h $(CSRC)/devmem.h $(CSRC)/dispatch.h $(CSRC)/ctx.h $(CSRC)/hostcombine.h $(CSRC)/hosthelper.h $(CSRC)/hostplan.h $(CSRC)/foldplan.h $(CSRC)/copypool.h $(CSRC)/devpool.h $(CSRC)/permkeygen.h $(CSRC)/tuplehash.h $(CSRC)/witness.h $(CSRC)/selftest_kat.h include/trh.h
+# every .hip under csrc/ is part of the library, every header there a prerequisite of every object
+SRCS := $(wildcard $(CSRC)/*.hip)
+OBJS := $(patsubst %.hip,%.o,$(SRCS))
+HDRS := $(wildcard $(CSRC)/*.h) include/trh.h
+ID_OBJ := $(CSRC)/capi.o
+# driver programs over include/trh.hpp that share one command line, each run by the GPU test of its subject: Params::write / read
+# (test_gpu_encoding.py), trh::Rng (test_gpu_rng.py), trh::PermutationAssembly (test_gpu_permkeygen.py), trh::Params::create
+# (test_gpu_hashtocurve.py), GateEvaluator::check and lookup_check (test_gpu_mock.py), trh::QuotientTerms (test_gpu_quotient.py),
+# columns_from_ints / even_odd_split / even_bits_table (test_gpu_witness.py)
+HPP_TESTS := $(addprefix tests/native/,params_io_test rng_fill_test perm_assembly_test params_new_test mock_check_test quotient_test witness_test)
+NATIVE := examples/replay tests/native/libtrh_q4broken.so $(HPP_TESTS) $(addprefix tests/native/,multi_ctx_test lazy29_dev_test lazy29_alias_test lazy29_segment_test \
+    foldplan_test permkeygen_test hashtocurve_vec_test transcript_test witness_vec_test)
 
-all: $(PKG)/libtrh.so oracle examples/replay tests/native/multi_ctx_test tests/native/libtrh_q4broken.so tests/native/lazy29_dev_test tests/native/lazy29_alias_test tests/native/lazy29_segment_test tests/native/params_io_test tests/native/rng_fill_test tests/native/foldplan_test tests/native/perm_assembly_test tests/native/permkeygen_test tests/native/hashtocurve_vec_test tests/native/params_new_test tests/native/mock_check_test tests/native/quotient_test tests/native/transcript_test tests/native/witness_vec_test tests/native/witness_test
+all: $(PKG)/libtrh.so oracle $(NATIVE)
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-# capi.o carries the build id: rebuilt whenever any source of the library changes
-$(CSRC)/capi.o: $(CSRC)/capi.hip $(HDRS) $(wildcard $(CSRC)/*.hip)
+# this object carries the build id: rebuilt whenever any source of the library changes
+$(ID_OBJ): $(ID_OBJ:.o=.hip) $(HDRS) $(SRCS)
 	$(HIPCC) $(HIPFLAGS) -DTRH_BUILD_ID='"$(BUILD_ID)"' -c $< -o $@
 
 $(PKG)/libtrh.so: $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(OBJS) -ldl -o $@
 
 # The library WITHOUT curve_q4.h's work-around for the ROCm 7.2 DPP-combiner miscompile: trh_init's self-test has to refuse it
-# (tests/test_gpu_selftest.py).  Only the two objects that instantiate the quad-lane group law are rebuilt.
+# (tests/test_gpu_selftest.py).  Only the objects that instantiate the quad-lane group law (they include curve_q4.h) and the one with the
+# build id are rebuilt.
+Q4B_OBJS := $(patsubst %.hip,%.o,$(shell grep -l 'include "curve_q4.h"' $(SRCS))) $(ID_OBJ)
 $(CSRC)/%.q4b.o: $(CSRC)/%.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -DTRH_TEST_DROP_Q4_WORKAROUND -DTRH_BUILD_ID='"$(BUILD_ID)-q4broken"' -c $< -o $@
-tests/native/libtrh_q4broken.so: $(CSRC)/capi.q4b.o $(CSRC)/msm.q4b.o $(OBJS)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(CSRC)/capi.q4b.o $(CSRC)/msm.q4b.o $(filter-out $(CSRC)/capi.o $(CSRC)/msm.o,$(OBJS)) -ldl -o $@
+tests/native/libtrh_q4broken.so: $(Q4B_OBJS:.o=.q4b.o) $(OBJS)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(Q4B_OBJS:.o=.q4b.o) $(filter-out $(Q4B_OBJS),$(OBJS)) -ldl -o $@
 
 # native (C++17, no Python) driver over include/trh.hpp
 examples/replay: examples/replay.cpp include/trh.hpp include/trh.h $(PKG)/libtrh.so
@@ -37,12 +49,7 @@ tests/native/multi_ctx_test: tests/native/multi_ctx_test.cpp include/trh.h $(PKG
 	g++ -O1 -std=c++17 -Wall -D__HIP_PLATFORM_AMD__ -Iinclude -I/opt/rocm/include $< -o $@ -L$(PKG) -ltrh -L/opt/rocm/lib -lamdhip64 -pthread \
 	    -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -Wl,-rpath,/opt/rocm/lib
 
-# native round trip of Params::write / Params::read over include/trh.hpp; run by tests/test_gpu_encoding.py
-tests/native/params_io_test: tests/native/params_io_test.cpp include/trh.hpp include/trh.h $(PKG)/libtrh.so
-	g++ -O1 -std=c++17 -Wall -Iinclude $< -o $@ -L$(PKG) -ltrh -pthread -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
-
-# trh::Rng (the random-scalar stream) over include/trh.hpp; run by tests/test_gpu_rng.py
-tests/native/rng_fill_test: tests/native/rng_fill_test.cpp include/trh.hpp include/trh.h $(PKG)/libtrh.so
+$(HPP_TESTS): tests/native/%: tests/native/%.cpp include/trh.hpp include/trh.h $(PKG)/libtrh.so
 	g++ -O1 -std=c++17 -Wall -Iinclude $< -o $@ -L$(PKG) -ltrh -pthread -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
 
 # the lazy 29-bit domain (field.h Fy, curve.h XYZZz) record by record on the device, compiled with the library's flags so that every
@@ -63,10 +70,6 @@ tests/native/lazy29_segment_test: tests/native/lazy29_segment_test.hip $(CSRC)/f
 tests/native/foldplan_test: tests/native/foldplan_test.cpp $(CSRC)/foldplan.h $(CSRC)/hostcombine.h
 	g++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=all $< -o $@
 
-# trh::PermutationAssembly (permutation keygen) over include/trh.hpp; run by tests/test_gpu_permkeygen.py
-tests/native/perm_assembly_test: tests/native/perm_assembly_test.cpp include/trh.hpp include/trh.h $(PKG)/libtrh.so
-	g++ -O1 -std=c++17 -Wall -Iinclude $< -o $@ -L$(PKG) -ltrh -pthread -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
-
 # the keygen assembly (csrc/permkeygen.h) on the host, under address + undefined sanitizers: reads copies, writes the mappings; run by
 # tests/test_permkeygen_host.py (which checks them against the model and a union-find)
 tests/native/permkeygen_test: tests/native/permkeygen_test.cpp $(CSRC)/permkeygen.h include/trh.h
@@ -76,18 +79,6 @@ tests/native/permkeygen_test: tests/native/permkeygen_test.cpp $(CSRC)/permkeyge
 # field elements and points; run by tests/test_hashtocurve_host.py (which checks them against hashlib and tests/hash_to_curve_model.py)
 tests/native/hashtocurve_vec_test: tests/native/hashtocurve_vec_test.cpp $(CSRC)/blake2b.h $(CSRC)/hashtocurve.h $(CSRC)/hashtocurve_consts.h $(CSRC)/chacha.h $(CSRC)/fieldsqrt.h $(CSRC)/curve.h $(CSRC)/field.h
 	g++ -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -fsanitize=address,undefined -fno-sanitize-recover=all $< -o $@
-
-# trh::Params::create (Params::new: hash_to_curve on the device) over include/trh.hpp; run by tests/test_gpu_hashtocurve.py
-tests/native/params_new_test: tests/native/params_new_test.cpp include/trh.hpp include/trh.h $(PKG)/libtrh.so
-	g++ -O1 -std=c++17 -Wall -Iinclude $< -o $@ -L$(PKG) -ltrh -pthread -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
-
-# trh::GateEvaluator::check and trh::lookup_check (MockProver's gate and lookup checks) over include/trh.hpp; run by tests/test_gpu_mock.py
-tests/native/mock_check_test: tests/native/mock_check_test.cpp include/trh.hpp include/trh.h $(PKG)/libtrh.so
-	g++ -O1 -std=c++17 -Wall -Iinclude $< -o $@ -L$(PKG) -ltrh -pthread -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
-
-# trh::QuotientTerms (the permutation and lookup terms of h(X)) over include/trh.hpp; run by tests/test_gpu_quotient.py
-tests/native/quotient_test: tests/native/quotient_test.cpp include/trh.hpp include/trh.h $(PKG)/libtrh.so
-	g++ -O1 -std=c++17 -Wall -Iinclude $< -o $@ -L$(PKG) -ltrh -pthread -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
 
 # csrc/blake2b.h with a personalisation, csrc/transcript.h (the proof transcript) and trh::Blake2bWrite / Blake2bRead of include/trh.hpp on
 # the host, under address + undefined sanitizers; the program defines the trh_tr_* entries itself (transcript_abi.cpp) and never loads libtrh;
@@ -100,15 +91,11 @@ tests/native/transcript_test: tests/native/transcript_test.cpp tests/native/tran
 tests/native/witness_vec_test: tests/native/witness_vec_test.cpp $(CSRC)/witness.h $(CSRC)/field.h
 	g++ -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -fsanitize=address,undefined -fno-sanitize-recover=all $< -o $@
 
-# trh::columns_from_ints, trh::even_odd_split and trh::even_bits_table over include/trh.hpp; run by tests/test_gpu_witness.py
-tests/native/witness_test: tests/native/witness_test.cpp include/trh.hpp include/trh.h $(PKG)/libtrh.so
-	g++ -O1 -std=c++17 -Wall -Iinclude $< -o $@ -L$(PKG) -ltrh -pthread -Wl,-rpath,'$$ORIGIN/../../$(PKG)'
-
 oracle:
 	$(MAKE) -s -C oracle libtrh_oracle.so
 
 clean:
-	rm -f $(OBJS) $(CSRC)/*.q4b.o $(PKG)/libtrh.so tests/native/libtrh_q4broken.so examples/replay tests/native/multi_ctx_test tests/native/lazy29_dev_test tests/native/lazy29_alias_test tests/native/lazy29_segment_test tests/native/params_io_test tests/native/rng_fill_test tests/native/foldplan_test tests/native/perm_assembly_test tests/native/permkeygen_test tests/native/hashtocurve_vec_test tests/native/params_new_test tests/native/mock_check_test tests/native/quotient_test tests/native/transcript_test tests/native/witness_vec_test tests/native/witness_test
+	rm -f $(OBJS) $(CSRC)/*.q4b.o $(PKG)/libtrh.so $(NATIVE)
 	$(MAKE) -s -C oracle clean
 
 .PHONY: all oracle clean

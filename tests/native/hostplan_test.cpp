@@ -1,4 +1,4 @@
-// csrc/hostplan.h without a device: the range boundaries msm_host_tiled (capi.hip) cuts an MSM with host scalars at, in both modes
+// csrc/hostplan.h without a device: the range boundaries msm_host_tiled (msmapi.hip) cuts an MSM with host scalars at, in both modes
 // (host bases: equal ranges of ceil(n / ceil(n / 2^20)) pairs above 2^21; resident bases: 2^21, 2^22, the rest above 3 * 2^21), and the
 // pass plan of the NTT for every accepted size and the number of transforms its lazy passes run per launch set (ntt_lazy_chunk: the invariants
 // over log_n 12..27 and the block counts in use, and the literal values tests/test_gpu_domain_chunks.py builds its cases on).  The range counts asserted here are the ones the GPU tests expect from trh_stat
@@ -213,7 +213,7 @@ int main() {
             // per_item = 16 * 2^20 * 12 + 1 = 201326593, floor(2^30 / 201326593) = 5 -> 5 + 1, not adaptive (fused zeroing), LDS bin sort
             {(size_t)1 << 20, 6, 0, 1, 16, 16, 16, 5, 2, false, true, false},
             {(size_t)1 << 20, 6, 0, 4, 16, 16, 16, 6, 1, false, true, false},
-            // the table trh_bases_precompute(0) attaches to 2^14 + 1 bases has 12-bit windows (capi.hip: floor(log2 n) - 2, a COPY of that rule: the
+            // the table trh_bases_precompute(0) attaches to 2^14 + 1 bases has 12-bit windows (bases.hip: floor(log2 n) - 2, a COPY of that rule: the
             // GPU test asserts the width the entry returns): one bucket set, the sampler is asked
             {((size_t)1 << 14) + 1, 70, 12, 4, 12, 22, 1, 64, 2, true, true, true},
         };

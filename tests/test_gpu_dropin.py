@@ -80,7 +80,7 @@ def test_dropin_replay_k10_matches_oracle(level):
         assert res["mode"] == "dropin-batched-blocks"
 
 
-# the sizes at which msm_host_tiled (csrc/capi.hip; boundaries in csrc/hostplan.h) changes the number of ranges
+# the sizes at which msm_host_tiled (csrc/msmapi.hip; boundaries in csrc/hostplan.h) changes the number of ranges
 HOST_SPLIT = 1 << 21          # host bases: one range up to here, equal ranges of about 2^20 pairs above
 RES_SPLIT = 3 << 21           # resident bases: one range up to here; above: 2^21, 2^22, the rest
 RES_OFFSET = 1000
@@ -155,6 +155,65 @@ def test_host_msm_tiles_vs_oracle(split_set):
     assert (api.best_multiexp(curve, sc[:0], bases[:0])[:8] == ident).all()
     assert (api.best_multiexp(curve, sc[:1], bases[:1])[:8] == cpu_ref.to_affine(curve, cpu_ref.best_multiexp(curve, sc[:1], bases[:1], threads=1))).all()
     assert api.stat("msm_host_ranges") == 1
+
+
+CACHE_SCRIPT = r"""
+import numpy as np
+import cpu_ref
+from tiny_ram_halo2_amd import api, synth
+api.init(0)
+assert api.get_option("bases_cache") == 1
+curve, n = "pallas", 1024
+bases = np.ascontiguousarray(cpu_ref.gen_bases_hashed(curve, 0xCAC4E, n + 1)[:n])   # ONE array for every call: the pointer is part of the key
+spare = cpu_ref.gen_bases_hashed(curve, 0xCAC4E, n + 1)[n].copy()
+sc = np.ascontiguousarray(synth.field_elements(0x5CA1, n))
+oracle = lambda m: cpu_ref.to_affine(curve, cpu_ref.best_multiexp(curve, sc[:m], bases[:m], threads=8))
+
+def call(m):
+    api.io_stats(reset=True)
+    got = api.best_multiexp(curve, sc[:m], bases[:m])
+    return got[:8], int(api.io_stats(reset=True)["h2d_bytes"])
+
+want, up = oracle(n), []
+for i in range(6):
+    got, b = call(n)
+    assert (got == want).all(), i
+    up.append(b)
+print("same", *up)
+bases[n // 2] = spare                 # another valid point, in place: same pointer, same length
+want, up = oracle(n), []
+for i in range(2):
+    got, b = call(n)
+    assert (got == want).all(), i
+    up.append(b)
+print("changed", *up)
+want, up = oracle(n - 1), []
+for i in range(3):
+    got, b = call(n - 1)
+    assert (got == want).all(), i
+    up.append(b)
+print("below", *up)
+api.shutdown()
+print("shutdown ok")
+"""
+
+
+def test_bases_cache_serves_resident_sets_and_never_a_stale_one():
+    """option bases_cache = 1 (off by default; csrc/basescache.h holds the policy, csrc/msmapi.hip best_multiexp_host the calls) at its own
+    threshold, n = 1024, with ONE bases array and ONE scalar array kept alive: every result against cpu_ref.best_multiexp, and the bytes
+    the call sent up (trh_io_stats; only the staged uploads count, a resident set's own upload is a plain copy).  Six identical calls: 96 n
+    bytes at the first sighting (scalars and bases), 32 n from the second on (the set is resident; the fifth call is its fourth use and
+    builds the fixed-base table).  One base changed in place: 96 n again and the NEW point (the stale copy is not served), then 32 n.
+    n = 1023 is below the threshold: 96 n every time.  trh_shutdown destroys the cached handles and returns."""
+    from common import run_with_options
+    n = 1024
+    text = run_with_options(CACHE_SCRIPT, {"TRH_BASES_CACHE": "1"})
+    print(text)
+    out = dict((ln.split()[0], [int(v) for v in ln.split()[1:]]) for ln in text.splitlines() if ln.startswith(("same", "changed", "below")))
+    assert text.rstrip().endswith("shutdown ok")
+    assert out["same"] == [96 * n] + [32 * n] * 5
+    assert out["changed"] == [96 * n, 32 * n]
+    assert out["below"] == [96 * (n - 1)] * 3
 
 
 @pytest.mark.parametrize("field,log_n,count", [("fp", 12, 37), ("fq", 16, 9), ("fp", 20, 5)])

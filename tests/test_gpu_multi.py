@@ -1,7 +1,7 @@
 """GPU tests (-m gpu) of the multi-GPU paths of the C ABI on the ONE GPU of the test box: a device group that lists device 0 several
 times makes every shard its own context -- own stream, own pinned rings, own copy threads -- so the code that feeds and collects G
 devices runs for real, only the links are shared (the reference proves in one process, /root/reference/src/test_utils.rs:37-54).
-  * host scalars into a range-sharded base set: one uploader thread per shard (csrc/capi.hip msm_sharded), same point as one context;
+  * host scalars into a range-sharded base set: one uploader thread per shard (csrc/msmapi.hip msm_sharded), same point as one context;
   * option force_no_peer = 1 (a subprocess): device-resident scalars reach every shard through pinned host memory (stage_d2d_via_host), same point;
   * the block pool behind trh_malloc / trh_free with a tiny cap (TRH_POOL_MB=1, a subprocess): eviction, double free, trim.
 The group is [0] * 8 everywhere in the suite (trh_init_multi accepts only the list it was first given)."""

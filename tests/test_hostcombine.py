@@ -79,6 +79,20 @@ def test_device_block_pool_index():
         assert r.returncode == 0 and "devpool: ok" in r.stdout, r.stdout + r.stderr
 
 
+def test_bases_cache_policy():
+    """csrc/basescache.h, the policy of the opt-in bases cache behind trh_best_multiexp_*, with made-up pointers and handles: a set is a
+    candidate at its first sighting and resident from its second, a changed fingerprint is another set, the ring holds 16 candidates and
+    the LRU 8 sets, an evicted or cleared handle comes back exactly once, "precompute" is said at the fourth use only, and the
+    fingerprint equals an independently computed literal"""
+    src = os.path.join(ROOT, "tests", "native", "basescache_test.cpp")
+    with tempfile.TemporaryDirectory() as tmp:
+        exe = os.path.join(tmp, "basescache_test")
+        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", exe])
+        r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0 and "basescache: ok" in r.stdout, r.stdout + r.stderr
+        assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr
+
+
 def test_host_range_cuts_and_ntt_pass_plan():
     """csrc/hostplan.h, the host-side shape decisions of the two headline operations: the range boundaries of an MSM with host scalars
     (both modes, sizes on and around the 2^21 and 3 * 2^21 thresholds, a ragged last range, 2^31 - 1), the NTT's pass plan for

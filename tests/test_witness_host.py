@@ -1,14 +1,17 @@
 """No device: csrc/witness.h on the host and the host side of the packed witness intake.
 
   witness_vec_test   the header's functions in a stand-alone program under address + undefined sanitizers (tests/native/witness_vec_test.cpp,
-                     built by `make`; it never loads libtrh), its lines against Python integers and oracle/pasta.py's limbs
+                     built by program() below as `make` builds it; it never loads libtrh), its lines against Python integers and oracle/pasta.py's limbs
   pack_bits          against an explicit bit loop
   the ABI            the four entries are exported, answer TRH_ENODEV without a device, and keep the stream out of their parameter lists"""
+import atexit
 import ctypes
 import os
 import random
 import re
+import shutil
 import subprocess
+import tempfile
 
 import numpy as np
 import pytest
@@ -17,15 +20,26 @@ import pasta as o
 from tiny_ram_halo2_amd import api, witness
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PROGRAM = os.path.join(ROOT, "tests", "native", "witness_vec_test")
+PROGRAM = [""]  # program()
 ENTRIES = ["trh_columns_from_ints_dev", "trh_columns_from_ints_host", "trh_even_odd_split_dev", "trh_even_bits_table_dev"]
 M64 = (1 << 64) - 1
 EVEN = int("01" * 32, 2)
 
 
+def program():
+    """the stand-alone program, compiled here once per run with the Makefile's command line into a directory of its own (as test_foldplan.py
+    and test_hashtocurve_host.py do): the tests without a device then need no build product under tests/"""
+    if not os.path.exists(PROGRAM[0]):
+        tmp = tempfile.mkdtemp(prefix="witness_vec_test_")
+        atexit.register(shutil.rmtree, tmp, ignore_errors=True)
+        PROGRAM[0] = os.path.join(tmp, "witness_vec_test")
+        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                               os.path.join(ROOT, "tests", "native", "witness_vec_test.cpp"), "-o", PROGRAM[0]])
+    return PROGRAM[0]
+
+
 def run(lines):
-    assert os.path.exists(PROGRAM), "tests/native/witness_vec_test is missing: run `make`"
-    p = subprocess.run([PROGRAM], input="".join(line + "\n" for line in lines), capture_output=True, text=True, timeout=60)
+    p = subprocess.run([program()], input="".join(line + "\n" for line in lines), capture_output=True, text=True, timeout=60)
     assert p.returncode == 0, p.stderr[-2000:]   # a sanitizer report ends the program with a non-zero status
     out = p.stdout.split("\n")[:-1]
     assert len(out) == len(lines)

@@ -64,7 +64,7 @@ const Options& opt();
         if (_rc != TRH_OK) return _rc; \
     } while (0)
 
-void pool_trim();  // capi.hip: returns the idle blocks of trh_malloc / trh_free to the device
+void pool_trim();  // devalloc.hip: returns the idle blocks of trh_malloc / trh_free to the device
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
@@ -164,7 +164,7 @@ struct MsmScratch {
     bool tile_sum_valid = false;
     u64 tile_sum[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     u64 range_tiles = 0;  // tiles of the last MSM enqueue that ran as range tiles, 0 if it did not (tests: the branch was taken)
-    u64 host_ranges = 0;  // ranges of the last MSM with host scalars (msm_host_tiled in capi.hip; tests)
+    u64 host_ranges = 0;  // ranges of the last MSM with host scalars (msm_host_tiled in msmapi.hip; tests)
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool ev_valid = false;
 };
@@ -276,6 +276,18 @@ struct Enter {
     ::trh::Enter _trh_enter; \
     TRH_TRY(_trh_enter.begin((hipStream_t)(stream), (cptr)))
 
+// Scope of a few HIP calls that belong to one device, outside any context: remembers the calling thread's current device, switches to
+// `device` (err: what the switch answered) and switches back.  Enter does its own: it restores the active context as well.
+struct DeviceScope {
+    int prev = -1, device;
+    hipError_t err = hipSuccess;
+    explicit DeviceScope(int device_) : device(device_) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != device) err = hipSetDevice(device);
+    }
+    ~DeviceScope() { if (prev >= 0 && prev != device) (void)hipSetDevice(prev); }
+};
+
 // roctx range around a primitive (rocprofv3 --marker-trace); resolved with dlopen, a no-op when the library is absent
 struct Range {
     explicit Range(const char* name);
@@ -373,7 +385,7 @@ int field_powers_device(int field, void* out_dev, size_t n, const u64 x_mont[4],
 // msm.hip
 int msm_enqueue(int curve, const void* bases_dev, const void* bases_z_or_null, const void* scalars_dev, size_t n, size_t batch,
                 size_t scalar_stride_elems, int mont, hipStream_t s, const MsmFixedBase* fb = nullptr, const void* tails_dev = nullptr, MsmFlags flags = {});
-// trh_msm_dev with the flags of its one msm_enqueue (capi.hip; the self-test runs the pipeline and the quad combine through it)
+// trh_msm_dev with the flags of its one MSM launch (msmapi.hip; the self-test runs the pipeline and the quad combine through it)
 int msm_dev_flagged(::trh_bases* bases, size_t offset, const void* scalars_dev, size_t n, int mont, void* stream, uint64_t out[12], MsmFlags flags);
 size_t msm_small_max_pairs();  // the largest MSM msm_small_kernel takes (batches of up to four, no window override)
 int msm_fixed_base_windows(int c);
@@ -386,6 +398,8 @@ int msm_build_table(int curve, const void* bases_dev, size_t n, int c, void* tab
 constexpr size_t ZREC = 128;
 int msm_convert_bases(int curve, const void* in_dev, void* out_dev, size_t n, hipStream_t s);
 int msm_finish(int curve, hipStream_t s, u64* out_xyz, size_t batch);
+// msmapi.hip: TRH_EBUSY (the error text opens with "<what>: ") while the entered context holds an enqueued MSM nobody has collected
+int msm_idle(const char* what);
 int point_sum_host(int curve, const u64* pts, size_t count, u64* out);
 int bases_generate_device(int curve, u64 s0, u64 d, u64 first, size_t n, void* out_dev, hipStream_t s);
 void msm_release();
@@ -401,21 +415,3 @@ int sqrt_table_device(int field_id, const void** out);
 void hashtocurve_release();
 
 }  // namespace trh
-
-struct trh_bases {
-    int curve;
-    void* d_xy;
-    size_t n;
-    bool owned;
-    void* d_z = nullptr;  // owned (immutable) sets: the bases converted once to the lazy Montgomery domain
-    void* d_table = nullptr;  // trh_bases_precompute: W x n shifted copies (see MsmFixedBase)
-    trh::MsmFixedBase fb{nullptr, 0, 0};
-    trh::Ctx* owner = nullptr;  // the context (device) the memory lives on
-    // handles are shared by every context of their device: the lazily built copies (d_z, d_table) are created / replaced under this lock
-    // (two threads on two contexts running their first MSM over the same set would otherwise both convert, and one copy would leak)
-    std::mutex mu;
-    // range-sharded set (trh_init_multi): shard g holds bases [shard_off[g], shard_off[g + 1]) on its own context's device;
-    // d_xy is null and the per-shard handles carry the device memory
-    std::vector<trh_bases*> shards;
-    std::vector<size_t> shard_off;
-};

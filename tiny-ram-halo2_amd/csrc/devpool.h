@@ -1,4 +1,4 @@
-// Bookkeeping of the device blocks trh_malloc / trh_free keep for reuse (capi.hip).  No HIP in here: the index is compiled and run on
+// Bookkeeping of the device blocks trh_malloc / trh_free keep for reuse (devalloc.hip).  No HIP in here: the index is compiled and run on
 // its own by tests/native/devpool_test.cpp with made-up device ids (the GPU box has one device; the eviction order across devices is
 // what went wrong in round 3: the "largest block of this device" was the largest block of the highest-numbered device).
 #pragma once

@@ -1,7 +1,7 @@
 // ff::Field::sqrt and GroupEncoding (the 32-byte compressed points of pasta_curves 0.4.1: `to_bytes` / `from_bytes`) on the device, and the
 // host-side single-point forms a transcript needs.  What they serve: `Params::read` (halo2_proofs 0.2.0 poly/commitment.rs) decodes
 // 2 * 2^k + 2 compressed points -- one square root each in a field of two-adicity 32 -- before a single base can be uploaded; here the 32-byte
-// encodings cross the link and one kernel turns them into the resident 64-byte PODs (capi.hip trh_bases_create_compressed).
+// encodings cross the link and one kernel turns them into the resident 64-byte PODs (bases.hip trh_bases_create_compressed).
 // The arithmetic is csrc/fieldsqrt.h (fixed schedule: no lane of a wavefront waits for another's Tonelli-Shanks rounds); one thread per
 // element, grid-stride.  The per-field table of fieldsqrt.h lives in the context beside its other tables, uploaded at first use.
 #include <string.h>

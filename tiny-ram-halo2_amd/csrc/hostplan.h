@@ -1,5 +1,5 @@
 // Host-side shape decisions of the two headline operations, free of HIP types so that a plain C++ test can check them
-// (tests/native/hostplan_test.cpp): where msm_host_tiled (capi.hip) cuts an MSM with host scalars into ranges, how
+// (tests/native/hostplan_test.cpp): where msm_host_tiled (msmapi.hip) cuts an MSM with host scalars into ranges, how
 // ntt.hip splits a transform into passes and a batch into launch sets, the launch plan of an MSM on the device (msm.hip: route, Pippenger geometry,
 // scratch layout) as a pure function of its shape, and the plan of an IPA opening (ipa.hip, ipafold.hip: the form of its MSMs, the generator
 // collapse, every round's geometry, the size of every scratch buffer) likewise.

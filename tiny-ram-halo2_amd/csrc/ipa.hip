@@ -15,7 +15,7 @@
 #include <initializer_list>
 #include <utility>
 
-#include "ctx.h"
+#include "bases.h"
 #include "devmem.h"
 #include "hostcombine.h"
 #include "hosthelper.h"
@@ -713,7 +713,7 @@ int trh_ipa_create_proof(trh_bases_t g_w, const uint64_t u_xy[8], uint32_t k, co
     TRH_ENTER(stream);
     Range range("trh_ipa_create_proof");
     if (g_w->owner && g_w->owner->device != ctx().device) { set_error("ipa_create_proof: the base set lives on another device than the calling context"); return TRH_EINVAL; }
-    if (ctx().msm.pending_curve >= 0) { set_error("ipa_create_proof: this context has an enqueued MSM that was not finished"); return TRH_EBUSY; }
+    TRH_TRY(msm_idle("ipa_create_proof"));
     if (g_w->n == ((size_t)1 << k) + 2) {  // g || w || u: the resident u must be the caller's
         uint64_t last[8];
         TRH_HIP_TRY(hipMemcpy(last, (const char*)g_w->d_xy + (g_w->n - 1) * 64, 64, hipMemcpyDeviceToHost));

@@ -18,7 +18,7 @@
 
 #include <vector>
 
-#include "ctx.h"
+#include "bases.h"
 #include "devmem.h"
 #include "foldplan.h"
 #include "hostcombine.h"

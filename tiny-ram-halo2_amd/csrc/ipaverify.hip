@@ -16,7 +16,7 @@
 
 #include <vector>
 
-#include "ctx.h"
+#include "bases.h"
 #include "devmem.h"
 
 struct trh_ipa_msm {
@@ -398,7 +398,7 @@ int trh_ipa_msm_eval(trh_ipa_msm_t m, void* stream, int* is_identity, uint64_t o
     TRH_TRY(check_msm(m, "ipa_msm_eval"));
     hipStream_t s = (hipStream_t)stream;
     m->stream = s;
-    if (ctx().msm.pending_curve >= 0) { set_error("ipa_msm_eval: this context has an enqueued MSM that was not finished"); return TRH_EBUSY; }
+    TRH_TRY(msm_idle("ipa_msm_eval"));
     // the small MSM: the appended terms, and w / u wherever the full-range MSM does not carry them
     std::vector<uint64_t> sc(m->other_scalars), bs(m->other_bases);
     auto push = [&](const uint64_t* scalar, const uint64_t* xy) { sc.insert(sc.end(), scalar, scalar + 4); bs.insert(bs.end(), xy, xy + 8); };
