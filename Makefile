@@ -14,10 +14,10 @@ ID_OBJ := $(CSRC)/capi.o
 # driver programs over include/trh.hpp that share one command line, each run by the GPU test of its subject: Params::write / read
 # (test_gpu_encoding.py), trh::Rng (test_gpu_rng.py), trh::PermutationAssembly (test_gpu_permkeygen.py), trh::Params::create
 # (test_gpu_hashtocurve.py), GateEvaluator::check and lookup_check (test_gpu_mock.py), trh::QuotientTerms (test_gpu_quotient.py),
-# columns_from_ints / even_odd_split / even_bits_table (test_gpu_witness.py)
-HPP_TESTS := $(addprefix tests/native/,params_io_test rng_fill_test perm_assembly_test params_new_test mock_check_test quotient_test witness_test)
+# columns_from_ints / even_odd_split / even_bits_table (test_gpu_witness.py), trh::mem_table (test_gpu_memtable.py)
+HPP_TESTS := $(addprefix tests/native/,params_io_test rng_fill_test perm_assembly_test params_new_test mock_check_test quotient_test witness_test memtable_test)
 NATIVE := examples/replay tests/native/libtrh_q4broken.so $(HPP_TESTS) $(addprefix tests/native/,multi_ctx_test lazy29_dev_test lazy29_alias_test lazy29_segment_test \
-    foldplan_test permkeygen_test hashtocurve_vec_test transcript_test witness_vec_test)
+    foldplan_test permkeygen_test hashtocurve_vec_test transcript_test witness_vec_test memtable_vec_test)
 
 all: $(PKG)/libtrh.so oracle $(NATIVE)
 
@@ -89,6 +89,12 @@ tests/native/transcript_test: tests/native/transcript_test.cpp tests/native/tran
 # csrc/witness.h (integers to field elements, the even-bits decomposition) on the host, under address + undefined sanitizers: reads cases,
 # prints limbs; never loads libtrh; run by tests/test_witness_host.py (which checks it against Python integers)
 tests/native/witness_vec_test: tests/native/witness_vec_test.cpp $(CSRC)/witness.h $(CSRC)/field.h
+	g++ -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -fsanitize=address,undefined -fno-sanitize-recover=all $< -o $@
+
+# csrc/memtable.h (the Mem table's plan, the rule of a log record, one row's thirteen integers) on the host, under address + undefined
+# sanitizers: reads cases, prints results; never loads libtrh; run by tests/test_memtable_host.py (which checks it against
+# tests/memtable_model.py)
+tests/native/memtable_vec_test: tests/native/memtable_vec_test.cpp $(CSRC)/memtable.h $(CSRC)/witness.h $(CSRC)/field.h
 	g++ -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -fsanitize=address,undefined -fno-sanitize-recover=all $< -o $@
 
 oracle:

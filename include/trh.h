@@ -709,6 +709,46 @@ int trh_columns_from_ints_host(int field_id, const trh_ints_args_t* args);
 int trh_even_odd_split_dev(int field_id, const trh_ints_args_t* args);
 int trh_even_bits_table_dev(int field_id, const trh_even_bits_table_args_t* args);
 
+/* ---- the memory-consistency table: access log to sorted, checked columns, on the device ---------------------------------------------------
+ * The one table of the reference's circuit whose rows are no per-row function of the trace (its Mem chip over the trace's access log).  The
+ * host hands over the log as it was executed -- four word arrays -- and the tape; the device groups the accesses by address (a stable radix
+ * sort on the address alone, so that time order survives inside a run), opens every run with an Init row (the tape word that lives at the
+ * address, or 0; tape word i lives at address i * word_bits / 8 and has a run whether it is accessed or not), carries the most recently
+ * stored value down each run and writes 13 columns of n rows, back to back in dst (csrc/memtable.h has the rules in full):
+ *   s_trace  address  time  init  store  load  value  addr_inc  time_inc  addr_inc_even  addr_inc_odd  time_inc_even  time_inc_odd
+ * rows = #runs + m rows are live; rows `rows` .. n - 1 are WRITTEN as zero.  src_index (optional) receives the log index of every row,
+ * 0xFFFFFFFF for Init rows and behind the table.
+ * Refusals (TRH_EINVAL), all with NOTHING written to dst or src_index:
+ *   a log record with an address, time or value >= 2^word_bits, a time of 0 or one that does not exceed the record before it:
+ *     trh_last_error() names the FIRST such log index;
+ *   rows > max_rows: args->rows reports the rows the table would need;
+ *   an unknown field, word_bits odd or outside 2 .. 32, a tape (t > 0) with word_bits % 8 != 0 or an address >= 2^word_bits, max_rows > n,
+ *     t + 2 m >= 2^31, a null array that is not empty, a dst that is not 16-byte aligned, a word array that is not 4-byte aligned.
+ * A load whose claimed value differs from the value the table carries to its row is REPORTED, not refused (a prover may want to prove that
+ * a trace is wrong): n_inconsistent counts them, first_inconsistent is the smallest log index among them (m when there is none); the
+ * `value` column holds the carried value either way.  m == 0 && t == 0 succeeds with rows == 0 and zeroes dst.
+ * The stream travels in the struct, as in trh_ints_args_t.  The entry knows `rows` before it writes and returns it, so it is NOT
+ * asynchronous: it synchronises with the host exactly twice -- once on args->stream after the sort, to read the log's verdict and the row
+ * count, and once when its scratch returns to the device pool (trh_free waits for the device as hipFree does), which is also when the count
+ * of inconsistent loads has landed.  Scratch is one block of the pool of trh_malloc, sized by memtable::make_plan (about 21 bytes per
+ * record and 24 per row); the entry allocates nothing else.
+ * trh_stat: "memtable_rows", "memtable_sort_passes" (ceil(word_bits / 8); 0 for an empty call) and "memtable_tiles" (the smallest tile count
+ * among the sort over the records, the scan over the records and the scan over the rows: above 1, every stage crossed a tile boundary)
+ * describe the last call on this context that got as far as its row count.                                                                  */
+typedef struct trh_mem_table_args {
+    uint32_t word_bits;                       /* even, 2 .. 32 */
+    const uint32_t *address, *time, *value;   /* device, m each, in execution order */
+    const uint32_t *store_bits;               /* device, ceil(m / 32) words: bit i & 31 of word i >> 5 is set for a store, clear for a load */
+    size_t m;
+    const uint32_t *tape; size_t t;           /* device; may be null when t == 0 */
+    void*  dst;                               /* device, 13 x n x 4 u64, 16-byte aligned, canonical Montgomery words */
+    size_t n, max_rows;                       /* rows per column; the table's extent, max_rows <= n */
+    uint32_t* src_index;                      /* optional device, n words */
+    void*  stream;
+    uint64_t rows, n_inconsistent, first_inconsistent;   /* out */
+} trh_mem_table_args_t;
+int trh_mem_table_dev(int field_id, trh_mem_table_args_t* args);
+
 /* ---- element-wise field / group ops on device memory (parity tests of the device arithmetic;
  *      op: 0 add, 1 sub, 2 mul, 3 sqr, 4 neg, 5 inv, 6 to_mont, 7 from_mont) ------------------ */
 int trh_field_op_dev(int field, int op, const void* a_dev, const void* b_dev, void* out_dev, size_t n, void* stream);
@@ -744,7 +784,8 @@ int trh_stream_synchronize(void* stream);
  * "msm_range_tiles": the tiles of the last MSM enqueue on this context that ran as range tiles of at most 2^25 pairs (0 when it did not);
  * "ntt_tableless_passes": of the last transform, the passes after the first that had no inter-pass twiddle table and computed their twiddles
  * per element (1 from 2^26 elements, where the last pass's table would exceed 1.125 GiB; 0 below);
- * "lookup_check_probes": the slots of the set visited by the two kernels (insert, probe) of the last trh_lookup_check_dev on this context. */
+ * "lookup_check_probes": the slots of the set visited by the two kernels (insert, probe) of the last trh_lookup_check_dev on this context;
+ * "memtable_rows", "memtable_sort_passes", "memtable_tiles": the last trh_mem_table_dev on this context (described with that entry). */
 int trh_stat(const char* name, uint64_t* value);
 /* GPU-side timing without HIP headers: events recorded on a stream between the steps (a hipEvent_t each), read afterwards.
  * trh_event_elapsed_ms waits for `end` and returns the device time between the two records. */

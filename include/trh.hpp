@@ -644,6 +644,18 @@ inline void even_bits_table(Field f, uint32_t word_bits, void* dst_dev, size_t n
     check(trh_even_bits_table_dev((int)f, &a), "even_bits_table");
 }
 
+// ---- the memory-consistency table (trh_mem_table_dev): an access log in execution order -> the 13 sorted, checked columns -----------------
+// address / time / value: m resident words each; store_bits: ceil(m / 32) resident bitmap words; tape: t resident words (null for none);
+// dst_dev: 13 x n elements.  Throws (check) on a refused log or one that needs more than max_rows rows.  Synchronises with the host.
+struct MemTableResult { uint64_t rows, n_inconsistent, first_inconsistent; };
+inline MemTableResult mem_table(Field f, uint32_t word_bits, const uint32_t* address_dev, const uint32_t* time_dev, const uint32_t* value_dev, const uint32_t* store_bits_dev,
+                                size_t m, const uint32_t* tape_dev, size_t t, void* dst_dev, size_t n, size_t max_rows, uint32_t* src_index_dev = nullptr,
+                                void* stream = nullptr) {
+    trh_mem_table_args_t a{word_bits, address_dev, time_dev, value_dev, store_bits_dev, m, tape_dev, t, dst_dev, n, max_rows, src_index_dev, stream, 0, 0, 0};
+    check(trh_mem_table_dev((int)f, &a), "mem_table");
+    return MemTableResult{a.rows, a.n_inconsistent, a.first_inconsistent};
+}
+
 // ---- plonk::permutation::keygen::Assembly (trh_perm_*): the copy constraints of the equality-enabled columns, the sigma columns they
 // induce -- made on the device -- and what keygen_vk / keygen_pk derive from them ---------------------------------------------------------
 // copy() merges cycles exactly as upstream does (the order of the copies decides the mapping).  Host memory, like Rng: copies and mapping()

@@ -88,6 +88,14 @@ class EvenBitsTableArgs(ctypes.Structure):
     _fields_ = [("word_bits", ctypes.c_uint32), ("dst", ctypes.c_void_p), ("n", ctypes.c_size_t), ("stream", ctypes.c_void_p)]
 
 
+class MemTableArgs(ctypes.Structure):
+    """trh_mem_table_args_t"""
+    _fields_ = [("word_bits", ctypes.c_uint32), ("address", ctypes.c_void_p), ("time", ctypes.c_void_p), ("value", ctypes.c_void_p), ("store_bits", ctypes.c_void_p),
+                ("m", ctypes.c_size_t), ("tape", ctypes.c_void_p), ("t", ctypes.c_size_t), ("dst", ctypes.c_void_p), ("n", ctypes.c_size_t), ("max_rows", ctypes.c_size_t),
+                ("src_index", ctypes.c_void_p), ("stream", ctypes.c_void_p), ("rows", ctypes.c_uint64), ("n_inconsistent", ctypes.c_uint64),
+                ("first_inconsistent", ctypes.c_uint64)]
+
+
 _SIGNATURES = {
     "trh_init": ([ctypes.c_int], ctypes.c_int),
     "trh_shutdown": ([], None),
@@ -261,6 +269,7 @@ _SIGNATURES = {
     "trh_columns_from_ints_host": ([ctypes.c_int, ctypes.POINTER(IntsArgs)], ctypes.c_int),
     "trh_even_odd_split_dev": ([ctypes.c_int, ctypes.POINTER(IntsArgs)], ctypes.c_int),
     "trh_even_bits_table_dev": ([ctypes.c_int, ctypes.POINTER(EvenBitsTableArgs)], ctypes.c_int),
+    "trh_mem_table_dev": ([ctypes.c_int, ctypes.POINTER(MemTableArgs)], ctypes.c_int),
     "trh_set_timing": ([ctypes.c_int], ctypes.c_int),
     "trh_last_timing": ([ctypes.POINTER(Timing)], ctypes.c_int),
 }

@@ -452,7 +452,8 @@ int trh_stat(const char* name, uint64_t* value) {
     const struct { const char* name; uint64_t value; } counters[] = {
         {"msm_lean_retries", m.lean_retries}, {"msm_small_launches", m.small_launches}, {"msm_chunks", m.chunks}, {"msm_unit_chunks", m.unit_chunks},
         {"msm_host_ranges", m.host_ranges}, {"msm_range_tiles", m.range_tiles}, {"ntt_tableless_passes", c.ntt_tableless_passes},
-        {"ipa_generator_collapses", c.ipa.collapses}, {"lookup_check_probes", c.lookup_check_probes}};
+        {"ipa_generator_collapses", c.ipa.collapses}, {"lookup_check_probes", c.lookup_check_probes},
+        {"memtable_rows", c.memtable_rows}, {"memtable_sort_passes", c.memtable_sort_passes}, {"memtable_tiles", c.memtable_tiles}};
     for (const auto& k : counters) if (strcmp(name, k.name) == 0) { *value = k.value; return TRH_OK; }
     if (strcmp(name, "msm_bin_sorted_windows") == 0) {  // synchronises the device: tests only
         *value = 0;

@@ -242,7 +242,8 @@ struct Ctx {
     u64 stamp = 0;
     void* lookup_scratch = nullptr;  // lookup.hip's buffers (opaque here)
     u64 lookup_check_probes = 0;     // slots visited by the two kernels of the last trh_lookup_check_dev (mockcheck.hip; tests)
-    int cu_count = 0;                // compute units of the device (persistent kernels size their grids by it); 0: not asked yet
+    u64 memtable_rows = 0, memtable_sort_passes = 0, memtable_tiles = 0;  // of the last trh_mem_table_dev that got as far as its row count (memtable.hip; tests)
+    int cu_count = 0;               // compute units of the device (persistent kernels size their grids by it); 0: not asked yet
     unsigned attr_done = 0;          // hipFuncSetAttribute is per device: bit per kernel family already configured for this context's device
     hipStream_t own_stream = nullptr;  // the multi-device MSM driver enqueues this context's shard here
     // scratch is shared by every stream that enters this context: a call on another stream than the previous one waits for it

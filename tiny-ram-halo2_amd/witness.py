@@ -10,7 +10,10 @@ the (columns, n, 4) Montgomery tensors that plonk.create_proof and mock.MockProv
     columns_from_ints(field, src, n)                  numpy array: from host memory (pageable is fine); torch device tensor: resident
     even_odd(field, words, n)                         the even-bits decomposition: w & 0x5555.., (w & 0xAAAA..) >> 1
     even_bits_table(field, word_bits, n)              the lookup table of the decomposition
-    AdviceBuilder(field, num_advice, n)               owns the advice tensor; ints / even_odd / full write into its column slices
+    AdviceBuilder(field, num_advice, n)               owns the advice tensor; ints / even_odd / full / mem_table write into its column slices
+
+The one table that is no per-row function of the trace, the memory-consistency table, is made from the access log by memtable.build
+(AdviceBuilder.mem_table): sorted, scanned and checked on the device.
 """
 from __future__ import annotations
 
@@ -194,6 +197,13 @@ class AdviceBuilder:
             limbs = torch.from_numpy(np.ascontiguousarray(limbs, dtype=np.uint64).view(np.int64))
         assert limbs.ndim == 2 and limbs.shape[1] == 4 and limbs.shape[0] <= self.n
         self._t[column, :limbs.shape[0]].copy_(limbs)
+
+    def mem_table(self, first_column: int, word_bits: int, address, time, value, is_store, tape=(), max_rows: int | None = None, stream=None, m: int | None = None):
+        """the memory-consistency table of an access log into the 13 columns first_column .. (memtable.COLUMNS, memtable.build): -> MemTable
+        whose .columns is the builder's own slice"""
+        from . import memtable
+        return memtable.build(self.field, word_bits, address, time, value, is_store, tape=tape, max_rows=max_rows, out=self._slice(first_column, len(memtable.COLUMNS)),
+                              stream=stream, m=m)
 
     def tensor(self):
         return self._t
