@@ -771,6 +771,8 @@ int trh_memcpy_d2h(void* host, const void* dev, size_t bytes);
 int trh_stream_synchronize(void* stream);
 /* counters of the calling thread's context, by name.  "msm_lean_retries": MSMs of callers that vouched for uniformly random scalars (the
  * opening's rounds) whose whole-bin LDS sort met a bin that did not fit and that were therefore run a second time with the chunked passes;
+ * "msm_lean_sorts": the MSMs enqueued that way so far, without the chunked passes behind the LDS sort (cumulative; a retry is not one), and
+ * "msm_quad_combines": the launches of the combine's quad form, which only such callers get (cumulative; for tests, like the one before);
  * "msm_bin_sorted_windows": of the last MSM's last chunk of items, the (item, window) bucket sets whose level-1 bins all fit the LDS
  * bin sort (0 when that MSM did not use it; synchronises the device, for tests);
  * "msm_small_launches": MSMs that ran as ONE launch (up to 8448 pairs, batches of up to four); "ipa_generator_collapses": openings that

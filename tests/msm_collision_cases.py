@@ -20,6 +20,9 @@ SHAPES = {
     "c18": dict(mode="override", c=18, seg_len=16, nbk=131072, tpw=4096, m=32, G=1, n=(512, 512)),
     "table16": dict(mode="table", c=16, seg_len=16, nbk=32768, tpw=16384, m=2, G=1, n=(512, 512)),
     "small": dict(mode="small", c=5),
+    # the table pipeline of the IPA opening at k = 14 (tests/ipa_collision_cases.py): the set g || w || u, the default table of 12 bits, the
+    # quad combine of the dense route; tpw and m for one item (the commitment to s') and for two (a round)
+    "ipa14": dict(mode="table", c=12, seg_len=16, nbk=2048, tpw=2048, m=1, G="q4", n=(16386, 16386)),
 }
 _rng = random.Random(0x5EED)
 FILL = [(1 << 60) + _rng.getrandbits(60) for _ in range(2048)]  # fillers: distinct multiples far from every designed value

@@ -15,6 +15,19 @@ csrc/hostplan.h by tests/native/hostplan_test.cpp -- and returns which of these 
     stale-clear            an identity base arrives while acc still holds the previous bucket's limbs (the stale-limbs guard)
     add-identity           a full addition one of whose operands is the identity
     publish-first / -direct / -last    where msm_accumulate_seg_kernel stores a run
+    head-first / -direct / -last       which of these msm_combine_q4_kernel takes as a bucket's first piece
+    heavy-handover                     a bucket of more than 64 pieces is put on the heavy list instead of being stored
+    identity-first / -middle / -last   a bucket of several pieces whose first / an inner / last piece is the identity (the quad combine)
+
+The quad combine (G = "q4": msm_combine_q4_kernel, the dense route of the IPA opening) takes the first piece from `first`, `direct` or
+`last`, adds the pieces t_lo + 1 .. t_hi one after the other (stage "combine-q4"), and hands a bucket of more than 64 pieces to
+msm_combine_heavy_kernel.
+
+Sensitivity.  Events(q, lose=(stage, event, where)) replaces the special-case branch of ONE event by "result lost": where the event is
+met (at `where`, or anywhere with where = None) the value the branch should have produced becomes the junk point LOST -- a doubling that
+was not taken, a cancellation that did not clear the accumulator, an identity that was added as if it were a point, a piece read from
+the wrong place; a lost stale-clear keeps the previous bucket's value in the register.  A case is sensitive to an event when the
+total changes under that replacement (tests/test_msm_events_model.py).
 
 The order of the entries INSIDE a bucket is decided by atomic ranks on the device (the sort; `cursor` in msm_small_kernel) and is not
 deterministic, so it is a parameter here: "asc" (by pair index), "desc", or a dict {(window, bucket): permutation}.
@@ -25,7 +38,9 @@ from collections import Counter
 
 SKIP, FIRST, DOUBLE, CANCEL = "skip-identity", "first", "double", "cancel"
 LATE_DOUBLE, LATE_CANCEL, RESTART, STALE, ADD_ID = "late-double", "late-cancel", "restart-after-cancel", "stale-clear", "add-identity"
+HEAD_FIRST, HEAD_DIRECT, HEAD_LAST, HANDOVER = "head-first", "head-direct", "head-last", "heavy-handover"
 HEAVY_PIECES = 64
+LOST = 0x1057_0000_0BAD_C0DE_0000_1057_0BAD_C0DE_1057  # the junk point of a lost result: far from every designed value and every filler
 SMALL_C, SMALL_NBK = 5, 16
 
 
@@ -58,10 +73,19 @@ def recode_small(s):
 class Events:
     """what the stages met: a Counter over (stage, event), and the same per (stage, event, window, bucket) where a bucket is known"""
 
-    def __init__(self, q):
+    def __init__(self, q, lose=None):
         self.q = q
         self.n = Counter()
         self.at = Counter()
+        self.lose, self.lost = lose, 0  # the one event whose result is lost, and how often that happened
+
+    def loses(self, stage, event, where=None):
+        if self.lose is None or (stage, event) != tuple(self.lose[:2]):
+            return False
+        if self.lose[2] is not None and (where is None or tuple(self.lose[2]) != tuple(where)):
+            return False
+        self.lost += 1
+        return True
 
     def note(self, stage, event, where=None):
         self.n[(stage, event)] += 1
@@ -70,12 +94,11 @@ class Events:
 
     def add(self, stage, x, y, where=None):
         """a full addition (xyzzz_add, q4_add, the host's padd)"""
-        if x == 0 or y == 0:
-            self.note(stage, ADD_ID, where)
-        elif x == y:
-            self.note(stage, DOUBLE, where)
-        elif (x + y) % self.q == 0:
-            self.note(stage, CANCEL, where)
+        event = ADD_ID if x == 0 or y == 0 else DOUBLE if x == y else CANCEL if (x + y) % self.q == 0 else None
+        if event:
+            self.note(stage, event, where)
+            if self.loses(stage, event, where):
+                return LOST
         return (x + y) % self.q
 
     def has(self, stage, event, where=None):
@@ -140,25 +163,35 @@ def accumulate(ev, lst, seg_len, window=0, segments=None):
                     first[t] = reg
                     ev.note("accumulate", "publish-first", (window, B))
                 else:
-                    direct[B] = reg
+                    direct[B] = LOST if ev.loses("accumulate", "publish-direct", (window, B)) else reg
                     ev.note("accumulate", "publish-direct", (window, B))
                 is_first, fresh, terms, cancelled, B = False, True, 0, False, b
             w = (window, B)
             if v == 0:
                 ev.note("accumulate", SKIP, w)
-                if fresh:
+                if ev.loses("accumulate", SKIP, w):  # the identity record taken for a point
+                    reg, fresh, terms = LOST, False, terms + 1
+                elif fresh:
                     if reg:
                         ev.note("accumulate", STALE, w)
+                        if ev.loses("accumulate", STALE, w):
+                            continue  # the previous bucket's limbs stay in the register
                     reg = 0
             elif fresh:
-                ev.note("accumulate", RESTART if cancelled else FIRST, w)
-                reg, fresh, terms = v, False, 1
+                e = RESTART if cancelled else FIRST
+                ev.note("accumulate", e, w)
+                reg, fresh, terms = (LOST if ev.loses("accumulate", e, w) else v), False, 1
             elif reg == v:
-                ev.note("accumulate", DOUBLE if terms == 1 else LATE_DOUBLE, w)
-                reg, terms = 2 * v % q, terms + 1
+                e = DOUBLE if terms == 1 else LATE_DOUBLE
+                ev.note("accumulate", e, w)
+                reg, terms = (LOST if ev.loses("accumulate", e, w) else 2 * v % q), terms + 1
             elif (reg + v) % q == 0:
-                ev.note("accumulate", CANCEL if terms == 1 else LATE_CANCEL, w)
-                reg, fresh, terms, cancelled = 0, True, 0, True
+                e = CANCEL if terms == 1 else LATE_CANCEL
+                ev.note("accumulate", e, w)
+                if ev.loses("accumulate", e, w):
+                    reg, terms = LOST, terms + 1
+                else:
+                    reg, fresh, terms, cancelled = 0, True, 0, True
             else:
                 reg, terms = (reg + v) % q, terms + 1
         w = (window, B)
@@ -166,25 +199,40 @@ def accumulate(ev, lst, seg_len, window=0, segments=None):
             first[t] = reg
             ev.note("accumulate", "publish-first", w)
         elif stop == total or lst[stop][0] != B:  # cur_end == stop
-            direct[B] = reg
+            direct[B] = LOST if ev.loses("accumulate", "publish-direct", w) else reg
             ev.note("accumulate", "publish-direct", w)
         else:
-            last[t] = reg
+            last[t] = LOST if ev.loses("accumulate", "publish-last", w) else reg
             ev.note("accumulate", "publish-last", w)
     return first, last, direct
 
 
 def combine_bucket(ev, b, S, E, pieces, seg_len, G, window=0):
-    """msm_combine_kernel<G> / msm_combine_heavy_kernel for bucket b = entries [S, E) of the list"""
+    """msm_combine_kernel<G> (G = "q4": msm_combine_q4_kernel) / msm_combine_heavy_kernel for bucket b = entries [S, E) of the list"""
     first, last, direct = pieces
     t_lo, t_hi = S // seg_len, (E - 1) // seg_len
     w = (window, b)
     if S == t_lo * seg_len:
-        head = first[t_lo]
+        head, choice = first[t_lo], HEAD_FIRST
     elif E <= (t_lo + 1) * seg_len:
-        head = direct[b]
+        head, choice = direct[b], HEAD_DIRECT
     else:
-        head = last[t_lo]
+        head, choice = last[t_lo], HEAD_LAST
+    if G == "q4":
+        if t_hi - t_lo > HEAVY_PIECES:
+            ev.note("combine-q4", HANDOVER, w)
+            if ev.loses("combine-q4", HANDOVER, w):
+                return LOST  # neither kernel stores the bucket: whatever the buffer held
+        else:
+            ev.note("combine-q4", choice, w)
+            acc = LOST if ev.loses("combine-q4", choice, w) else head
+            if t_hi > t_lo and head == 0:
+                ev.note("combine-q4", "identity-first", w)
+            for t in range(t_lo + 1, t_hi + 1):  # one quad, the pieces one after the other
+                if first[t] == 0:
+                    ev.note("combine-q4", "identity-last" if t == t_hi else "identity-middle", w)
+                acc = ev.add("combine-q4", acc, first[t], w)
+            return acc
     if t_hi - t_lo > HEAVY_PIECES:  # one workgroup: thread 0 takes the head, the threads stride over the other pieces, LDS tree
         lanes = [0] * 256
         lanes[0] = head
@@ -277,9 +325,14 @@ def horner(ev, sums, W, c):
 
 def run_pipeline(q, a, s, c, seg_len, m, G=1, quad=False, table=False, order="asc"):
     """the per-window pipeline (table: the fixed-base form, one bucket set) -> (Events, result)"""
-    ev = Events(q)
-    nbk = 1 << (c - 1)
     lists = window_lists(q, a, [recode_pipeline(x, c) for x in s], flat_c=c if table else 0, order=order)
+    return run_lists(q, lists, c, seg_len, m, G, quad, table)
+
+
+def run_lists(q, lists, c, seg_len, m, G=1, quad=False, table=False, lose=None):
+    """run_pipeline behind the sort: `lists` as window_lists makes them; lose: see Events"""
+    ev = Events(q, lose)
+    nbk = 1 << (c - 1)
     sums = {}
     for j, lst in lists.items():
         pieces = accumulate(ev, lst, seg_len, j)

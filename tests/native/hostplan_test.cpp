@@ -251,6 +251,8 @@ int main() {
             {512, 512, 1, 0, 18, 18, 16, 131072, 4096, 32, 16, 1},
             {512, 512, 1, 16, 0, 16, 16, 32768, 16384, 2, 64, 1},       // "table16": one bucket set, slices of 2
             {512, 6143, 8, 0, 0, 8, 16, 128, 128, 1, 1, 1},             // eight items: the plan's own c = 8, adaptive segments
+            {16386, 16386, 1, 12, 0, 12, 16, 2048, 2048, 1, 8, 4},      // "ipa14" (tests/ipa_collision_cases.py): the opening's commitment to s' at k = 14 ...
+            {16386, 16386, 2, 12, 0, 12, 16, 2048, 2048, 1, 8, 4},      // ... and its rounds 0 and 1: one set of 2048 buckets, slices of one bucket
         };
         for (const auto& r : rows) for (size_t n : {r.n_lo, (r.n_lo + r.n_hi) / 2, r.n_hi}) {
             const MsmShape sh{n, r.batch, r.fc, r.ov, 4};
@@ -269,6 +271,24 @@ int main() {
             if (r.fc) {  // the quad reduction takes this shape: 16384 quads of 2 buckets, 256 workgroups of 64 quads
                 expect((size_t)p.tpw * 4 * p.Ws <= ((size_t)1 << 16) && p.nbk % p.tpw == 0 && p.tpw >= 64, "collision shape: the table shape passes the quad gate at tpw", n, p.tpw);
             } else expect(p.Ws > 8, "collision shape: more than 8 bucket sets keep the thread-per-slice reduction", n, p.Ws);
+        }
+        // "ipa14", what the dense route of the opening decides from the plan (COPIES of stage_accumulate's and enqueue_pipeline's rules, as above): the
+        // quad combine needs three expected pieces per bucket and at most 8 bucket sets in the launch, the lean sort the LDS bin sort
+        for (size_t batch : {(size_t)1, (size_t)2}) {
+            const MsmPlan p = msm_plan(MsmShape{16386, batch, 12, 0, 4});
+            expect(p.W == 22 && p.ns == (size_t)22 * 16386 && p.chunk == batch, "ipa14: 22 table levels in one list, one launch set", batch, p.W);
+            expect(p.ns / ((size_t)p.nbk * p.seg_len0) == 11 && p.ns / ((size_t)p.nbk * p.seg_len0) >= 3, "ipa14: eleven expected pieces per bucket", batch, p.ns);
+            expect((size_t)p.Ws * batch <= 8, "ipa14: at most 8 bucket sets per launch (the quad combine, the quad reduction)", batch, p.Ws);
+            expect(p.use_bin_shape && p.bin_cap == 24576 && p.nbins == 16 && p.k2 == 7, "ipa14: the LDS bin sort, 16 bins of 128 buckets, 24576 entries each at most", batch, p.bin_cap);
+            expect((size_t)p.tpw * 4 * p.Ws * batch <= ((size_t)1 << 16) && p.nbk % p.tpw == 0, "ipa14: the quad reduction, one bucket per quad", batch, p.tpw);
+            expect(1100 / p.seg_len0 > HEAVY_PIECES && !p.adaptive, "ipa14: a bucket of 1100 entries spans more than HEAVY_PIECES segments of the plan's own length", batch, p.seg_len0);
+        }
+        {   // the openings of tests/test_gpu_ipa_collisions.py: small (level 0 of the table) up to k = 13, the table pipeline with one collapse to 2^12 at k = 14
+            const IpaPlan small = ipa_plan(IpaShape{13, ((size_t)1 << 13) + 2, true, 11, 24, 0, 1, SMALL_MAX_N});
+            const IpaPlan p14 = ipa_plan(IpaShape{14, ((size_t)1 << 14) + 2, true, 12, 22, 0, 1, SMALL_MAX_N});
+            expect(small.first_msm == IPA_MSM_SMALL_Z && small.fold_at == 0, "k = 13 with a table: msm_small_kernel over level 0", 13, small.fold_at);
+            expect(p14.first_msm == IPA_MSM_TABLE && p14.fold_at == 2 && p14.m == 4096 && p14.round(1).table && !p14.round(2).table && p14.round(2).canon == 1,
+                   "k = 14 with a table: rounds 0 and 1 over the table, then 12 small rounds over 2^12 + 2 points", 14, p14.fold_at);
         }
         // 2048 entries in one bucket at c = 3: 128 segments, beyond HEAVY_PIECES
         expect(msm_plan(MsmShape{2048, 1, 0, 3, 4}).nseg0 == 128 && 128 - 1 > HEAVY_PIECES, "collision shape: a 2048-entry bucket is heavy", 2048, HEAVY_PIECES);

@@ -11,7 +11,8 @@ how the device orders or splits the work.  Every result is compared limb for lim
 identity); up to 4096 pairs also with cpu_ref.best_multiexp.  trh_stat "msm_small_launches" proves the route; the pipeline is forced at
 small n with api.set_window_bits.  tests/test_msm_events_model.py proves on the CPU which events each case meets at which stage;
 test_gpu_q4.py runs this file again with TRH_REDUCE_Q4=0 (thread-per-slice reduction, the small kernel's shuffle sums).
-msm_combine_q4_kernel runs only for the IPA's dense_hint and is not reached from here."""
+msm_combine_q4_kernel runs only for the IPA's dense_hint: that route (the lean sort, the quad combine and its heavy hand-over, the retry) has
+its own designed cases, run through trh_ipa_create_proof, in tests/test_gpu_ipa_collisions.py (tests/ipa_collision_cases.py)."""
 import numpy as np
 import pytest
 

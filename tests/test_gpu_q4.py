@@ -78,12 +78,13 @@ def test_msm_with_q4_reduction_vs_oracle(curve, n, cbits, nb):
 
 def test_thread_per_slice_reduction_in_a_subprocess():
     """TRH_REDUCE_Q4=0 (read once per process): the MSM parity tests over the one-thread-per-slice reduction kernels, which remain the path of
-    every launch that is not a latency chain, and the collision cases (test_gpu_msm_collisions.py: the table shape then reduces by
-    msm_reduce_kernel, the small kernel sums by shuffles)"""
+    every launch that is not a latency chain, the collision cases (test_gpu_msm_collisions.py: the table shape then reduces by
+    msm_reduce_kernel, the small kernel sums by shuffles) and the openings over colliding generators (test_gpu_ipa_collisions.py: the
+    dense route then combines with msm_combine_kernel<4> under the lean gate and msm_quad_combines stays 0)"""
     if os.environ.get("TRH_REDUCE_Q4_NESTED"):
         pytest.skip("already inside the TRH_REDUCE_Q4=0 run")
     env = dict(os.environ, TRH_REDUCE_Q4="0", TRH_REDUCE_Q4_NESTED="1")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), os.path.join(ROOT, "tests", "test_gpu_q4.py"),
-                        os.path.join(ROOT, "tests", "test_gpu_msm_collisions.py"), "-q", "-x", "-m", "gpu",
+                        os.path.join(ROOT, "tests", "test_gpu_msm_collisions.py"), os.path.join(ROOT, "tests", "test_gpu_ipa_collisions.py"), "-q", "-x", "-m", "gpu",
                         "-k", "msm"], capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
     assert r.returncode == 0 and " passed" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

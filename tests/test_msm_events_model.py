@@ -158,3 +158,125 @@ def test_four_lane_cancellations_hold_in_every_order():
             cancels += ev.has(stage, M.CANCEL, (0, b))
         assert not ev.has("combine", M.DOUBLE, (0, 1))
     assert cancels >= 60  # identities on both sides are the rare outcome
+
+
+# ---------------------------------------------------------------------------------------
+# The designed MSMs of the IPA opening's dense route (tests/ipa_collision_cases.py, tests/test_gpu_ipa_collisions.py): the rows are the ones
+# the opening really forms -- the undesigned full-size scalars on coefficient 0, w and u included -- walked with the quad combine
+# ---------------------------------------------------------------------------------------
+import ipa_collision_cases as I  # noqa: E402
+
+Q4 = "combine-q4"
+NOTES_ONLY = ("identity-first", "identity-middle", "identity-last")  # positions of an identity piece: the event that can be lost there is the add-identity
+DOUBLES_Q4 = (("accumulate", M.DOUBLE), ("accumulate", M.LATE_DOUBLE), (Q4, M.DOUBLE))
+CANCELS_Q4 = (("accumulate", M.CANCEL), ("accumulate", M.LATE_CANCEL), (Q4, M.CANCEL))
+
+
+def _sensitive(q, lists, want, event, context):
+    ev, result = I.run(q, lists, lose=event)
+    assert ev.lost > 0, (context, event, "the walk never reaches the event that was to be lost")
+    assert result != want, (context, event, "the total does not change when this event's result is lost")
+
+
+@pytest.mark.parametrize("curve", sorted(ORDERS))
+@pytest.mark.parametrize("name", [c.name for c in I.CASES])
+def test_opening_cases_meet_their_events_and_are_sensitive(curve, name):
+    """for every designed MSM of an opening, as the opening forms it, in ascending and descending order: the layout the designs were made for
+    holds; the model's total is the closed form (and the exponent model's S, L_0, R_0); every named event occurs at its bucket in its stage;
+    with that one event's result lost the total changes"""
+    q, case = ORDERS[curve], I.BY_NAME[name]
+    inp, designs, rows = case.build(curve)
+    assert not I.layout_problems(q, inp, designs, rows, case)
+    assert all(len(r) == I.SET for r in rows.values())
+    walked = dict(designs, S=designs.get("S"))  # kind P: S = s_blind W over an otherwise all-zero row, a case of its own
+    for row, d in walked.items():
+        want = I.closed_form(q, inp, rows[row])
+        if d is None:
+            assert case.kind == "P" and not any(rows[row][:I.N]) and rows[row][I.N] == inp["s_blind"] and want == inp["s_blind"] * inp["omega"] % q
+        for order in ("asc", "desc"):
+            lists = I.sorted_lists(q, inp, rows[row], order)
+            ev, result = I.run(q, lists)
+            ctx = (name, curve, row, order)
+            assert result == want, ctx
+            if d is None:
+                continue
+            for e in d.expect:
+                assert ev.has(*e), (ctx, e, sorted(k for k in ev.at if k[2:] == e[2]))
+                if e[1] not in NOTES_ONLY:
+                    _sensitive(q, lists, want, e, ctx)
+            for window, bucket, needs, label in d.designed:
+                w = (window, bucket)
+                for need, options in (("skip", (("accumulate", M.SKIP),)), ("double", DOUBLES_Q4), ("cancel", CANCELS_Q4)):
+                    if need in needs:
+                        met = [(s, e) for s, e in options if ev.has(s, e, w)]
+                        assert met, (ctx, label, need)
+                        for s, e in met:
+                            _sensitive(q, lists, want, (s, e, w), (ctx, label))
+            # the accumulate's control flow under the gate: a restart after a cancellation, and stale limbs that must not be published
+            for event in (M.RESTART, M.STALE):
+                at = sorted(k[2:] for k in ev.at if k[:2] == ("accumulate", event))
+                assert at, (ctx, event)
+                changed = 0
+                for w in at:
+                    changed += I.run(q, lists, lose=("accumulate", event, w))[1] != want
+                assert changed >= 1, (ctx, event, at)
+            # the heavy bucket lies between ordinary buckets that the quad stores itself
+            hw, hb = d.heavy
+            assert ev.at[(Q4, M.HANDOVER, hw, hb)] == 1 and ev.n[(Q4, M.HANDOVER)] == 1, ctx
+            assert all(any(ev.has(Q4, h, (hw, b)) for h in (M.HEAD_FIRST, M.HEAD_DIRECT, M.HEAD_LAST)) for b in (hb - 1, hb + 1)), ctx
+
+
+@pytest.mark.parametrize("name", [c.name for c in I.CASES])
+def test_opening_multisets_meet_their_events_in_every_order(name):
+    """the multisets E1 - E6 inside an opening's rows, under the quad combine: every distinct order of a bucket of at most 8 entries, both
+    orders and a sample of random ones otherwise; no undesigned entry shares a bucket with them (asserted above)"""
+    q, case = ORDERS["pallas"], I.BY_NAME[name]
+    inp, designs, rows = case.build("pallas")
+    rng = random.Random(17)
+    offsets, targets = set(), set()
+    for row, d in designs.items():
+        lst = I.sorted_lists(q, inp, rows[row])[0]
+        ranges = M.bucket_ranges(lst)
+        for window, bucket, needs, label in d.designed:
+            if not needs:
+                continue
+            S, E = ranges[bucket]
+            offsets.add(S % 16)
+            assert S > 0 and lst[S - 1][1] != 0 and lst[S - 1][0] == bucket - 1  # it follows an ordinary bucket
+            if row != "R_0":
+                assert label.endswith(f"at offset {S % 16}"), (label, S)
+            values = [v for _, v, _ in lst[S:E]]
+            w = (window, bucket)
+            for perm in _orders(E - S, values, rng):
+                ev, total = M.bucket_events(q, lst, bucket, perm, I.SHAPE["seg_len"], "q4")
+                assert total == sum(values) % q, (label, perm)
+                targets.update(t for t in ("first", "direct", "last") if ev.has("accumulate", "publish-" + t, w))
+                if "skip" in needs:
+                    assert ev.has("accumulate", M.SKIP, w), (label, perm)
+                if "double" in needs:
+                    assert _any(ev, w, *DOUBLES_Q4), (label, perm)
+                if "cancel" in needs:
+                    assert _any(ev, w, *CANCELS_Q4), (label, perm)
+    assert len(offsets) >= 12 and targets == {"first", "direct", "last"}, (offsets, targets)
+
+
+def test_quad_combine_model_order_and_hand_over():
+    """the quad combine as msm_combine_q4_kernel does it: the first piece from first / direct / last, then t_lo + 1 .. t_hi one after the other
+    (one lane group, no tree), and more than 64 pieces go to the heavy list; 64 further pieces still stay with the quad.  The bucket starts
+    at offset 3: 13 + 64 * 16 = 1037 entries end segment 64, one more opens segment 65"""
+    q = ORDERS["pallas"]
+    for count, heavy in ((1037, False), (1038, True), (1026, False)):
+        lst = [(1, 5, i) for i in range(3)] + [(2, 3, 3 + i) for i in range(count)] + [(3, 7, 3 + count)]
+        ev = M.Events(q)
+        pieces = M.accumulate(ev, lst, 16)
+        total = M.combine_bucket(ev, 2, 3, 3 + count, pieces, 16, "q4")
+        assert total == 3 * count % q
+        assert ev.has(Q4, M.HANDOVER, (0, 2)) == heavy and ev.has(Q4, M.HEAD_LAST, (0, 2)) == (not heavy)
+        assert ev.has("combine-heavy-tree", M.DOUBLE, (0, 2)) == heavy
+        assert not ev.has("combine", M.DOUBLE) and not ev.has("combine-tree", M.DOUBLE)  # neither the one-lane nor the four-lane form
+    # serial order: 13 P (last), then 16 P five times: the running sum meets no equal piece but the second (13 + 16 != 16); with an aligned
+    # start every piece is 16 P and only the FIRST addition doubles -- the four-lane tree would double again at its last level
+    lst = [(2, 3, i) for i in range(16 * 6)]
+    ev = M.Events(q)
+    assert M.combine_bucket(ev, 2, 0, 96, M.accumulate(ev, lst, 16), 16, "q4") == 3 * 96
+    assert ev.at[(Q4, M.DOUBLE, 0, 2)] == 1 and ev.has(Q4, M.HEAD_FIRST, (0, 2))

@@ -450,7 +450,7 @@ int trh_stat(const char* name, uint64_t* value) {
     const Ctx& c = ctx();
     const MsmScratch& m = c.msm;
     const struct { const char* name; uint64_t value; } counters[] = {
-        {"msm_lean_retries", m.lean_retries}, {"msm_small_launches", m.small_launches}, {"msm_chunks", m.chunks}, {"msm_unit_chunks", m.unit_chunks},
+        {"msm_lean_retries", m.lean_retries}, {"msm_lean_sorts", m.lean_sorts}, {"msm_quad_combines", m.quad_combines}, {"msm_small_launches", m.small_launches}, {"msm_chunks", m.chunks}, {"msm_unit_chunks", m.unit_chunks},
         {"msm_host_ranges", m.host_ranges}, {"msm_range_tiles", m.range_tiles}, {"ntt_tableless_passes", c.ntt_tableless_passes},
         {"ipa_generator_collapses", c.ipa.collapses}, {"lookup_check_probes", c.lookup_check_probes},
         {"memtable_rows", c.memtable_rows}, {"memtable_sort_passes", c.memtable_sort_passes}, {"memtable_tiles", c.memtable_tiles}};

@@ -145,6 +145,8 @@ struct MsmScratch {
     bool lean_pending = false;
     struct { const void *bases_dev, *bases_z, *scalars_dev, *tails_dev; size_t n, batch, stride; int mont; bool has_fb; MsmFixedBase fb; MsmFlags flags; } retry{};
     unsigned lean_retries = 0;  // how often that happened on this context (tests)
+    u64 lean_sorts = 0;         // MSMs enqueued with the lean sort (tests: the dense route was taken)
+    u64 quad_combines = 0;      // launches of msm_combine_q4_kernel (tests: the quad form of the combine ran)
     u64 small_launches = 0;     // MSMs that ran as one msm_small_kernel launch (tests: the path was taken, not fallen back from)
     u64 chunks = 0;             // launch sets of the pipeline: one per iteration of enqueue_pipeline's chunk loop (tests: a batch ran as that many chunks)
     u64 unit_chunks = 0;        // of those, the fixed-base chunks whose vote held after the emit (sparse_chunk's unit path)

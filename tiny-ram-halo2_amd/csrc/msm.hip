@@ -1764,11 +1764,12 @@ int stage_accumulate(const MsmRun& r, const MsmChunk& ch) {
     // quad form only where the caller vouches for uniformly full-size scalars (dense_hint: the IPA's rounds, three or four pieces per bucket):
     // opening 12.8 -> 12.4 ms; on a lone even-bits column (256 buckets of 32 pieces, which four lanes share better than one quad walks)
     // it measured 0.52 -> 0.58 ms, full-size and word columns the same
-    if (pieces >= 3 && nbk >= 4 && !ch.compact && opt().reduce_q4 && r.a.f.dense_hint && (size_t)p.Ws * nb <= 8)
+    if (pieces >= 3 && nbk >= 4 && !ch.compact && opt().reduce_q4 && r.a.f.dense_hint && (size_t)p.Ws * nb <= 8) {
+        ++r.m->quad_combines;
         hipLaunchKernelGGL((msm_combine_q4_kernel<BF>), dim3((unsigned)(((size_t)nbk * 4 + 255) / 256), p.Ws, nb), dim3(256), 0, s, L.starts.as<u32>(), L.ends.as<u32>(),
                            L.first.as<XYZZzMem>(), L.last.as<XYZZzMem>(), L.direct.as<XYZZzMem>(), L.buckets.as<XYZZzMem>(), nbk, nseg, seg_len, L.heavy.as<u32>(), ch.seg.heavy_stride,
                            r.lean_gate);
-    else if (pieces >= 3 && nbk >= 4) launch_combine<BF, 4>(r, ch);
+    } else if (pieces >= 3 && nbk >= 4) launch_combine<BF, 4>(r, ch);
     else launch_combine<BF, 1>(r, ch);
     hipLaunchKernelGGL((msm_combine_heavy_kernel<BF>), dim3(ch.seg.heavy_blocks, 1, nb), dim3(256), 0, s, L.starts.as<u32>(), L.ends.as<u32>(), L.first.as<XYZZzMem>(),
                        L.last.as<XYZZzMem>(), L.buckets.as<XYZZzMem>(), nbk, nseg, seg_len, L.heavy.as<u32>(), (u32)p.Ws, ch.seg.heavy_stride);
@@ -1955,6 +1956,7 @@ int enqueue_pipeline(const MsmCall& a, const hostplan::MsmShape& sh) {
     TRH_HIP_TRY(hipMemcpyAsync(m.host_sums, m.window_sums.p, hs, hipMemcpyDeviceToHost, s));
     set_pending(m, BF::ID, p.Ws, p.c, a, r.timing, r.lean_sort);
     if (r.lean_sort) {  // what msm_finish needs to run this MSM again with the chunked passes
+        ++m.lean_sorts;
         m.retry.bases_dev = a.bases_dev; m.retry.bases_z = a.bases_z; m.retry.scalars_dev = a.scalars_dev; m.retry.tails_dev = a.tails_dev;
         m.retry.n = n; m.retry.batch = batch; m.retry.stride = a.stride; m.retry.mont = a.mont;
         m.retry.has_fb = a.fb != nullptr;
