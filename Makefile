@@ -14,10 +14,11 @@ ID_OBJ := $(CSRC)/capi.o
 # driver programs over include/trh.hpp that share one command line, each run by the GPU test of its subject: Params::write / read
 # (test_gpu_encoding.py), trh::Rng (test_gpu_rng.py), trh::PermutationAssembly (test_gpu_permkeygen.py), trh::Params::create
 # (test_gpu_hashtocurve.py), GateEvaluator::check and lookup_check (test_gpu_mock.py), trh::QuotientTerms (test_gpu_quotient.py),
-# columns_from_ints / even_odd_split / even_bits_table (test_gpu_witness.py), trh::mem_table (test_gpu_memtable.py)
-HPP_TESTS := $(addprefix tests/native/,params_io_test rng_fill_test perm_assembly_test params_new_test mock_check_test quotient_test witness_test memtable_test)
+# columns_from_ints / even_odd_split / even_bits_table (test_gpu_witness.py), trh::mem_table (test_gpu_memtable.py),
+# trh::exe_table (test_gpu_exetable.py)
+HPP_TESTS := $(addprefix tests/native/,params_io_test rng_fill_test perm_assembly_test params_new_test mock_check_test quotient_test witness_test memtable_test exetable_test)
 NATIVE := examples/replay tests/native/libtrh_q4broken.so $(HPP_TESTS) $(addprefix tests/native/,multi_ctx_test lazy29_dev_test lazy29_alias_test lazy29_segment_test \
-    foldplan_test permkeygen_test hashtocurve_vec_test transcript_test witness_vec_test memtable_vec_test)
+    foldplan_test permkeygen_test hashtocurve_vec_test transcript_test witness_vec_test memtable_vec_test exetable_vec_test)
 
 all: $(PKG)/libtrh.so oracle $(NATIVE)
 
@@ -95,6 +96,12 @@ tests/native/witness_vec_test: tests/native/witness_vec_test.cpp $(CSRC)/witness
 # sanitizers: reads cases, prints results; never loads libtrh; run by tests/test_memtable_host.py (which checks it against
 # tests/memtable_model.py)
 tests/native/memtable_vec_test: tests/native/memtable_vec_test.cpp $(CSRC)/memtable.h $(CSRC)/witness.h $(CSRC)/field.h
+	g++ -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -fsanitize=address,undefined -fno-sanitize-recover=all $< -o $@
+
+# csrc/exetable.h (the Exe table's instruction decode, the rules of a selection table and of a step, one row's values and one-hot selectors)
+# on the host, under address + undefined sanitizers: reads cases, prints results; never loads libtrh; run by tests/test_exetable_host.py
+# (which checks it against tests/exetable_model.py)
+tests/native/exetable_vec_test: tests/native/exetable_vec_test.cpp $(CSRC)/exetable.h $(CSRC)/witness.h $(CSRC)/field.h include/trh.h
 	g++ -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -fsanitize=address,undefined -fno-sanitize-recover=all $< -o $@
 
 oracle:

@@ -749,6 +749,66 @@ typedef struct trh_mem_table_args {
 } trh_mem_table_args_t;
 int trh_mem_table_dev(int field_id, trh_mem_table_args_t* args);
 
+/* ---- the Exe table: trace steps to temp-var columns and selectors, on the device ---------------------------------------------------------
+ * For every step of the trace the reference's ExeChip::assign_trace derives the four temporary variables a, b, c, d (the non-deterministic
+ * advice included), their one-hot selector cells and the plain trace cells: a pure per-row function of the step and its successor.  The
+ * host hands over the steps as machine words, m of them in execution order:
+ *   pc, inst, a, value   u32[m]; inst packs the opcode in bits 0 - 4, ri in bits 8 - 11, rj in bits 12 - 15, "operand A is a register" in
+ *                        bit 16; a is the immediate or the register's number; value is the word loaded or stored, 0 elsewhere
+ *   regs                 u32[m x reg_count], step-major: the registers BEFORE the step
+ *   flag_bits            ceil(m / 32) words: bit i & 31 of word i >> 5 is the flag before step i
+ * and the device writes 28 + 9 reg_count columns of n rows, back to back in dst (csrc/exetable.h has the layout in full):
+ *   s_trace pc flag reg* opcode immediate value tv_a tv_b tv_c tv_d | sa_* | sb_* | sc_* | sd_* | sa_non_det sb_non_det sc_non_det sd_non_det
+ * the first 24 + 9 reg_count being ADVICE of tests/golden/make_exe_gates.py.  Rows m .. n - 1 are WRITTEN as zero; `immediate` is A when A
+ * is an immediate and 0 when it is a register; the successor of step m - 1 is the zero row (index m of no input is read).
+ * The per-opcode selection is DATA: selection[opcode] packs one source per temporary variable, TRH_EXE_ENTRY(a, b, c, d), or is
+ * TRH_EXE_UNKNOWN.  Sources: UNSET (no selector, value 0), PC, PC_NEXT, PC_PLUS_ONE, REG_RI, REG_RJ, REG_NEXT_RI, A, VALUE, ZERO, ONE,
+ * MAX_WORD (2^word_bits - 1) and TRH_EXE_NONDET + rule.  A source is legal for a variable when the variable's selector family has its
+ * column (a: pc_next reg reg_next a v_addr; b: pc pc_next pc_plus_one reg reg_next a max_word; c: reg reg_next a zero; d: pc reg reg_next
+ * a zero one); UNSET and NONDET are legal everywhere.  Source A with a register operand sets s?_reg{A}, with an immediate s?_a.
+ * Non-deterministic rules, integers over RI = reg[ri], RJ = reg[rj] (contents before the step), A = the operand's VALUE, W = word_bits:
+ *   REM      A == 0 ? 0 : RJ mod A                                QUOT     A == 0 ? 0 : RJ div A
+ *   CMP_GT   RI > A ? 2^W - (RI - A) : A - RI                     CMP_GE   RI >= A ? 2^W - 1 - (RI - A) : A - RI - 1
+ *   MUL_HI   (RJ A) >> W                                          MUL_LO   (RJ A) mod 2^W
+ *   SMUL_LO  the low word of the product of A and RJ as signed words
+ *   XOR      RI xor A                                             PC_PLUS_ONE  pc + 1 (an integer: 2^32 when pc = 2^32 - 1)
+ *   SHL_HI   s = min(A, W): (RJ 2^s) >> W                         SHR_LO   s = min(A, W): 2^s RJ - 2^W (RJ >> s), negative values as m - |v|
+ * s = min(A, W) is this library's choice where the reference's 2u64.pow(a) overflows.
+ * The default table (exetable.DEFAULT_SELECTION in the Python package, trh::exe_default_selection in trh.hpp) restates the reference's
+ * TempVarSelectorsRow::from (aux.rs:105-398) with two departures:
+ *   a register operand's value is the register's CONTENT, which is what the reference's reg_gate demands of a cell under s?_reg{A}; its
+ *     push_temp_var_vals writes the register's NUMBER there (aux.rs:410-417);
+ *   CJmp's d is NONDET(PC_PLUS_ONE); the reference sets both sd_pc and sd_one (aux.rs:1070-1073), which under pc_gate and one_gate forces
+ *     pc = 1.
+ * With the default table every produced row satisfies the 90 gates of tests/golden/exe_tempvar_gates.json.
+ * Refusals (TRH_EINVAL), all with NOTHING written to dst; for a step, trh_last_error() names the FIRST offending step index:
+ *   a step with an opcode the table does not know, ri, rj or a register operand >= reg_count, a pc, a, register or value >= 2^word_bits;
+ *   a last step whose opcode is not 0b11111 (Answer);  m == 0 or m >= n;
+ *   an unknown field, word_bits outside 2 .. 32, reg_count outside 1 .. 16, a table entry with an illegal source, a null array, a dst
+ *     that is not 16-byte aligned, a word array that is not 4-byte aligned.
+ * The stream travels in the struct, as in trh_mem_table_args_t.  A validation kernel runs first and the host reads its verdict -- the one
+ * synchronisation of the entry, on args->stream; the row kernel is queued behind it and the entry returns without waiting for it.
+ * trh_stat "exetable_rows": the m of the last call on this context that passed validation.                                                 */
+enum { TRH_EXE_UNSET = 0, TRH_EXE_PC, TRH_EXE_PC_NEXT, TRH_EXE_PC_PLUS_ONE, TRH_EXE_REG_RI, TRH_EXE_REG_RJ, TRH_EXE_REG_NEXT_RI, TRH_EXE_A, TRH_EXE_VALUE,
+       TRH_EXE_ZERO, TRH_EXE_ONE, TRH_EXE_MAX_WORD, TRH_EXE_NONDET = 16 /* + rule */ };
+enum { TRH_EXE_RULE_REM = 0, TRH_EXE_RULE_QUOT, TRH_EXE_RULE_CMP_GT, TRH_EXE_RULE_CMP_GE, TRH_EXE_RULE_MUL_HI, TRH_EXE_RULE_MUL_LO, TRH_EXE_RULE_SMUL_LO,
+       TRH_EXE_RULE_XOR, TRH_EXE_RULE_SHL_HI, TRH_EXE_RULE_SHR_LO, TRH_EXE_RULE_PC_PLUS_ONE, TRH_EXE_RULES };
+#define TRH_EXE_UNKNOWN 0xFFFFFFFFu
+#define TRH_EXE_ENTRY(a, b, c, d) ((uint32_t)(a) | (uint32_t)(b) << 8 | (uint32_t)(c) << 16 | (uint32_t)(d) << 24)
+typedef struct trh_exe_table_args {
+    uint32_t word_bits;                        /* 2 .. 32 */
+    uint32_t reg_count;                        /* 1 .. 16 */
+    const uint32_t *pc, *inst, *a, *value;     /* device, m each, in execution order */
+    const uint32_t *regs;                      /* device, m x reg_count, step-major */
+    const uint32_t *flag_bits;                 /* device, ceil(m / 32) words */
+    size_t m;
+    uint32_t selection[32];                    /* by opcode: TRH_EXE_ENTRY(a, b, c, d) or TRH_EXE_UNKNOWN */
+    void*  dst;                                /* device, (28 + 9 reg_count) x n x 4 u64, 16-byte aligned, canonical Montgomery words */
+    size_t n;                                  /* rows per column, > m */
+    void*  stream;
+} trh_exe_table_args_t;
+int trh_exe_table_dev(int field_id, trh_exe_table_args_t* args);
+
 /* ---- element-wise field / group ops on device memory (parity tests of the device arithmetic;
  *      op: 0 add, 1 sub, 2 mul, 3 sqr, 4 neg, 5 inv, 6 to_mont, 7 from_mont) ------------------ */
 int trh_field_op_dev(int field, int op, const void* a_dev, const void* b_dev, void* out_dev, size_t n, void* stream);
@@ -787,7 +847,8 @@ int trh_stream_synchronize(void* stream);
  * "ntt_tableless_passes": of the last transform, the passes after the first that had no inter-pass twiddle table and computed their twiddles
  * per element (1 from 2^26 elements, where the last pass's table would exceed 1.125 GiB; 0 below);
  * "lookup_check_probes": the slots of the set visited by the two kernels (insert, probe) of the last trh_lookup_check_dev on this context;
- * "memtable_rows", "memtable_sort_passes", "memtable_tiles": the last trh_mem_table_dev on this context (described with that entry). */
+ * "memtable_rows", "memtable_sort_passes", "memtable_tiles": the last trh_mem_table_dev on this context (described with that entry);
+ * "exetable_rows": the steps of the last trh_exe_table_dev on this context that passed validation. */
 int trh_stat(const char* name, uint64_t* value);
 /* GPU-side timing without HIP headers: events recorded on a stream between the steps (a hipEvent_t each), read afterwards.
  * trh_event_elapsed_ms waits for `end` and returns the device time between the two records. */

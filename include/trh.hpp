@@ -656,6 +656,54 @@ inline MemTableResult mem_table(Field f, uint32_t word_bits, const uint32_t* add
     return MemTableResult{a.rows, a.n_inconsistent, a.first_inconsistent};
 }
 
+// ---- the Exe table (trh_exe_table_dev): the steps of a trace -> trace cells, temporary variables and their one-hot selectors ---------------
+// ExeSelection: one TRH_EXE_ENTRY(a, b, c, d) per opcode, TRH_EXE_UNKNOWN for an opcode the table does not know.  exe_default_selection()
+// restates the reference's TempVarSelectorsRow::from with the two departures trh.h documents (a register operand's content; CJmp's d).
+typedef std::array<uint32_t, 32> ExeSelection;
+inline uint32_t exe_encode(uint32_t opcode, uint32_t ri, uint32_t rj, bool a_is_reg) { return (opcode & 31u) | (ri & 15u) << 8 | (rj & 15u) << 12 | (a_is_reg ? 1u << 16 : 0u); }
+inline ExeSelection exe_default_selection() {
+    ExeSelection t;
+    t.fill(TRH_EXE_UNKNOWN);
+    const auto nd = [](int rule) { return TRH_EXE_NONDET + rule; };
+    const uint32_t logic = TRH_EXE_ENTRY(TRH_EXE_A, TRH_EXE_REG_RJ, TRH_EXE_REG_NEXT_RI, TRH_EXE_UNSET);
+    t[0] = t[1] = t[2] = logic;                                                                                   // and, or, xor
+    t[3] = TRH_EXE_ENTRY(TRH_EXE_A, TRH_EXE_MAX_WORD, TRH_EXE_REG_NEXT_RI, TRH_EXE_UNSET);                        // not
+    t[4] = TRH_EXE_ENTRY(TRH_EXE_A, TRH_EXE_REG_RJ, TRH_EXE_REG_NEXT_RI, TRH_EXE_ZERO);                           // add
+    t[5] = TRH_EXE_ENTRY(TRH_EXE_A, TRH_EXE_REG_NEXT_RI, TRH_EXE_REG_RJ, TRH_EXE_ZERO);                           // sub
+    t[6] = TRH_EXE_ENTRY(TRH_EXE_A, TRH_EXE_REG_RJ, nd(TRH_EXE_RULE_MUL_HI), TRH_EXE_REG_NEXT_RI);                // mull
+    t[7] = TRH_EXE_ENTRY(TRH_EXE_A, TRH_EXE_REG_RJ, TRH_EXE_REG_NEXT_RI, nd(TRH_EXE_RULE_MUL_LO));                // umulh
+    t[8] = TRH_EXE_ENTRY(TRH_EXE_A, TRH_EXE_REG_RJ, TRH_EXE_REG_NEXT_RI, nd(TRH_EXE_RULE_SMUL_LO));               // smulh
+    t[9] = TRH_EXE_ENTRY(nd(TRH_EXE_RULE_REM), TRH_EXE_REG_NEXT_RI, TRH_EXE_A, TRH_EXE_REG_RJ);                   // udiv
+    t[10] = TRH_EXE_ENTRY(TRH_EXE_REG_NEXT_RI, nd(TRH_EXE_RULE_QUOT), TRH_EXE_A, TRH_EXE_REG_RJ);                 // umod
+    t[11] = TRH_EXE_ENTRY(TRH_EXE_A, TRH_EXE_REG_RJ, nd(TRH_EXE_RULE_SHL_HI), TRH_EXE_REG_NEXT_RI);               // shl
+    t[12] = TRH_EXE_ENTRY(TRH_EXE_A, TRH_EXE_REG_RJ, TRH_EXE_REG_NEXT_RI, nd(TRH_EXE_RULE_SHR_LO));               // shr
+    t[13] = TRH_EXE_ENTRY(TRH_EXE_A, TRH_EXE_REG_RI, nd(TRH_EXE_RULE_XOR), TRH_EXE_UNSET);                        // cmpe
+    t[14] = t[16] = TRH_EXE_ENTRY(TRH_EXE_REG_RI, nd(TRH_EXE_RULE_CMP_GT), TRH_EXE_A, TRH_EXE_ZERO);              // cmpa, cmpg
+    t[15] = t[17] = TRH_EXE_ENTRY(TRH_EXE_REG_RI, nd(TRH_EXE_RULE_CMP_GE), TRH_EXE_A, TRH_EXE_ONE);               // cmpae, cmpge
+    t[18] = TRH_EXE_ENTRY(TRH_EXE_A, TRH_EXE_REG_NEXT_RI, TRH_EXE_ZERO, TRH_EXE_UNSET);                           // mov
+    t[19] = TRH_EXE_ENTRY(TRH_EXE_REG_NEXT_RI, TRH_EXE_A, TRH_EXE_ZERO, TRH_EXE_REG_RI);                          // cmov
+    t[20] = TRH_EXE_ENTRY(TRH_EXE_A, TRH_EXE_PC_NEXT, TRH_EXE_ZERO, TRH_EXE_UNSET);                               // jmp
+    t[21] = TRH_EXE_ENTRY(TRH_EXE_PC_NEXT, TRH_EXE_A, TRH_EXE_ZERO, nd(TRH_EXE_RULE_PC_PLUS_ONE));                // cjmp
+    t[22] = TRH_EXE_ENTRY(TRH_EXE_PC_NEXT, TRH_EXE_PC_PLUS_ONE, TRH_EXE_ZERO, TRH_EXE_A);                         // cnjmp
+    t[28] = TRH_EXE_ENTRY(TRH_EXE_VALUE, TRH_EXE_REG_NEXT_RI, TRH_EXE_ZERO, TRH_EXE_ZERO);                        // store.w
+    t[29] = TRH_EXE_ENTRY(TRH_EXE_VALUE, TRH_EXE_REG_RI, TRH_EXE_ZERO, TRH_EXE_ZERO);                             // load.w
+    t[31] = TRH_EXE_ENTRY(TRH_EXE_A, TRH_EXE_PC, TRH_EXE_ZERO, TRH_EXE_ZERO);                                     // answer
+    return t;
+}
+inline size_t exe_columns(uint32_t reg_count) { return 28 + 9 * (size_t)reg_count; }
+// pc / inst / a / value: m resident words each; regs: m x reg_count resident words, step-major; flag_bits: ceil(m / 32) resident bitmap
+// words; dst_dev: exe_columns(reg_count) x n elements.  Throws (check) on refused steps or a bad table; synchronises with the host once.
+inline void exe_table(Field f, uint32_t word_bits, uint32_t reg_count, const uint32_t* pc_dev, const uint32_t* inst_dev, const uint32_t* a_dev, const uint32_t* value_dev,
+                      const uint32_t* regs_dev, const uint32_t* flag_bits_dev, size_t m, void* dst_dev, size_t n, const ExeSelection& selection = exe_default_selection(),
+                      void* stream = nullptr) {
+    trh_exe_table_args_t a{};
+    a.word_bits = word_bits; a.reg_count = reg_count;
+    a.pc = pc_dev; a.inst = inst_dev; a.a = a_dev; a.value = value_dev; a.regs = regs_dev; a.flag_bits = flag_bits_dev; a.m = m;
+    for (size_t o = 0; o < selection.size(); ++o) a.selection[o] = selection[o];
+    a.dst = dst_dev; a.n = n; a.stream = stream;
+    check(trh_exe_table_dev((int)f, &a), "exe_table");
+}
+
 // ---- plonk::permutation::keygen::Assembly (trh_perm_*): the copy constraints of the equality-enabled columns, the sigma columns they
 // induce -- made on the device -- and what keygen_vk / keygen_pk derive from them ---------------------------------------------------------
 // copy() merges cycles exactly as upstream does (the order of the copies decides the mapping).  Host memory, like Rng: copies and mapping()

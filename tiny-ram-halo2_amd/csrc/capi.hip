@@ -193,6 +193,7 @@ static void destroy_ctx(Ctx* c) {
             c->io.release();
             stage_release(*c);
             c->factors.release();
+            c->exe_first_bad.release();
             if (c->pinned_ring) { (void)hipHostFree(c->pinned_ring); c->pinned_ring = nullptr; c->pinned_slot = 0; }
             if (c->pinned_land) { (void)hipHostFree(c->pinned_land); c->pinned_land = nullptr; }
             c->pfft.release();
@@ -453,7 +454,8 @@ int trh_stat(const char* name, uint64_t* value) {
         {"msm_lean_retries", m.lean_retries}, {"msm_lean_sorts", m.lean_sorts}, {"msm_quad_combines", m.quad_combines}, {"msm_small_launches", m.small_launches}, {"msm_chunks", m.chunks}, {"msm_unit_chunks", m.unit_chunks},
         {"msm_host_ranges", m.host_ranges}, {"msm_range_tiles", m.range_tiles}, {"ntt_tableless_passes", c.ntt_tableless_passes},
         {"ipa_generator_collapses", c.ipa.collapses}, {"lookup_check_probes", c.lookup_check_probes},
-        {"memtable_rows", c.memtable_rows}, {"memtable_sort_passes", c.memtable_sort_passes}, {"memtable_tiles", c.memtable_tiles}};
+        {"memtable_rows", c.memtable_rows}, {"memtable_sort_passes", c.memtable_sort_passes}, {"memtable_tiles", c.memtable_tiles},
+        {"exetable_rows", c.exetable_rows}};
     for (const auto& k : counters) if (strcmp(name, k.name) == 0) { *value = k.value; return TRH_OK; }
     if (strcmp(name, "msm_bin_sorted_windows") == 0) {  // synchronises the device: tests only
         *value = 0;

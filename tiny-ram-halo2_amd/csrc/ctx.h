@@ -245,6 +245,8 @@ struct Ctx {
     void* lookup_scratch = nullptr;  // lookup.hip's buffers (opaque here)
     u64 lookup_check_probes = 0;     // slots visited by the two kernels of the last trh_lookup_check_dev (mockcheck.hip; tests)
     u64 memtable_rows = 0, memtable_sort_passes = 0, memtable_tiles = 0;  // of the last trh_mem_table_dev that got as far as its row count (memtable.hip; tests)
+    DevBuf exe_first_bad;            // one word: the smallest step index the last trh_exe_table_dev's validation refused (exetable.hip)
+    u64 exetable_rows = 0;           // steps of the last trh_exe_table_dev that passed validation (tests)
     int cu_count = 0;               // compute units of the device (persistent kernels size their grids by it); 0: not asked yet
     unsigned attr_done = 0;          // hipFuncSetAttribute is per device: bit per kernel family already configured for this context's device
     hipStream_t own_stream = nullptr;  // the multi-device MSM driver enqueues this context's shard here

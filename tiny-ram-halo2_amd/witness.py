@@ -13,7 +13,8 @@ the (columns, n, 4) Montgomery tensors that plonk.create_proof and mock.MockProv
     AdviceBuilder(field, num_advice, n)               owns the advice tensor; ints / even_odd / full / mem_table write into its column slices
 
 The one table that is no per-row function of the trace, the memory-consistency table, is made from the access log by memtable.build
-(AdviceBuilder.mem_table): sorted, scanned and checked on the device.
+(AdviceBuilder.mem_table): sorted, scanned and checked on the device.  The Exe table's temporary variables and selectors are derived from
+the steps themselves by exetable.build (AdviceBuilder.exe_table).
 """
 from __future__ import annotations
 
@@ -204,6 +205,13 @@ class AdviceBuilder:
         from . import memtable
         return memtable.build(self.field, word_bits, address, time, value, is_store, tape=tape, max_rows=max_rows, out=self._slice(first_column, len(memtable.COLUMNS)),
                               stream=stream, m=m)
+
+    def exe_table(self, first_column: int, word_bits: int, reg_count: int, pc, inst, a, regs, flags, value, selection=None, stream=None, m: int | None = None):
+        """the Exe table of a trace's steps into the 28 + 9 reg_count columns first_column .. (exetable.columns, exetable.build): -> the
+        builder's own slice"""
+        from . import exetable
+        return exetable.build(self.field, word_bits, reg_count, pc, inst, a, regs, flags, value, selection=selection,
+                              out=self._slice(first_column, 28 + 9 * reg_count), stream=stream, m=m)
 
     def tensor(self):
         return self._t
