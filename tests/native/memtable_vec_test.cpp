@@ -17,11 +17,11 @@ using namespace trh::memtable;
 
 static bool layout_ok(const Plan& p) {
     const u64 off[] = {p.off_keys[0], p.off_index[0], p.off_keys[1], p.off_index[1], p.off_hist, p.off_hist_sums, p.off_place, p.off_place_sums, p.off_row_address,
-                       p.off_row_time, p.off_row_value, p.off_row_source, p.off_last, p.off_last_sums, p.off_result, p.bytes};
+                       p.off_row_time, p.off_row_value, p.off_row_source, p.off_last, p.off_last_sums, p.bytes};
     const u64 size[] = {4 * p.records, 4 * p.records, 4 * p.records, 4 * p.records, 4 * (u64)RADIX * p.sort_tiles, 4 * p.hist_scan_tiles, 4 * p.records,
-                        4 * p.record_scan_tiles, 4 * p.row_cap, 4 * p.row_cap, 4 * p.row_cap, 4 * p.row_cap, 8 * p.row_cap, 8 * p.row_scan_tiles, 32};
+                        4 * p.record_scan_tiles, 4 * p.row_cap, 4 * p.row_cap, 4 * p.row_cap, 4 * p.row_cap, 8 * p.row_cap, 8 * p.row_scan_tiles};
     if (off[0] != 0) return false;
-    for (int i = 0; i < 15; ++i)
+    for (int i = 0; i < 14; ++i)
         if (off[i] % 256 != 0 || off[i] + size[i] > off[i + 1]) return false;
     return true;
 }

@@ -180,6 +180,65 @@ def test_gate_check_equals_the_model(field, log_n):
     assert seen_through_rotation == (usable < n)
 
 
+def test_gate_check_with_more_outputs_than_one_landing_area_holds():
+    """300 outputs are 600 verdict words, 4800 bytes: more than the 4 KiB the context's pinned landing area starts with.  In a fresh context
+    the five-output check comes first and allocates the area at 4 KiB; the 300-output check behind it has to GROW it (the old area is freed
+    while the context lives on); then the five-output check again, which asks for less than is there, and the 300 outputs once more through
+    the area as it stands.  300 gates of expr.synthetic_gates, one output each, at log_n = 7 with 100 usable rows: the advice is random and
+    every selector zero, so every output vanishes -- except that three gates which share their selector with no other gate have it set on
+    one row each: rows 0, 63 (the last lane of the first wave) and 99 (the last usable row).  The expected verdict is the oracle's, row by
+    row."""
+    field, log_n, usable, n_gates = "fp", 7, 100, 300
+    f, n = o.FIELDS[field], 1 << log_n
+    gates = expr.synthetic_gates(12, 4096, n_gates, seed=0x4B1D)
+    selector_of = [g.a.column for g in gates]                                  # a gate is Selector * body
+    assert all(isinstance(g.a, expr.Selector) for g in gates)
+    lone = [a for a, c in enumerate(selector_of) if selector_of.count(c) == 1]
+    chosen = {lone[0]: 0, lone[len(lone) // 2]: 63, lone[-1]: 99}
+    assert len(chosen) == 3
+    ev = expr.GateEvaluator(expr.compile_outputs(field, gates), n_outputs=n_gates)
+    rng = random.Random(0x1A4D)
+    ints = {key: [rng.randrange(f.m) for _ in range(n)] if key[0] == "advice" else [0] * n for key in ev.program.columns}
+    for a, row in chosen.items():
+        ints[("selector", selector_of[a])][row] = 1
+    tuples = [expr_to_tuple(g) for g in gates]
+    want = [[row for row in range(usable) if o.evaluate_expression(f, t, ints, row, n, 1)] for t in tuples]
+    assert {a: b for a, b in enumerate(want) if b} == {a: [row] for a, row in chosen.items()}
+    zeros = to_dev(f, [0] * n)
+    dev = {key: to_dev(f, col) if any(col) else zeros for key, col in ints.items()}
+    # the five-gate system at log_n = 6, satisfied and with one corrupted cell
+    ints5 = gate_witness(field, 6)
+    dev5 = {k: to_dev(f, col) for k, col in ints5.items()}
+    bad5 = dict(ints5)
+    bad5[("advice", 2)] = list(ints5[("advice", 2)])
+    bad5[("advice", 2)][57] = (bad5[("advice", 2)][57] + 1) % f.m
+    bad_dev5 = dict(dev5)
+    bad_dev5[("advice", 2)] = to_dev(f, bad5[("advice", 2)])
+
+    def five_outputs():
+        assert check_against_model(field, 6, ints5, dev5) == [[]] * 5
+        assert any(check_against_model(field, 6, bad5, bad_dev5))
+
+    def three_hundred_outputs():
+        W = n // 64
+        n_bad, first, words = ev.check(dev, log_n, usable, bitmap=True)
+        assert [int(v) for v in n_bad] == [len(b) for b in want]
+        assert [int(v) for v in first] == [b[0] if b else usable for b in want]
+        assert words.shape == (n_gates, W) and (words_of(words) == np.stack([bitmap_of(W, b) for b in want])).all()
+        plain = ev.check(dev, log_n, usable)
+        assert (plain[0] == n_bad).all() and (plain[1] == first).all()
+
+    fresh = api.Context(0)                                                     # whatever ran before this test: this context has no landing area yet
+    try:
+        with fresh:
+            five_outputs()            # allocates the area at 4 KiB
+            three_hundred_outputs()   # grows it
+            five_outputs()            # asks for less than is there
+            three_hundred_outputs()
+    finally:
+        fresh.destroy()
+
+
 def test_gate_check_refusals():
     field, log_n = "fp", 6
     f = o.FIELDS[field]

@@ -185,28 +185,48 @@ def test_grand_product_closes_and_check_agrees(field):
 
 
 # ---- the check kernel's reductions ------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def big():
-    """(12, 20) with 5 000 random copies, and pairs that put a cycle of two or more cells into every block of 256 cells, cell 0 and the last"""
+WAVE_EDGES = [3 * 256 + 63, 3 * 256 + 64, 3 * 256 + 191, 3 * 256 + 192, 9 * 256, 9 * 256 + 255]   # cells of column 0; then the last cell
+
+
+def big_assembly(extra_pairs):
     k, n_columns = 12, 20
     n = 1 << k
     a = permutation.Assembly("fp", k, n_columns)
     a.copy_many(random_copies(k, n_columns, 5000, 0xB16))
     pairs = [(c, r, (c + 7) % n_columns, r + 1) for c in range(n_columns) for r in range(0, n, 128)] + [(n_columns - 1, n - 1, 3, 5)]
-    a.copy_many(pairs)
+    a.copy_many(pairs + extra_pairs)
     mapping = a.mapping().reshape(-1).astype(np.int64)
     values, _ = cycle_values(mapping, 0xB17)
     values.setflags(write=False)
-    yield a, mapping, values, [c * n + r for c, r, _, _ in pairs]
-    a.destroy()
+    return a, mapping, values, [c * n + r for c, r, _, _ in pairs]
 
 
-@pytest.mark.parametrize("case", ["none", "cell_0", "last_cell", "every_block"])
-def test_check_against_numpy(big, case):
-    a, mapping, values, marked = big
+@pytest.fixture(scope="module")
+def big():
+    """(12, 20) with 5 000 random copies, and pairs that put a cycle of two or more cells into every block of 256 cells, cell 0 and the last"""
+    made = big_assembly([])
+    yield made
+    made[0].destroy()
+
+
+@pytest.fixture(scope="module")
+def big_edges():
+    """the same, and every cell of WAVE_EDGES copied to its row in column 10: in `big` four of the six are alone in their cycle, and a cell
+    that maps to itself cannot be bad whatever its value"""
+    made = big_assembly([(0, cell, 10, cell) for cell in WAVE_EDGES])
+    yield made
+    made[0].destroy()
+
+
+@pytest.mark.parametrize("case", ["none", "cell_0", "last_cell", "every_block", "wave_edges"])
+def test_check_against_numpy(request, case):
+    """wave_edges: the last lane of a wave and the first of the next, twice in one block (all four of its waves report), the first and the
+    last lane of another block, and the last cell -- every wave adds its own count and lowers the minimum itself, so the total and the
+    first cell are right only if no wave's report is lost or merged with a neighbour's"""
+    a, mapping, values, marked = request.getfixturevalue("big_edges" if case == "wave_edges" else "big")
     n, cells = a.n, a.n * a.n_columns
     vals = values.copy()
-    changed = {"none": [], "cell_0": [0], "last_cell": [cells - 1], "every_block": marked}[case]
+    changed = {"none": [], "cell_0": [0], "last_cell": [cells - 1], "every_block": marked, "wave_edges": WAVE_EDGES + [cells - 1]}[case]
     vals[changed] = synth.field_elements(0xC4A, len(changed))
     bad = (vals != vals[mapping]).any(axis=1)
     n_bad = int(bad.sum())
@@ -214,6 +234,9 @@ def test_check_against_numpy(big, case):
         assert n_bad == 0
     elif case == "every_block":
         assert bad.reshape(-1, 256).any(axis=1).all() and n_bad > cells // 256
+    elif case == "wave_edges":
+        # every changed cell is bad, and no cell that maps to one lies in blocks 0 .. 2: the first bad cell is in block 3, not in block 0
+        assert bad[changed].all() and not bad[:3 * 256].any() and int(np.argmax(bad)) == 3 * 256 + 63
     else:
         assert n_bad == 2 and bad[changed[0]]
     first = int(np.argmax(bad)) if n_bad else None

@@ -212,7 +212,7 @@ def test_the_plan_tiles():
         assert sort_tiles == ceil(records, memtable.SORT_TILE) == memtable.plan(m, t, 32)["sort_tiles"]
         assert record_tiles == ceil(records, memtable.SCAN_TILE) == memtable.plan(m, t, 32)["scan_tiles"]
         assert hist_tiles == ceil(256 * sort_tiles, memtable.SCAN_TILE) and row_tiles == ceil(row_cap, memtable.SCAN_TILE)
-        assert nbytes >= 20 * records + 4 * 256 * sort_tiles + 24 * row_cap and nbytes <= 20 * records + 1024 * sort_tiles + 24 * row_cap + 8 * (record_tiles + hist_tiles + row_tiles) + 16 * 256
+        assert nbytes >= 20 * records + 4 * 256 * sort_tiles + 24 * row_cap and nbytes <= 20 * records + 1024 * sort_tiles + 24 * row_cap + 8 * (record_tiles + hist_tiles + row_tiles) + 14 * 256
 
 
 # ---- the ABI -------------------------------------------------------------------------------------------------------------------------------------

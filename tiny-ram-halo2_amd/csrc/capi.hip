@@ -193,9 +193,9 @@ static void destroy_ctx(Ctx* c) {
             c->io.release();
             stage_release(*c);
             c->factors.release();
-            c->exe_first_bad.release();
             if (c->pinned_ring) { (void)hipHostFree(c->pinned_ring); c->pinned_ring = nullptr; c->pinned_slot = 0; }
-            if (c->pinned_land) { (void)hipHostFree(c->pinned_land); c->pinned_land = nullptr; }
+            c->verdict.dev.release();  // the verdict words and where they land
+            if (c->pinned_land) { (void)hipHostFree(c->pinned_land); c->pinned_land = nullptr; c->pinned_land_cap = 0; }
             c->pfft.release();
             c->scan.release(); c->scan2.release();
             c->last_stream_valid = false;

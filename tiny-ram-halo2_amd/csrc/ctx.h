@@ -86,6 +86,8 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
     template <class T> T* as() const { return (T*)p; }
 };
+inline unsigned blocks_of(u64 count, u32 per_block) { return (unsigned)((count + per_block - 1) / per_block); }  // blocks of per_block lanes that cover count elements
+struct VerdictWords { DevBuf dev; size_t n_sums = 0, n_mins = 0; };  // the words a judging kernel reports in: n_sums u64, then n_mins u64 (verdict.h)
 
 struct TwiddleEntry {
     int field, log_n;
@@ -230,13 +232,12 @@ struct Ctx {
     DevBuf pfft;  // curve-point FFT work array + twiddle scalars
     DevBuf scan, scan2;  // prefix-product block totals / batch-inversion running products
     DevBuf sqrt_tab[2];     // fieldsqrt.h's table per field (encoding.hip; uploaded at first use, kept like the twiddle tables)
-    DevBuf enc_first_bad;   // one word: the smallest invalid index of the last decompression
     DevBuf h2c_u;           // hashtocurve.hip: the field elements between the fused entry's hash and map kernels (one chunk of points)
     IpaScratch ipa;
     DevBuf factors;  // ring of 16 small factor tables for the scale kernels
     unsigned factor_slot = 0;
     void* pinned_ring = nullptr;  // 64 x 2 KiB of pinned host memory mirroring the factor ring: constants are copied here first, so the
-    void* pinned_land = nullptr;  // 4 KiB pinned landing area for the few words the host reads back per IPA round (a pageable target costs a staging copy)
+    void* pinned_land = nullptr; size_t pinned_land_cap = 0;  // host_land(): pinned landing area (>= 4 KiB) for the few words the host reads back per IPA round or verdict (a pageable target costs a staging copy)
     unsigned pinned_slot = 0;     // asynchronous upload never reads a caller's stack buffer and needs no synchronisation
     bool helper_failed = false;
     class HostHelper* helper = nullptr;  // host thread for the second half of a batch's Horners (hosthelper.h; msm_finish)
@@ -245,7 +246,7 @@ struct Ctx {
     void* lookup_scratch = nullptr;  // lookup.hip's buffers (opaque here)
     u64 lookup_check_probes = 0;     // slots visited by the two kernels of the last trh_lookup_check_dev (mockcheck.hip; tests)
     u64 memtable_rows = 0, memtable_sort_passes = 0, memtable_tiles = 0;  // of the last trh_mem_table_dev that got as far as its row count (memtable.hip; tests)
-    DevBuf exe_first_bad;            // one word: the smallest step index the last trh_exe_table_dev's validation refused (exetable.hip)
+    VerdictWords verdict;            // the one verdict a context has open at a time (verdict.h)
     u64 exetable_rows = 0;           // steps of the last trh_exe_table_dev that passed validation (tests)
     int cu_count = 0;               // compute units of the device (persistent kernels size their grids by it); 0: not asked yet
     unsigned attr_done = 0;          // hipFuncSetAttribute is per device: bit per kernel family already configured for this context's device
@@ -257,6 +258,18 @@ struct Ctx {
 };
 enum { ATTR_MSM = 1u, ATTR_NTT = 2u, ATTR_EXPR = 4u };
 
+// The context's pinned landing area, at least `bytes` long and never less than 4096: grow-only, allocated at first use.  Growing frees the
+// old area, which is safe because every user has synchronised before its entry returns (callers hold the context lock).  out may be null.
+inline int host_land(Ctx& c, size_t bytes, void** out) {
+    if (bytes < 4096) bytes = 4096;
+    if (bytes > c.pinned_land_cap) {
+        if (c.pinned_land) { (void)hipHostFree(c.pinned_land); c.pinned_land = nullptr; c.pinned_land_cap = 0; }
+        TRH_HIP_TRY(hipHostMalloc(&c.pinned_land, bytes, hipHostMallocDefault));
+        c.pinned_land_cap = bytes;
+    }
+    if (out) *out = c.pinned_land;
+    return TRH_OK;
+}
 Ctx& ctx();  // the context entered (TRH_ENTER) by the calling thread
 int require_init();
 // capi.hip: TRH_EINVAL and the error text for an id that with_field / with_curve (dispatch.h) must not see
@@ -413,7 +426,7 @@ void lookup_release();
 // encoding decodes to the all-zero POD; first_bad (optional) receives the smallest invalid index, n if there is none -- and synchronises s
 int points_decompress_device(int curve, const void* bytes_dev, void* xy_dev, void* ok_dev, size_t n, hipStream_t s, u64* first_bad);
 int points_compress_device(int curve, const void* xy_dev, void* bytes_dev, size_t n, hipStream_t s);
-void encoding_release();
+void encoding_release();  // the square-root tables
 // the context's copy of fieldsqrt.h's SqrtTable<F> for field id 0 (Fp) / 1 (Fq), uploaded at first use
 int sqrt_table_device(int field_id, const void** out);
 // hashtocurve.hip

@@ -22,6 +22,11 @@ __device__ __forceinline__ void store_fe(uint4* p, const Fe<F>& v) {
     p[0] = make_uint4(w[0], w[1], w[2], w[3]);
     p[1] = make_uint4(w[4], w[5], w[6], w[7]);
 }
+// the field's zero: the same eight words in both fields
+__device__ __forceinline__ void store_zero(uint4* p) {
+    p[0] = make_uint4(0u, 0u, 0u, 0u);
+    p[1] = make_uint4(0u, 0u, 0u, 0u);
+}
 // canonical Montgomery words -> the lazy domain (fy_load)
 template <class F>
 __device__ __forceinline__ Fy<F> load_fy(const uint4* p) {

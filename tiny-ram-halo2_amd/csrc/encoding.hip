@@ -3,11 +3,12 @@
 // 2 * 2^k + 2 compressed points -- one square root each in a field of two-adicity 32 -- before a single base can be uploaded; here the 32-byte
 // encodings cross the link and one kernel turns them into the resident 64-byte PODs (bases.hip trh_bases_create_compressed).
 // The arithmetic is csrc/fieldsqrt.h (fixed schedule: no lane of a wavefront waits for another's Tonelli-Shanks rounds); one thread per
-// element, grid-stride.  The per-field table of fieldsqrt.h lives in the context beside its other tables, uploaded at first use.
+// element, grid-stride; the decompression's smallest invalid index is a verdict of one min word (verdict.h).  The per-field table of fieldsqrt.h lives in the context.
 #include <string.h>
 
 #include "ctx.h"
 #include "fieldsqrt.h"
+#include "verdict.h"
 
 namespace trh {
 namespace {
@@ -91,16 +92,14 @@ template <class F> int decompress_t(const void* bytes, void* xy, void* ok, size_
     Ctx& c = ctx();
     const SqrtTable<F>* tab;
     TRH_TRY(sqrt_table_dev<F>(&tab));
-    TRH_TRY(c.enc_first_bad.ensure(8));
-    TRH_HIP_TRY(hipMemsetAsync(c.enc_first_bad.p, 0xff, 8, s));
-    hipLaunchKernelGGL((decompress_kernel<F>), dim3(enc_grid(n)), dim3(ENC_BLOCK), 0, s, (const u32*)bytes, (uint4*)xy, (unsigned char*)ok,
-                       c.enc_first_bad.as<unsigned long long>(), n, tab);
+    unsigned long long* d_min;  // the verdict: the smallest invalid index
+    TRH_TRY(verdict_begin(c, 0, 1, s, nullptr, &d_min));
+    hipLaunchKernelGGL((decompress_kernel<F>), dim3(enc_grid(n)), dim3(ENC_BLOCK), 0, s, (const u32*)bytes, (uint4*)xy, (unsigned char*)ok, d_min, n, tab);
     TRH_HIP_TRY(hipGetLastError());
-    if (first_bad) {
-        u64 v = 0;
-        TRH_HIP_TRY(hipMemcpyAsync(&v, c.enc_first_bad.p, 8, hipMemcpyDeviceToHost, s));
-        TRH_HIP_TRY(hipStreamSynchronize(s));
-        *first_bad = v < n ? v : (u64)n;
+    if (first_bad) {  // without it the verdict is never read: no synchronisation
+        const u64* min;
+        TRH_TRY(verdict_read(c, s, nullptr, &min));
+        *first_bad = min_or(min[0], n);
     }
     return TRH_OK;
 }
@@ -148,10 +147,7 @@ int sqrt_table_device(int field_id, const void** out) {
     }
     return TRH_OK;
 }
-void encoding_release() {
-    Ctx& c = ctx();
-    c.sqrt_tab[0].release(); c.sqrt_tab[1].release(); c.enc_first_bad.release();
-}
+void encoding_release() { ctx().sqrt_tab[0].release(); ctx().sqrt_tab[1].release(); }
 
 }  // namespace trh
 

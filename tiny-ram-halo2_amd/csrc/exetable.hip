@@ -1,8 +1,8 @@
 // trh_exe_table_dev (include/trh.h): the steps of a trace into the 28 + 9 reg_count columns of the Exe table -- the plain trace cells, the
 // four temporary variables with their non-deterministic advice, and their one-hot selectors -- over csrc/exetable.h.  Every row is a
 // function of its step and the step behind it, so there is nothing to sort or scan: two kernels, one lane per step.
-//   validate  exetable::step_ok and step_regs_ok on every step, atomicMin of the first index that breaks them.  The host reads the verdict
-//             (the entry's one synchronisation) BEFORE anything is written to the destination
+//   validate  exetable::step_ok and step_regs_ok on every step, atomicMin of the first index that breaks them into a verdict of one min
+//             word (verdict.h).  The host reads it (the entry's one synchronisation) BEFORE anything is written to the destination
 //   rows      one lane owns one row, so the 64 lanes of a wave write 64 consecutive 32-byte elements of one column -- 2 KiB in one piece
 //             per store pair -- and walk the columns together.  exe_row gives the row's integers; each distinct word of the row is
 //             converted once (csrc/witness.h: one Montgomery multiplication, none for 0 and 1): a temporary variable that equals pc, a
@@ -13,6 +13,7 @@
 #include "ctx.h"
 #include "devmem.h"
 #include "exetable.h"
+#include "verdict.h"
 
 namespace trh {
 namespace {
@@ -41,11 +42,6 @@ __global__ void __launch_bounds__(EXE_THREADS) exe_validate_kernel(StepPtrs g, S
     const bool ok = step_ok(g.word_bits, g.reg_count, entry_of(t, inst_opcode(inst)), g.pc[i], inst, g.a[i], g.value[i], i + 1 == g.m) &&
                     step_regs_ok(g.word_bits, g.reg_count, g.regs + i * g.reg_count);
     if (!ok) atomicMin(first_bad, (unsigned long long)i);
-}
-
-__device__ __forceinline__ void store_zero(uint4* p) {
-    p[0] = make_uint4(0u, 0u, 0u, 0u);
-    p[1] = make_uint4(0u, 0u, 0u, 0u);
 }
 
 template <class F>
@@ -101,8 +97,6 @@ __global__ void __launch_bounds__(EXE_THREADS) exe_rows_kernel(StepPtrs g, Selec
     }
 }
 
-unsigned blocks_of(u64 count, u32 per_block) { return (unsigned)((count + per_block - 1) / per_block); }
-
 int check_args(int field, const trh_exe_table_args_t* a) {
     if (!a) { set_error("exe_table_dev: null arguments"); return TRH_EINVAL; }
     TRH_TRY(check_field(field));
@@ -138,23 +132,20 @@ int trh_exe_table_dev(int field_id, trh_exe_table_args_t* a) {
     Range range("trh_exe_table_dev");
     Ctx& c = ctx();
     const hipStream_t s = (hipStream_t)a->stream;
-    if (!c.pinned_land) TRH_HIP_TRY(hipHostMalloc(&c.pinned_land, 4096, hipHostMallocDefault));
-    TRH_TRY(c.exe_first_bad.ensure(8));
-    unsigned long long* first_bad = c.exe_first_bad.as<unsigned long long>();
-    unsigned long long* land = (unsigned long long*)c.pinned_land;
     const StepPtrs g{a->pc, a->inst, a->a, a->value, a->regs, a->flag_bits, a->m, a->word_bits, a->reg_count};
     Selection t;
     for (u32 o = 0; o < OPCODES; ++o) t.e[o] = a->selection[o];
 
-    TRH_HIP_TRY(hipMemsetAsync(first_bad, 0xff, 8, s));
-    hipLaunchKernelGGL(exe_validate_kernel, dim3(blocks_of(a->m, EXE_THREADS)), dim3(EXE_THREADS), 0, s, g, t, first_bad);
+    unsigned long long* d_first_bad;  // the verdict: the smallest step index that breaks a rule
+    TRH_TRY(verdict_begin(c, 0, 1, s, nullptr, &d_first_bad));
+    hipLaunchKernelGGL(exe_validate_kernel, dim3(blocks_of(a->m, EXE_THREADS)), dim3(EXE_THREADS), 0, s, g, t, d_first_bad);
     TRH_HIP_TRY(hipGetLastError());
     // the one synchronisation: the verdict on the steps, before the destination is touched
-    TRH_HIP_TRY(hipMemcpyAsync(land, first_bad, 8, hipMemcpyDeviceToHost, s));
-    TRH_HIP_TRY(hipStreamSynchronize(s));
-    if (land[0] != ~0ull) {
+    const u64* min;
+    TRH_TRY(verdict_read(c, s, nullptr, &min));
+    if (lowered(min[0])) {
         set_error("exe_table_dev: step %llu breaks the table's rules (an opcode the selection knows, ri, rj and a register operand below %u, pc, a, registers and value "
-                  "below 2^%u, Answer on the last step)", land[0], a->reg_count, a->word_bits);
+                  "below 2^%u, Answer on the last step)", (unsigned long long)min[0], a->reg_count, a->word_bits);
         return TRH_EINVAL;
     }
     const unsigned blocks = blocks_of(a->n, EXE_THREADS);

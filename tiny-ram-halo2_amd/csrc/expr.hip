@@ -32,6 +32,7 @@
 
 #include "ctx.h"
 #include "devmem.h"
+#include "verdict.h"
 
 struct trh_expr {
     int field;
@@ -188,31 +189,24 @@ __global__ void __launch_bounds__(THREADS) expr_eval_kernel(const DevInsn* __res
 }
 
 // MockProver's gate check: the same program over one cyclic domain with rot_step 1, every output tested against zero on the rows below
-// usable_rows instead of being stored.  A wave holds 64 consecutive, 64-aligned rows, so the verdict of an output is one ballot: lane 0
-// writes it as word a * W + gid / 64 of the bitmap (every word, zeros included), and only a wave that saw a bad row adds its count to
-// result[2 a] and lowers result[2 a + 1] to its smallest bad row -- a satisfied witness issues no atomics.
+// usable_rows instead of being stored.  A wave holds 64 consecutive, 64-aligned rows, so the verdict of an output is one ballot
+// (verdict.h wave_verdict): only a wave that saw a bad row adds its count to sums[a] and lowers mins[a] to its smallest bad row -- a
+// satisfied witness issues no atomics -- and lane 0 writes the ballot as word a * W + gid / 64 of the bitmap (every word, zeros included).
 template <class F>
 __global__ void __launch_bounds__(THREADS) expr_check_kernel(const DevInsn* __restrict__ prog, u32 n_insn, const uint4* const* __restrict__ ptrs,
                                                              const uint4* __restrict__ consts, u32 log_n, size_t usable_rows,
-                                                             unsigned long long* __restrict__ result, unsigned long long* __restrict__ bitmap, size_t W) {
+                                                             unsigned long long* __restrict__ sums, unsigned long long* __restrict__ mins, unsigned long long* __restrict__ bitmap, size_t W) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const size_t N = (size_t)1 << log_n;
     const size_t gid = (size_t)blockIdx.x * THREADS + threadIdx.x;
     const size_t row = gid & (N - 1);  // lanes beyond the domain (2^log_n < 256) repeat rows and are masked: usable_rows <= 2^log_n
     const bool live = gid < usable_rows;
-    const bool lane0 = (threadIdx.x & 63) == 0;
     auto test = [&](u32 a, const Fe<F>& v) {
         u32 w[8];
         fe_store(v, w);
         const bool bad = live && (w[0] | w[1] | w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) != 0;
-        const unsigned long long ballot = __ballot(bad);
-        if (lane0) {
-            if (bitmap && (gid >> 6) < W) bitmap[(size_t)a * W + (gid >> 6)] = ballot;
-            if (ballot) {
-                atomicAdd(result + 2 * (size_t)a, (unsigned long long)__popcll(ballot));
-                atomicMin(result + 2 * (size_t)a + 1, (unsigned long long)(gid + (size_t)(__ffsll((long long)ballot) - 1)));
-            }
-        }
+        const unsigned long long ballot = wave_verdict(bad, gid, sums + a, mins + a);
+        if ((threadIdx.x & 63) == 0 && bitmap && (gid >> 6) < W) bitmap[(size_t)a * W + (gid >> 6)] = ballot;
     };
     expr_run<F>(smem, prog, n_insn, ptrs, consts, N, 1u, row, test);
 }
@@ -466,26 +460,22 @@ int trh_expr_check_dev(trh_expr* e, const void* const* columns_dev, uint32_t log
     Range range("trh_expr_check_dev");
     Ctx& c = ctx();
     const hipStream_t s = nullptr;
-    // the (count, smallest row) pair of every output, in context scratch, initialised on the stream before the launch
-    std::vector<unsigned long long> result(2 * (size_t)e->n_outputs);
-    for (uint32_t a = 0; a < e->n_outputs; ++a) { result[2 * a] = 0; result[2 * a + 1] = ~0ull; }
-    TRH_TRY(c.scan.ensure(result.size() * 8));
-    unsigned long long* d_result = c.scan.as<unsigned long long>();
-    TRH_HIP_TRY(hipMemcpyAsync(d_result, result.data(), result.size() * 8, hipMemcpyHostToDevice, s));
+    unsigned long long *d_sums, *d_mins;  // per output: its bad rows, the smallest of them
+    TRH_TRY(verdict_begin(c, e->n_outputs, e->n_outputs, s, &d_sums, &d_mins));
     if (e->n_columns) TRH_HIP_TRY(hipMemcpyAsync(e->d_ptrs, e->h_ptrs.data(), (size_t)e->n_columns * sizeof(void*), hipMemcpyHostToDevice, s));
     const unsigned blocks = (unsigned)((N + THREADS - 1) / THREADS);
     const size_t lds = (size_t)e->lds_slots * THREADS * 36;
     const size_t W = N >= 64 ? N / 64 : 1;
     with_field(e->field, [&](auto f) {
         hipLaunchKernelGGL((expr_check_kernel<decltype(f)>), dim3(blocks), dim3(THREADS), lds, s, (const DevInsn*)e->d_prog, e->n_insn, (const uint4* const*)e->d_ptrs,
-                           (const uint4*)e->d_consts, log_n, usable_rows, d_result, (unsigned long long*)bad_bitmap_dev_or_null, W);
+                           (const uint4*)e->d_consts, log_n, usable_rows, d_sums, d_mins, (unsigned long long*)bad_bitmap_dev_or_null, W);
     });
     TRH_HIP_TRY(hipGetLastError());
-    TRH_HIP_TRY(hipMemcpyAsync(result.data(), d_result, result.size() * 8, hipMemcpyDeviceToHost, s));
-    TRH_HIP_TRY(hipStreamSynchronize(s));  // h_ptrs is reused by the next call
+    const u64 *sums, *mins;
+    TRH_TRY(verdict_read(c, s, &sums, &mins));  // the synchronisation: h_ptrs is reused by the next call
     for (uint32_t a = 0; a < e->n_outputs; ++a) {
-        n_bad[a] = result[2 * a];
-        first_bad_row[a] = result[2 * a] ? result[2 * a + 1] : (uint64_t)usable_rows;
+        n_bad[a] = sums[a];
+        first_bad_row[a] = min_or(mins[a], usable_rows);
     }
     return TRH_OK;
 }

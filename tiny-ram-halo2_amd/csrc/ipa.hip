@@ -294,7 +294,7 @@ int read_back(void* out, const void* dev, size_t bytes, hipStream_t s) {
         TRH_HIP_TRY(hipStreamSynchronize(s));
         return TRH_OK;
     }
-    if (!c.pinned_land) TRH_HIP_TRY(hipHostMalloc(&c.pinned_land, 4096, hipHostMallocDefault));
+    TRH_TRY(host_land(c, 4096, nullptr));
     TRH_HIP_TRY(hipMemcpyAsync(c.pinned_land, dev, bytes, hipMemcpyDeviceToHost, s));
     TRH_HIP_TRY(hipStreamSynchronize(s));
     memcpy(out, c.pinned_land, bytes);

@@ -91,7 +91,6 @@ struct Plan {
     u64 off_place, off_place_sums;        // records, record_scan_tiles x u32
     u64 off_row_address, off_row_time, off_row_value, off_row_source;  // row_cap x u32 each
     u64 off_last, off_last_sums;          // row_cap, row_scan_tiles x (u32, u32)
-    u64 off_result;                       // 4 x u64: first bad record, synthesized rows, inconsistent loads, first inconsistent load
     u64 bytes;
 };
 
@@ -117,7 +116,6 @@ TRH_HD Plan make_plan(u64 m, u64 t, u64 n, u32 word_bits) {
     p.off_row_source = take(4 * p.row_cap);
     p.off_last = take(8 * p.row_cap);
     p.off_last_sums = take(8 * p.row_scan_tiles);
-    p.off_result = take(4 * 8);
     p.bytes = at;
     return p;
 }

@@ -15,11 +15,13 @@
 //   columns   one lane per row: memtable::derive_row, thirteen conversions (csrc/witness.h) and 26 sixteen-byte stores, a wave writing
 //             2 KiB of each column in one piece; inconsistent loads counted (atomicAdd) and the first one named (atomicMin); rows behind
 //             the table zeroed.  The verdict is read back with the scratch's return to the pool (second host synchronisation)
+// What the host reads is ONE verdict (verdict.h) in the context: sums {rows that place adds, inconsistent loads}, mins {first bad record, first inconsistent load}.
 // Scans are multi-tile in the manner of lookup.hip's scan_tiles_kernel / scan_sums_kernel: a scan per tile, one workgroup over the tile
 // sums, and the consumer adds its tile's offset.  Tiles are sized for wave64: 256 lanes, 4 KiB (sort) and 1 - 2 KiB (scan) of the LDS.
 #include "ctx.h"
 #include "devmem.h"
 #include "memtable.h"
+#include "verdict.h"
 
 namespace trh {
 namespace {
@@ -233,17 +235,12 @@ __global__ void __launch_bounds__(MEM_THREADS) mem_last_scan_kernel(const u32* _
     }, rows, last, sums);
 }
 
-__device__ __forceinline__ void store_zero(uint4* p) {
-    p[0] = make_uint4(0u, 0u, 0u, 0u);
-    p[1] = make_uint4(0u, 0u, 0u, 0u);
-}
-
-// result[2] += inconsistent loads, result[3] = min(result[3], log index of one); source_fill (may be null): NO_SOURCE behind the table
+// *n_inconsistent += inconsistent loads, *first_inconsistent = min(., log index of one); source_fill (may be null): NO_SOURCE behind the table
 template <class F>
 __global__ void __launch_bounds__(MEM_THREADS) mem_columns_kernel(const u32* __restrict__ row_address, const u32* __restrict__ row_time, const u32* __restrict__ row_value,
                                                                   const u32* __restrict__ row_source, const uint2* __restrict__ last, const uint2* __restrict__ last_sums,
                                                                   const u32* __restrict__ store_bits, size_t rows, uint4* __restrict__ dst, size_t n,
-                                                                  u32* __restrict__ source_fill, unsigned long long* __restrict__ result) {
+                                                                  u32* __restrict__ source_fill, unsigned long long* __restrict__ n_inconsistent, unsigned long long* __restrict__ first_inconsistent) {
     for (size_t r = (size_t)blockIdx.x * MEM_THREADS + threadIdx.x; r < n; r += (size_t)gridDim.x * MEM_THREADS) {
         if (r >= rows) {
 #pragma unroll
@@ -262,15 +259,13 @@ __global__ void __launch_bounds__(MEM_THREADS) mem_columns_kernel(const u32* __r
         const u32 carried = row_value[holder];
         const Row row = derive_row(row_address[r], row_time[r], init, store, prev_time, prev_run_address, carried);
         if (!init && !store && row_value[r] != carried) {
-            atomicAdd(result + 2, 1ull);
-            atomicMin(result + 3, (unsigned long long)src);
+            atomicAdd(n_inconsistent, 1ull);
+            atomicMin(first_inconsistent, (unsigned long long)src);
         }
 #pragma unroll
         for (u32 c = 0; c < MEM_COLUMNS; ++c) store_fe(dst + 2 * ((size_t)c * n + r), fe_from_u64<F>((u64)row.c[c]));
     }
 }
-
-unsigned blocks_of(u64 count, u32 per_block) { return (unsigned)((count + per_block - 1) / per_block); }
 
 int check_args(int field, const trh_mem_table_args_t* a) {
     if (!a) { set_error("mem_table_dev: null arguments"); return TRH_EINVAL; }
@@ -290,8 +285,8 @@ int check_args(int field, const trh_mem_table_args_t* a) {
     return TRH_OK;
 }
 
-// everything queued between the scratch's allocation and its return; the first failure ends it
-int run(int field, trh_mem_table_args_t* a, const Plan& p, char* block, unsigned long long* land, Ctx& c) {
+// everything queued between the scratch's allocation and its return; the first failure ends it.  *sums / *mins: where the verdict lands (its second pair: once s has drained)
+int run(int field, trh_mem_table_args_t* a, const Plan& p, char* block, Ctx& c, const u64** sums, const u64** mins) {
     const hipStream_t s = (hipStream_t)a->stream;
     u32* keys[2] = {(u32*)(block + p.off_keys[0]), (u32*)(block + p.off_keys[1])};
     u32* index[2] = {(u32*)(block + p.off_index[0]), (u32*)(block + p.off_index[1])};
@@ -300,16 +295,14 @@ int run(int field, trh_mem_table_args_t* a, const Plan& p, char* block, unsigned
     u32 *row_address = (u32*)(block + p.off_row_address), *row_time = (u32*)(block + p.off_row_time), *row_value = (u32*)(block + p.off_row_value);
     u32* row_source = a->src_index ? a->src_index : (u32*)(block + p.off_row_source);
     uint2 *last = (uint2*)(block + p.off_last), *last_sums = (uint2*)(block + p.off_last_sums);
-    unsigned long long* result = (unsigned long long*)(block + p.off_result);
     const LogPtrs g{a->address, a->time, a->value, a->store_bits, a->tape, a->m, a->t, a->word_bits};
     const size_t count = (size_t)p.records;
 
-    // land[0 .. 3]: what the device's result words start from; land[4 .. 7]: where they come back
-    land[0] = ~0ull; land[1] = 0; land[2] = 0; land[3] = ~0ull;
-    TRH_HIP_TRY(hipMemcpyAsync(result, land, 32, hipMemcpyHostToDevice, s));
+    unsigned long long *d_sums, *d_mins;
+    TRH_TRY(verdict_begin(c, 2, 2, s, &d_sums, &d_mins));
     u32 sorted = 0;
     if (count) {
-        hipLaunchKernelGGL(mem_keys_kernel, dim3(blocks_of(count, MEM_THREADS)), dim3(MEM_THREADS), 0, s, g, keys[0], index[0], result);
+        hipLaunchKernelGGL(mem_keys_kernel, dim3(blocks_of(count, MEM_THREADS)), dim3(MEM_THREADS), 0, s, g, keys[0], index[0], d_mins);
         for (u32 pass = 0; pass < p.passes; ++pass, sorted ^= 1u) {
             const u32 shift = pass * RADIX_BITS;
             hipLaunchKernelGGL(mem_hist_kernel, dim3((unsigned)p.sort_tiles), dim3(MEM_THREADS), 0, s, (const u32*)keys[sorted], count, shift, hist);
@@ -320,18 +313,17 @@ int run(int field, trh_mem_table_args_t* a, const Plan& p, char* block, unsigned
         }
         hipLaunchKernelGGL(mem_place_scan_kernel, dim3((unsigned)p.record_scan_tiles), dim3(MEM_THREADS), 0, s, (const u32*)keys[sorted], (const u32*)index[sorted], (size_t)a->t, count,
                            place, place_sums);
-        // the total lands in the low word of result[1] (little-endian; the high word was cleared with it)
-        hipLaunchKernelGGL(mem_scan_sums_kernel<OpAdd>, dim3(1), dim3(MEM_THREADS), 0, s, place_sums, (u32)p.record_scan_tiles, (u32*)(result + 1));
+        // the total lands in the low word of sum 0 (little-endian; the high word was seeded zero with it)
+        hipLaunchKernelGGL(mem_scan_sums_kernel<OpAdd>, dim3(1), dim3(MEM_THREADS), 0, s, place_sums, (u32)p.record_scan_tiles, (u32*)d_sums);
         TRH_HIP_TRY(hipGetLastError());
     }
     // first synchronisation: the verdict on the log and the number of rows, before the destination is touched
-    TRH_HIP_TRY(hipMemcpyAsync(land + 4, result, 16, hipMemcpyDeviceToHost, s));
-    TRH_HIP_TRY(hipStreamSynchronize(s));
-    if (land[4] != ~0ull) {
-        set_error("mem_table_dev: log record %llu breaks the table's rules (address, time and value below 2^%u, times strictly increasing from 1)", land[4], a->word_bits);
+    TRH_TRY(verdict_read(c, s, sums, mins));
+    if (lowered((*mins)[0])) {
+        set_error("mem_table_dev: log record %llu breaks the table's rules (address, time and value below 2^%u, times strictly increasing from 1)", (unsigned long long)(*mins)[0], a->word_bits);
         return TRH_EINVAL;
     }
-    const u64 rows = p.records + land[5];
+    const u64 rows = p.records + (*sums)[0];
     a->rows = rows;
     if (rows > a->max_rows) { set_error("mem_table_dev: the table has %llu rows, max_rows is %zu", (unsigned long long)rows, a->max_rows); return TRH_EINVAL; }
     const u64 row_tiles = tiles_of(rows, SCAN_TILE);  // <= p.row_scan_tiles: rows <= row_cap
@@ -346,11 +338,11 @@ int run(int field, trh_mem_table_args_t* a, const Plan& p, char* block, unsigned
         with_field(field, [&](auto f) {
             hipLaunchKernelGGL((mem_columns_kernel<decltype(f)>), dim3(blocks < 4096u ? blocks : 4096u), dim3(MEM_THREADS), 0, s, (const u32*)row_address, (const u32*)row_time,
                                (const u32*)row_value, (const u32*)row_source, (const uint2*)last, (const uint2*)last_sums, a->store_bits, (size_t)rows, (uint4*)a->dst, a->n,
-                               a->src_index, result);
+                               a->src_index, d_sums + 1, d_mins + 1);
         });
     }
     TRH_HIP_TRY(hipGetLastError());
-    TRH_HIP_TRY(hipMemcpyAsync(land + 6, result + 2, 16, hipMemcpyDeviceToHost, s));
+    TRH_TRY(verdict_fetch(c, s));
     c.memtable_rows = rows;
     c.memtable_sort_passes = count ? p.passes : 0;
     const u64 tiles[3] = {p.sort_tiles, p.record_scan_tiles, row_tiles};
@@ -373,17 +365,16 @@ int trh_mem_table_dev(int field_id, trh_mem_table_args_t* a) {
     Ctx& c = ctx();
     a->rows = 0; a->n_inconsistent = 0; a->first_inconsistent = 0;
     const Plan p = make_plan(a->m, a->t, a->n, a->word_bits);
-    if (!c.pinned_land) TRH_HIP_TRY(hipHostMalloc(&c.pinned_land, 4096, hipHostMallocDefault));
     void* block = nullptr;
     TRH_TRY(trh_malloc(&block, (size_t)p.bytes));
-    unsigned long long* land = (unsigned long long*)c.pinned_land;
-    const int rc = run(field_id, a, p, (char*)block, land, c);
+    const u64 *sums = nullptr, *mins = nullptr;
+    const int rc = run(field_id, a, p, (char*)block, c, &sums, &mins);
     // second synchronisation: trh_free returns once the device has drained (as hipFree does), which is when the verdict has landed
     const int rc_free = trh_free(block);
     TRH_TRY(rc);
     TRH_TRY(rc_free);
-    a->n_inconsistent = land[6];
-    a->first_inconsistent = land[6] ? land[7] : a->m;
+    a->n_inconsistent = sums[1];
+    a->first_inconsistent = min_or(mins[1], a->m);
     return TRH_OK;
 }
 

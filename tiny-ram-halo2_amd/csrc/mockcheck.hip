@@ -2,12 +2,11 @@
 // halo2_proofs 0.2.0 dev.rs collects the table's rows of evaluated expressions and reports every usable row whose input tuple is not among
 // them.  Here the table's rows go into a lock-free open-addressing set of row indices (csrc/tuplehash.h: the hash, the slot sequence, insert
 // and probe, shared with the host test) and every input row probes it: exact tuple membership, not the theta compression of the prover.
-// The verdict leaves as in expr.hip's gate check: one ballot per wave of 64 consecutive rows, written by lane 0 as a bitmap word, and one
-// atomicAdd / atomicMin per wave that saw a bad row.
-#include <vector>
-
+// The verdict leaves as in expr.hip's gate check (verdict.h): one ballot per wave of 64 consecutive rows, written by lane 0 as a bitmap
+// word, and one atomicAdd / atomicMin per wave that saw a bad row.  Sums: bad rows, slots visited; min: the smallest bad row.
 #include "ctx.h"
 #include "tuplehash.h"
+#include "verdict.h"
 
 namespace trh {
 namespace {
@@ -38,22 +37,16 @@ __global__ void __launch_bounds__(MC_BLOCK) tuple_insert_kernel(u32* __restrict_
 }
 
 // cols: the `width` input columns, then the `width` table columns.  One thread per input row; rows at or beyond usable_rows are never read.
-// result[0] += bad rows, result[1] = min(result[1], smallest bad row); bitmap (may be null): ceil(usable_rows / 64) words, every one written.
+// *n_bad += bad rows, *first_bad = min(*first_bad, smallest bad row); bitmap (may be null): ceil(usable_rows / 64) words, every one written.
 __global__ void __launch_bounds__(MC_BLOCK) tuple_probe_kernel(const u32* __restrict__ slots, u64 capacity, const void* const* __restrict__ cols, u32 width,
-                                                               size_t usable_rows, unsigned long long* __restrict__ result, unsigned long long* __restrict__ bitmap,
-                                                               unsigned long long* __restrict__ probes) {
+                                                               size_t usable_rows, unsigned long long* __restrict__ n_bad, unsigned long long* __restrict__ first_bad,
+                                                               unsigned long long* __restrict__ bitmap, unsigned long long* __restrict__ probes) {
     const size_t gid = (size_t)blockIdx.x * MC_BLOCK + threadIdx.x;
     u32 visited = 0;
     bool bad = false;
     if (gid < usable_rows) bad = !tuplehash::probe_row(slots, capacity, cols, cols + width, width, gid, &visited);
-    const unsigned long long ballot = __ballot(bad);
-    if ((threadIdx.x & 63) == 0) {
-        if (bitmap && (gid >> 6) < (usable_rows + 63) / 64) bitmap[gid >> 6] = ballot;
-        if (ballot) {
-            atomicAdd(result, (unsigned long long)__popcll(ballot));
-            atomicMin(result + 1, (unsigned long long)(gid + (size_t)(__ffsll((long long)ballot) - 1)));
-        }
-    }
+    const unsigned long long ballot = wave_verdict(bad, gid, n_bad, first_bad);
+    if ((threadIdx.x & 63) == 0 && bitmap && (gid >> 6) < (usable_rows + 63) / 64) bitmap[gid >> 6] = ballot;
     wave_add(probes, visited);
 }
 
@@ -83,33 +76,32 @@ int trh_lookup_check_dev(int field_id, const void* const* inputs_dev, const void
     Range range("trh_lookup_check_dev");
     Ctx& c = ctx();
     const hipStream_t s = nullptr;
-    // one block of the device pool: the slots, the column pointers, then (bad rows, smallest bad row, slots visited)
+    // one block of the device pool: the slots, then the column pointers
     const u64 capacity = tuplehash::capacity_for(usable_rows);
     const size_t slot_bytes = (size_t)capacity * sizeof(u32), ptr_bytes = 2 * (size_t)width * sizeof(void*);
     void* block = nullptr;
-    TRH_TRY(trh_malloc(&block, slot_bytes + ptr_bytes + 3 * sizeof(unsigned long long)));
+    unsigned long long *d_sums, *d_min;
+    TRH_TRY(verdict_begin(c, 2, 1, s, &d_sums, &d_min));
+    TRH_TRY(trh_malloc(&block, slot_bytes + ptr_bytes));
     u32* d_slots = (u32*)block;
     const void** d_cols = (const void**)((char*)block + slot_bytes);
-    unsigned long long* d_result = (unsigned long long*)((char*)block + slot_bytes + ptr_bytes);
-    unsigned long long result[3] = {0, ~0ull, 0};
-    const unsigned blocks = (unsigned)((usable_rows + MC_BLOCK - 1) / MC_BLOCK);
+    const unsigned blocks = blocks_of(usable_rows, MC_BLOCK);
+    const u64 *sums = nullptr, *min = nullptr;
     hipError_t err = hipMemsetAsync(d_slots, 0xFF, slot_bytes, s);
     if (err == hipSuccess) err = hipMemcpyAsync(d_cols, h_cols, ptr_bytes, hipMemcpyHostToDevice, s);
-    if (err == hipSuccess) err = hipMemcpyAsync(d_result, result, sizeof(result), hipMemcpyHostToDevice, s);
     if (err == hipSuccess) {
-        hipLaunchKernelGGL(tuple_insert_kernel, dim3(blocks), dim3(MC_BLOCK), 0, s, d_slots, capacity, (const void* const*)(d_cols + width), width, usable_rows, d_result + 2);
-        hipLaunchKernelGGL(tuple_probe_kernel, dim3(blocks), dim3(MC_BLOCK), 0, s, (const u32*)d_slots, capacity, (const void* const*)d_cols, width, usable_rows, d_result,
-                           (unsigned long long*)bad_bitmap_dev_or_null, d_result + 2);
+        hipLaunchKernelGGL(tuple_insert_kernel, dim3(blocks), dim3(MC_BLOCK), 0, s, d_slots, capacity, (const void* const*)(d_cols + width), width, usable_rows, d_sums + 1);
+        hipLaunchKernelGGL(tuple_probe_kernel, dim3(blocks), dim3(MC_BLOCK), 0, s, (const u32*)d_slots, capacity, (const void* const*)d_cols, width, usable_rows, d_sums, d_min,
+                           (unsigned long long*)bad_bitmap_dev_or_null, d_sums + 1);
         err = hipGetLastError();
     }
-    if (err == hipSuccess) err = hipMemcpyAsync(result, d_result, sizeof(result), hipMemcpyDeviceToHost, s);
-    if (err == hipSuccess) err = hipStreamSynchronize(s);
+    if (err == hipSuccess && verdict_read(c, s, &sums, &min) != TRH_OK && (err = hipGetLastError()) == hipSuccess) err = hipErrorUnknown;  // reported in this entry's own text
     const int rc_free = trh_free(block);
     if (err != hipSuccess) { set_error("lookup_check: %s", hipGetErrorString(err)); return TRH_EHIP; }
     TRH_TRY(rc_free);
-    c.lookup_check_probes = result[2];
-    *n_bad = result[0];
-    *first_bad_row = result[0] ? result[1] : (uint64_t)usable_rows;
+    c.lookup_check_probes = sums[1];
+    *n_bad = sums[0];
+    *first_bad_row = min_or(min[0], usable_rows);
     return TRH_OK;
 }
 

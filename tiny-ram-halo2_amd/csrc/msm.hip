@@ -1582,7 +1582,7 @@ int reserve_scratch(const MsmRun& r) {
     TRH_TRY(L.parted.ensure(p.entries_bytes()));
     TRH_TRY(L.sorted.ensure(p.entries_bytes()));
     TRH_TRY(L.counts.ensure(p.counts_bytes()));
-    if (p.adaptive && !r.c->pinned_land) TRH_HIP_TRY(hipHostMalloc(&r.c->pinned_land, 4096, hipHostMallocDefault));  // (size_segments reads a chunk's entry totals back only where nb x Ws x 4 B fit it)
+    if (p.adaptive) TRH_TRY(host_land(*r.c, 4096, nullptr));  // (size_segments reads a chunk's entry totals back only where nb x Ws x 4 B fit it)
     TRH_TRY(L.bin_starts.ensure(p.bins_bytes(p.chunk)));
     TRH_TRY(L.starts.ensure(p.ranges_bytes(p.chunk)));
     TRH_TRY(L.bucket_cnt.ensure(p.ranges_bytes(p.chunk) + 16));

@@ -15,6 +15,7 @@
 #include "ctx.h"
 #include "devmem.h"
 #include "permkeygen.h"
+#include "verdict.h"
 
 struct trh_perm_s {
     std::mutex mu;  // guards the assembly and the device copies; taken INSIDE a context's lock by the device entries
@@ -45,12 +46,10 @@ __global__ void __launch_bounds__(PERM_BLOCK) perm_sigma_kernel(const u32* __res
     store_fe(out + 2 * i, fe_mul(load_fe<F>(delta_tab + 2 * (size_t)col), load_fe<F>(omega_tab + 2 * (size_t)row)));
 }
 
-// result[0] += cells with value[cell] != value[mapping[cell]], result[1] = min(result[1], smallest such cell).  Columns hold canonical stored
-// forms, so the eight words are compared as they are.  Lanes hold consecutive cells: the first set bit of a wave's ballot is its smallest.
+// *n_bad += cells with value[cell] != value[mapping[cell]], *first_bad = min(*first_bad, smallest such cell).  Columns hold canonical stored
+// forms, so the eight words are compared as they are.  Lanes hold consecutive cells, so the kernel ends in verdict.h's ballot tail.
 __global__ void __launch_bounds__(PERM_BLOCK) perm_check_kernel(const u32* __restrict__ mapping, size_t cells, u32 k, const uint4* const* __restrict__ columns,
-                                                                unsigned long long* __restrict__ result) {
-    __shared__ u32 s_cnt[PERM_BLOCK / 64];
-    __shared__ unsigned long long s_min[PERM_BLOCK / 64];
+                                                                unsigned long long* __restrict__ n_bad, unsigned long long* __restrict__ first_bad) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     bool bad = false;
     if (i < cells) {
@@ -61,25 +60,7 @@ __global__ void __launch_bounds__(PERM_BLOCK) perm_check_kernel(const u32* __res
         const uint4 a0 = a[0], a1 = a[1], b0 = b[0], b1 = b[1];
         bad = ((a0.x ^ b0.x) | (a0.y ^ b0.y) | (a0.z ^ b0.z) | (a0.w ^ b0.w) | (a1.x ^ b1.x) | (a1.y ^ b1.y) | (a1.z ^ b1.z) | (a1.w ^ b1.w)) != 0;
     }
-    const unsigned long long ballot = __ballot(bad);
-    const unsigned wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        s_cnt[wave] = (u32)__popcll(ballot);
-        s_min[wave] = ballot ? (unsigned long long)(i + (size_t)(__ffsll((long long)ballot) - 1)) : ~0ull;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u32 cnt = 0;
-        unsigned long long mn = ~0ull;
-        for (unsigned w = 0; w < PERM_BLOCK / 64; ++w) {
-            cnt += s_cnt[w];
-            if (s_min[w] < mn) mn = s_min[w];
-        }
-        if (cnt) {
-            atomicAdd(result, (unsigned long long)cnt);
-            atomicMin(result + 1, mn);
-        }
-    }
+    wave_verdict(bad, i, n_bad, first_bad);
 }
 
 int perm_grid(const char* who, size_t cells, unsigned* blocks) {
@@ -267,20 +248,19 @@ int trh_perm_check_dev(trh_perm_t p, int field, const void* const* columns_dev, 
     TRH_TRY(perm_grid("perm_check_dev", a.cells, &blocks));
     const u32* d_mapping = nullptr;
     TRH_TRY(perm_device_mapping(p, s, &d_mapping));
-    // scratch: the two result words, then the column pointers
+    // scratch: the column pointers
     const size_t ptr_bytes = (size_t)a.n_columns * sizeof(void*);
-    TRH_TRY(c.scan.ensure(16 + ptr_bytes));
-    unsigned long long* d_result = c.scan.as<unsigned long long>();
-    const uint4** d_columns = (const uint4**)(d_result + 2);
-    unsigned long long result[2] = {0, ~0ull};
-    TRH_HIP_TRY(hipMemcpyAsync(d_result, result, sizeof(result), hipMemcpyHostToDevice, s));
+    TRH_TRY(c.scan.ensure(ptr_bytes));
+    const uint4** d_columns = c.scan.as<const uint4*>();
+    unsigned long long *d_sum, *d_min;
+    TRH_TRY(verdict_begin(c, 1, 1, s, &d_sum, &d_min));
     TRH_HIP_TRY(hipMemcpyAsync(d_columns, columns_dev, ptr_bytes, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(perm_check_kernel, dim3(blocks), dim3(PERM_BLOCK), 0, s, d_mapping, a.cells, (u32)a.k, (const uint4* const*)d_columns, d_result);
+    hipLaunchKernelGGL(perm_check_kernel, dim3(blocks), dim3(PERM_BLOCK), 0, s, d_mapping, a.cells, (u32)a.k, (const uint4* const*)d_columns, d_sum, d_min);
     TRH_HIP_TRY(hipGetLastError());
-    TRH_HIP_TRY(hipMemcpyAsync(result, d_result, sizeof(result), hipMemcpyDeviceToHost, s));
-    TRH_HIP_TRY(hipStreamSynchronize(s));  // the caller's pointer array and `result` have been read / written by now
-    *n_bad = result[0];
-    *first_bad_cell = result[0] ? result[1] : (uint64_t)a.cells;
+    const u64 *sum, *min;
+    TRH_TRY(verdict_read(c, s, &sum, &min));  // the synchronisation: the caller's pointer array has been read by now
+    *n_bad = sum[0];
+    *first_bad_cell = min_or(min[0], a.cells);
     return TRH_OK;
 }
 

@@ -22,11 +22,6 @@ constexpr unsigned WIT_GRID_BLOCKS = 4096;
 // is max(WIT_STAGE_BYTES, one packed column) -- at most a quarter of the destination it fills
 constexpr size_t WIT_STAGE_BYTES = (size_t)64 << 20;
 
-__device__ __forceinline__ void store_zero(uint4* p) {
-    p[0] = make_uint4(0u, 0u, 0u, 0u);
-    p[1] = make_uint4(0u, 0u, 0u, 0u);
-}
-
 template <class F, class T>
 __device__ __forceinline__ Fe<F> fe_from_int(T v) {
     if constexpr (std::is_signed<T>::value) return fe_from_i64<F>((i64)v);
