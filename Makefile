@@ -15,10 +15,11 @@ ID_OBJ := $(CSRC)/capi.o
 # (test_gpu_encoding.py), trh::Rng (test_gpu_rng.py), trh::PermutationAssembly (test_gpu_permkeygen.py), trh::Params::create
 # (test_gpu_hashtocurve.py), GateEvaluator::check and lookup_check (test_gpu_mock.py), trh::QuotientTerms (test_gpu_quotient.py),
 # columns_from_ints / even_odd_split / even_bits_table (test_gpu_witness.py), trh::mem_table (test_gpu_memtable.py),
-# trh::exe_table (test_gpu_exetable.py)
-HPP_TESTS := $(addprefix tests/native/,params_io_test rng_fill_test perm_assembly_test params_new_test mock_check_test quotient_test witness_test memtable_test exetable_test)
+# trh::exe_table (test_gpu_exetable.py), trh::exe_chips (test_gpu_exechips.py)
+HPP_TESTS := $(addprefix tests/native/,params_io_test rng_fill_test perm_assembly_test params_new_test mock_check_test quotient_test witness_test memtable_test exetable_test \
+    exechips_test)
 NATIVE := examples/replay tests/native/libtrh_q4broken.so $(HPP_TESTS) $(addprefix tests/native/,multi_ctx_test lazy29_dev_test lazy29_alias_test lazy29_segment_test \
-    foldplan_test permkeygen_test hashtocurve_vec_test transcript_test witness_vec_test memtable_vec_test exetable_vec_test)
+    foldplan_test permkeygen_test hashtocurve_vec_test transcript_test witness_vec_test memtable_vec_test exetable_vec_test exechips_vec_test)
 
 all: $(PKG)/libtrh.so oracle $(NATIVE)
 
@@ -103,6 +104,17 @@ tests/native/memtable_vec_test: tests/native/memtable_vec_test.cpp $(CSRC)/memta
 # (which checks it against tests/exetable_model.py)
 tests/native/exetable_vec_test: tests/native/exetable_vec_test.cpp $(CSRC)/exetable.h $(CSRC)/witness.h $(CSRC)/field.h include/trh.h
 	g++ -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -fsanitize=address,undefined -fno-sanitize-recover=all $< -o $@
+
+# the chips part of csrc/exetable.h (the layout, the rules of a chips table, one row's cells) on the host, under address + undefined
+# sanitizers: reads cases, prints results; never loads libtrh; run by tests/test_exechips_host.py (which checks it against
+# tests/exechips_model.py)
+tests/native/exechips_vec_test: tests/native/exechips_vec_test.cpp $(CSRC)/exetable.h $(CSRC)/witness.h $(CSRC)/field.h include/trh.h
+	g++ -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -fsanitize=address,undefined -fno-sanitize-recover=all $< -o $@
+
+# the inversion kernel of trh_exe_chips_dev (csrc/exechips_inv.h) at strips of 1, 4 and 8 rows per lane, timed on its own; not part of
+# `all`: tools/exechips_probe.py runs it when it has been built
+tools/exechips_inv_probe: tools/exechips_inv_probe.hip $(HDRS)
+	$(HIPCC) $(HIPFLAGS) $< -o $@
 
 oracle:
 	$(MAKE) -s -C oracle libtrh_oracle.so

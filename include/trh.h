@@ -809,6 +809,69 @@ typedef struct trh_exe_table_args {
 } trh_exe_table_args_t;
 int trh_exe_table_dev(int field_id, trh_exe_table_args_t* args);
 
+/* ---- the Exe chips: Out, the changed flags and the sub-chips' advice, on the device ---------------------------------------------------------
+ * The rest of what ExeChip::assign_trace (exe.rs:849-1067) writes per row: the Out selectors, ChangedSelectors, and the intermediates of the
+ * logic, ssum, sprod, shift and flag2 - flag4 chips.  They are functions of the row's a, b, c, d, of the SUCCESSOR's flag (flag', 0 behind
+ * the last step) and of a second per-opcode table.  The step arrays, selection and their rules are those of trh_exe_table_args_t; the entry
+ * derives a, b, c, d itself, reads no column of trh_exe_table_dev, and the two can run in either order.
+ * chips[opcode] is DATA like selection[opcode]: TRH_CHIP_* bits, or TRH_EXE_UNKNOWN.  Bits 0 - 12 are the reference's Out in Out::new order
+ * (and xor or sum prod ssum sprod mod shift flag1 flag2 flag3 flag4), bit 13 is b_flag (flag4 reads the top bit of b: a left shift), bits
+ * 14 - 16 are ch_pc, ch_flag, ch_reg[ri].  The default table (exetable.DEFAULT_CHIPS, trh::exe_default_chips) restates out.rs:148-349 and
+ * the `ch:` fields of aux.rs:109-396.
+ * dst: 52 + reg_count columns of n rows, cells as in trh_exe_table_dev, rows m .. n - 1 WRITTEN as zero:
+ *   out_and out_xor out_or out_sum out_prod out_ssum out_sprod out_mod out_shift out_flag1 out_flag2 out_flag3 out_flag4
+ *   ch_reg[reg_count] ch_pc ch_flag
+ *   a_even a_odd b_even b_odd c_even c_odd d_even d_odd          one decomposition per variable (the reference allocates a's twice: bind
+ *                                                                the same column twice)
+ *   es_word es_even es_odd os_word os_even os_odd                logic: a_even + b_even, a_odd + b_odd, and their halves
+ *   sg_a_msb sg_a_sigma sg_a_check sg_a_check_even sg_a_check_odd, the same for sg_b_ and sg_c_
+ *   r_word r_even r_odd | a_shift a_power | a_flag | lsb_b b_flag
+ * A cell is computed on a row whose chips entry has one of the cell's enabling bits and is ZERO elsewhere (the reference fills with
+ * 2^64 - 1):
+ *   a halves   mod and or xor ssum sprod            even / odd bits of a         b halves   mod sum ssum sprod flag4 and xor or
+ *   c halves   xor prod shift ssum sprod                                         d halves   prod sprod
+ *   es_*, os_* and xor or
+ *   sg_a_*     ssum sprod     msb = bit W - 1, sigma = |a as a signed word|, check = a_odd + (1 - 2 msb) 2^(W - 2), check's halves
+ *   sg_b_*     sprod flag4                          sg_c_*     ssum sprod
+ *   r_*        flag3: c == 0 ? 0 : c - a - 1        shift: a > W ? 0 : W - a
+ *   a_shift, a_power   shift: a > W; 2^min(a, W) (0 for a negative a)
+ *   a_flag     flag2: the inverse of c + flag' in the field, 0 when c + flag' = 0
+ *   lsb_b, b_flag      flag4: b & 1; bit 13 of the entry
+ * a .. d are the signed integers of trh_exe_table_dev's rules (SHR_LO can be negative, pc + 1 can be 2^W).  A _word cell carries the
+ * integer, a negative one as m - |v|; halves, msb, sigma and check come from an input that is a word (0 <= v < 2^W), otherwise all cells of
+ * that group are zero.  VM semantics are not checked.
+ * Two departures from the reference:
+ *   saturated shifts  assign_shift writes a_power = 0 at A == W and overflows 2u64.pow above; with its own c, d the gate
+ *     a_power b - d - 2^W c then fails at A == W.  Here a_power = 2^min(a, W), which with SHL_HI / SHR_LO's s = min(A, W) satisfies the gate
+ *     for every A; the pow lookup table that goes with it carries (W, 2^W) where pow.rs:58-62 has (W, 0);
+ *   a_flag  the reference inverts on every row and draws a random value when c + flag' = 0; here flag2 rows only, and 0 there.
+ * Refusals (TRH_EINVAL, nothing written to dst): everything trh_exe_table_dev refuses, in its words; word_bits odd (the signed check puts
+ * the sign at an odd bit, the even-bits table has 2^(W/2) rows); a chips entry, named by its opcode, with a bit above 16, with flag3 and
+ * shift together (they share r_*), with bit 13 and no flag4, or known where selection's is unknown or the other way round.
+ * One synchronisation, as in trh_exe_table_dev: the verdict on the steps; the row kernel and the inversion of the a_flag column (one field
+ * inversion per strip of rows, Montgomery's trick) are queued behind it.  trh_stat "exechips_rows": the m of the last call that passed
+ * validation; "exechips_flag2_rows": the flag2 rows its inversion kernel visited.
+ * Measured on an MI355X at k = 18, reg_count = 8, word_bits = 32 (profiles/exechips_probe.txt): the entry 0.347 ms, 4.31 times a fill of
+ * its 503 MB; the row kernel alone 1.35 times the fill; the inversion 0.186 ms of the entry -- alone 87, 28 and 27 times the fill of its
+ * column at strips of 1, 4 and 8 rows per lane, the latency of one field inversion from a strip of 4 on.                                */
+enum { TRH_CHIP_AND = 1 << 0, TRH_CHIP_XOR = 1 << 1, TRH_CHIP_OR = 1 << 2, TRH_CHIP_SUM = 1 << 3, TRH_CHIP_PROD = 1 << 4, TRH_CHIP_SSUM = 1 << 5,
+       TRH_CHIP_SPROD = 1 << 6, TRH_CHIP_MOD = 1 << 7, TRH_CHIP_SHIFT = 1 << 8, TRH_CHIP_FLAG1 = 1 << 9, TRH_CHIP_FLAG2 = 1 << 10, TRH_CHIP_FLAG3 = 1 << 11,
+       TRH_CHIP_FLAG4 = 1 << 12, TRH_CHIP_B_FLAG = 1 << 13, TRH_CHIP_CH_PC = 1 << 14, TRH_CHIP_CH_FLAG = 1 << 15, TRH_CHIP_CH_REG = 1 << 16 };
+typedef struct trh_exe_chips_args {
+    uint32_t word_bits;                        /* even, 2 .. 32 */
+    uint32_t reg_count;                        /* 1 .. 16 */
+    const uint32_t *pc, *inst, *a, *value;     /* device, m each, in execution order */
+    const uint32_t *regs;                      /* device, m x reg_count, step-major */
+    const uint32_t *flag_bits;                 /* device, ceil(m / 32) words */
+    size_t m;
+    uint32_t selection[32];                    /* by opcode: TRH_EXE_ENTRY(a, b, c, d) or TRH_EXE_UNKNOWN */
+    uint32_t chips[32];                        /* by opcode: TRH_CHIP_* bits or TRH_EXE_UNKNOWN */
+    void*  dst;                                /* device, (52 + reg_count) x n x 4 u64, 16-byte aligned, canonical Montgomery words */
+    size_t n;                                  /* rows per column, > m */
+    void*  stream;
+} trh_exe_chips_args_t;
+int trh_exe_chips_dev(int field_id, trh_exe_chips_args_t* args);
+
 /* ---- element-wise field / group ops on device memory (parity tests of the device arithmetic;
  *      op: 0 add, 1 sub, 2 mul, 3 sqr, 4 neg, 5 inv, 6 to_mont, 7 from_mont) ------------------ */
 int trh_field_op_dev(int field, int op, const void* a_dev, const void* b_dev, void* out_dev, size_t n, void* stream);
@@ -848,7 +911,9 @@ int trh_stream_synchronize(void* stream);
  * per element (1 from 2^26 elements, where the last pass's table would exceed 1.125 GiB; 0 below);
  * "lookup_check_probes": the slots of the set visited by the two kernels (insert, probe) of the last trh_lookup_check_dev on this context;
  * "memtable_rows", "memtable_sort_passes", "memtable_tiles": the last trh_mem_table_dev on this context (described with that entry);
- * "exetable_rows": the steps of the last trh_exe_table_dev on this context that passed validation. */
+ * "exetable_rows": the steps of the last trh_exe_table_dev on this context that passed validation;
+ * "exechips_rows": the same of trh_exe_chips_dev; "exechips_flag2_rows": the rows with the flag2 bit that the inversion kernel of the last
+ * trh_exe_chips_dev on this context visited (synchronises the device, for tests). */
 int trh_stat(const char* name, uint64_t* value);
 /* GPU-side timing without HIP headers: events recorded on a stream between the steps (a hipEvent_t each), read afterwards.
  * trh_event_elapsed_ms waits for `end` and returns the device time between the two records. */

@@ -704,6 +704,49 @@ inline void exe_table(Field f, uint32_t word_bits, uint32_t reg_count, const uin
     check(trh_exe_table_dev((int)f, &a), "exe_table");
 }
 
+// ---- the Exe chips (trh_exe_chips_dev): the same steps -> Out, the changed flags and the sub-chips' advice ----------------------------------
+// ExeChips: TRH_CHIP_* bits per opcode, TRH_EXE_UNKNOWN for an opcode the table does not know (exactly those the selection does not know).
+// exe_default_chips() restates the reference's OutPut::OUT (out.rs:148-349) and the `ch:` fields of TempVarSelectorsRow::from.
+typedef std::array<uint32_t, 32> ExeChips;
+inline ExeChips exe_default_chips() {
+    ExeChips t;
+    t.fill(TRH_EXE_UNKNOWN);
+    const uint32_t f12 = TRH_CHIP_FLAG1 | TRH_CHIP_FLAG2, reg = TRH_CHIP_CH_REG, flag = TRH_CHIP_CH_FLAG, pc = TRH_CHIP_CH_PC;
+    t[0] = TRH_CHIP_AND | f12 | reg | flag;                                     // and
+    t[1] = TRH_CHIP_OR | f12 | reg | flag;                                      // or
+    t[2] = t[3] = TRH_CHIP_XOR | f12 | reg | flag;                              // xor, not
+    t[4] = t[5] = TRH_CHIP_SUM | reg | flag;                                    // add, sub
+    t[6] = t[7] = TRH_CHIP_PROD | f12 | reg | flag;                             // mull, umulh
+    t[8] = TRH_CHIP_SPROD | f12 | reg | flag;                                   // smulh
+    t[9] = t[10] = TRH_CHIP_MOD | f12 | TRH_CHIP_FLAG3 | reg | flag;            // udiv, umod
+    t[11] = TRH_CHIP_SHIFT | TRH_CHIP_FLAG4 | TRH_CHIP_B_FLAG | reg | flag;     // shl: flag4 reads b's top bit
+    t[12] = TRH_CHIP_SHIFT | TRH_CHIP_FLAG4 | reg | flag;                       // shr
+    t[13] = TRH_CHIP_XOR | f12 | flag;                                          // cmpe
+    t[14] = t[15] = TRH_CHIP_SUM | flag;                                        // cmpa, cmpae
+    t[16] = t[17] = TRH_CHIP_SSUM | flag;                                       // cmpg, cmpge
+    t[18] = TRH_CHIP_XOR | reg;                                                 // mov
+    t[19] = TRH_CHIP_MOD | reg;                                                 // cmov
+    t[20] = TRH_CHIP_XOR | pc;                                                  // jmp
+    t[21] = t[22] = TRH_CHIP_MOD | pc;                                          // cjmp, cnjmp
+    t[28] = TRH_CHIP_XOR;                                                       // store.w
+    t[29] = reg;                                                                // load.w
+    t[31] = 0;                                                                  // answer
+    return t;
+}
+inline size_t exe_chip_columns(uint32_t reg_count) { return 52 + (size_t)reg_count; }
+// the step arrays as in exe_table; dst_dev: exe_chip_columns(reg_count) x n elements; word_bits even.  Throws (check) on refused steps or a
+// bad table; synchronises with the host once.
+inline void exe_chips(Field f, uint32_t word_bits, uint32_t reg_count, const uint32_t* pc_dev, const uint32_t* inst_dev, const uint32_t* a_dev, const uint32_t* value_dev,
+                      const uint32_t* regs_dev, const uint32_t* flag_bits_dev, size_t m, void* dst_dev, size_t n, const ExeSelection& selection = exe_default_selection(),
+                      const ExeChips& chips = exe_default_chips(), void* stream = nullptr) {
+    trh_exe_chips_args_t a{};
+    a.word_bits = word_bits; a.reg_count = reg_count;
+    a.pc = pc_dev; a.inst = inst_dev; a.a = a_dev; a.value = value_dev; a.regs = regs_dev; a.flag_bits = flag_bits_dev; a.m = m;
+    for (size_t o = 0; o < selection.size(); ++o) { a.selection[o] = selection[o]; a.chips[o] = chips[o]; }
+    a.dst = dst_dev; a.n = n; a.stream = stream;
+    check(trh_exe_chips_dev((int)f, &a), "exe_chips");
+}
+
 // ---- plonk::permutation::keygen::Assembly (trh_perm_*): the copy constraints of the equality-enabled columns, the sigma columns they
 // induce -- made on the device -- and what keygen_vk / keygen_pk derive from them ---------------------------------------------------------
 // copy() merges cycles exactly as upstream does (the order of the copies decides the mapping).  Host memory, like Rng: copies and mapping()

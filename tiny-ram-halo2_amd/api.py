@@ -103,6 +103,13 @@ class ExeTableArgs(ctypes.Structure):
                 ("dst", ctypes.c_void_p), ("n", ctypes.c_size_t), ("stream", ctypes.c_void_p)]
 
 
+class ExeChipsArgs(ctypes.Structure):
+    """trh_exe_chips_args_t"""
+    _fields_ = [("word_bits", ctypes.c_uint32), ("reg_count", ctypes.c_uint32), ("pc", ctypes.c_void_p), ("inst", ctypes.c_void_p), ("a", ctypes.c_void_p),
+                ("value", ctypes.c_void_p), ("regs", ctypes.c_void_p), ("flag_bits", ctypes.c_void_p), ("m", ctypes.c_size_t), ("selection", ctypes.c_uint32 * 32),
+                ("chips", ctypes.c_uint32 * 32), ("dst", ctypes.c_void_p), ("n", ctypes.c_size_t), ("stream", ctypes.c_void_p)]
+
+
 _SIGNATURES = {
     "trh_init": ([ctypes.c_int], ctypes.c_int),
     "trh_shutdown": ([], None),
@@ -278,6 +285,7 @@ _SIGNATURES = {
     "trh_even_bits_table_dev": ([ctypes.c_int, ctypes.POINTER(EvenBitsTableArgs)], ctypes.c_int),
     "trh_mem_table_dev": ([ctypes.c_int, ctypes.POINTER(MemTableArgs)], ctypes.c_int),
     "trh_exe_table_dev": ([ctypes.c_int, ctypes.POINTER(ExeTableArgs)], ctypes.c_int),
+    "trh_exe_chips_dev": ([ctypes.c_int, ctypes.POINTER(ExeChipsArgs)], ctypes.c_int),
     "trh_set_timing": ([ctypes.c_int], ctypes.c_int),
     "trh_last_timing": ([ctypes.POINTER(Timing)], ctypes.c_int),
 }

@@ -195,6 +195,7 @@ static void destroy_ctx(Ctx* c) {
             c->factors.release();
             if (c->pinned_ring) { (void)hipHostFree(c->pinned_ring); c->pinned_ring = nullptr; c->pinned_slot = 0; }
             c->verdict.dev.release();  // the verdict words and where they land
+            c->exechips_flag2.release();
             if (c->pinned_land) { (void)hipHostFree(c->pinned_land); c->pinned_land = nullptr; c->pinned_land_cap = 0; }
             c->pfft.release();
             c->scan.release(); c->scan2.release();
@@ -455,7 +456,7 @@ int trh_stat(const char* name, uint64_t* value) {
         {"msm_host_ranges", m.host_ranges}, {"msm_range_tiles", m.range_tiles}, {"ntt_tableless_passes", c.ntt_tableless_passes},
         {"ipa_generator_collapses", c.ipa.collapses}, {"lookup_check_probes", c.lookup_check_probes},
         {"memtable_rows", c.memtable_rows}, {"memtable_sort_passes", c.memtable_sort_passes}, {"memtable_tiles", c.memtable_tiles},
-        {"exetable_rows", c.exetable_rows}};
+        {"exetable_rows", c.exetable_rows}, {"exechips_rows", c.exechips_rows}};
     for (const auto& k : counters) if (strcmp(name, k.name) == 0) { *value = k.value; return TRH_OK; }
     if (strcmp(name, "msm_bin_sorted_windows") == 0) {  // synchronises the device: tests only
         *value = 0;
@@ -464,6 +465,13 @@ int trh_stat(const char* name, uint64_t* value) {
         TRH_HIP_TRY(hipDeviceSynchronize());
         TRH_HIP_TRY(hipMemcpy(flags.data(), m.sort_flags, flags.size() * 4, hipMemcpyDeviceToHost));
         for (u32 k = 0; k < m.sort_flag_count; ++k) *value += flags[k] == 0u;
+        return TRH_OK;
+    }
+    if (strcmp(name, "exechips_flag2_rows") == 0) {  // synchronises the device: tests only
+        *value = 0;
+        if (!c.exechips_flag2.p) return TRH_OK;
+        TRH_HIP_TRY(hipDeviceSynchronize());
+        TRH_HIP_TRY(hipMemcpy(value, c.exechips_flag2.p, 8, hipMemcpyDeviceToHost));
         return TRH_OK;
     }
     set_error("trh_stat: unknown counter '%s'", name);

@@ -248,6 +248,8 @@ struct Ctx {
     u64 memtable_rows = 0, memtable_sort_passes = 0, memtable_tiles = 0;  // of the last trh_mem_table_dev that got as far as its row count (memtable.hip; tests)
     VerdictWords verdict;            // the one verdict a context has open at a time (verdict.h)
     u64 exetable_rows = 0;           // steps of the last trh_exe_table_dev that passed validation (tests)
+    u64 exechips_rows = 0;           // the same of trh_exe_chips_dev
+    DevBuf exechips_flag2;           // one u64: the verdict sum word of the last trh_exe_chips_dev's inversion kernel, copied on its stream (exechips.hip; tests)
     int cu_count = 0;               // compute units of the device (persistent kernels size their grids by it); 0: not asked yet
     unsigned attr_done = 0;          // hipFuncSetAttribute is per device: bit per kernel family already configured for this context's device
     hipStream_t own_stream = nullptr;  // the multi-device MSM driver enqueues this context's shard here

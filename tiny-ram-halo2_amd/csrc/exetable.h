@@ -2,7 +2,8 @@
 // decode of a packed instruction, the rule a selection table and a step must keep, the layout of the columns, and exe_row(), which yields one
 // row's values and the one-hot selector of each temporary variable.  exetable.hip writes the table with them;
 // tests/native/exetable_vec_test.cpp drives the same functions on the host under the address and undefined-behaviour sanitizers, against
-// tests/exetable_model.py.
+// tests/exetable_model.py.  Further down: the chips (Out, the changed flags, the sub-chips' advice) for exechips.hip, and what the two
+// entries share on the device.
 //
 // A step is (pc, inst, a, regs[reg_count] BEFORE the step, flag BEFORE the step, value); its successor is the next step, the zero row
 // behind the last one.  inst packs the opcode in bits 0 - 4, ri in bits 8 - 11, rj in bits 12 - 15 and "operand A is a register" in bit 16;
@@ -218,5 +219,189 @@ TRH_HD Row exe_row(u32 W, u32 R, u32 entry, const Step& st) {
     return r;
 }
 
+
+// ---- the chips: Out, the changed flags and the sub-chips' advice (trh_exe_chips_dev, csrc/exechips.hip) ----------------------------------------
+// A second per-opcode table, chips[opcode] (include/trh.h TRH_CHIP_*): bits 0 - 12 the reference's Out in Out::new order, bit 13 b_flag,
+// bits 14 - 16 ch_pc, ch_flag, ch_reg[ri]; 0xFFFFFFFF for an opcode the table does not know.  Columns, R = reg_count
+// (chip_columns(R) = 52 + R):
+//   out_* (13) | ch_reg[R] ch_pc ch_flag | the CHIP_CELLS = 37 cells below, which chip_row() yields in this order
+//   a_even a_odd b_even b_odd c_even c_odd d_even d_odd | es_word es_even es_odd os_word os_even os_odd
+//   sg_a_{msb sigma check check_even check_odd} sg_b_{..} sg_c_{..} | r_word r_even r_odd | a_shift a_power | a_flag | lsb_b b_flag
+// A cell is computed on a row whose mask has one of the cell's enabling bits and is zero elsewhere; halves, msb, sigma and check come from
+// an input that is a word (0 <= v < 2^W), else the whole group is zero.  The a_flag cell of chip_row() is the DENOMINATOR c + flag' (on
+// flag2 rows): the inversion is the field's, csrc/exechips.hip does it.
+// Magnitudes stay below 2^64: every value of exe_row but SHR_LO is at most 2^32, |SHR_LO| <= (2^32 - 1)^2, and two SHR_LO of one row are
+// equal, so |c - a - 1| < 2^64.
+enum { OUT_AND = 0, OUT_XOR, OUT_OR, OUT_SUM, OUT_PROD, OUT_SSUM, OUT_SPROD, OUT_MOD, OUT_SHIFT, OUT_FLAG1, OUT_FLAG2, OUT_FLAG3, OUT_FLAG4, OUTS };
+constexpr u32 CHIP_BITS = 17;  // the bits a chips entry may set
+enum { CELL_A_EVEN = 0, CELL_B_EVEN = 2, CELL_C_EVEN = 4, CELL_D_EVEN = 6, CELL_ES_WORD = 8, CELL_OS_WORD = 11, CELL_SG_A = 14, CELL_SG_B = 19, CELL_SG_C = 24,
+       CELL_R_WORD = 29, CELL_A_SHIFT = 32, CELL_A_POWER = 33, CELL_A_FLAG = 34, CELL_LSB_B = 35, CELL_B_FLAG = 36, CHIP_CELLS = 37 };
+TRH_HD u32 chip_columns(u32 R) { return 52u + R; }
+TRH_HD u32 col_out(u32 o) { return o; }
+TRH_HD u32 col_ch_reg(u32 k) { return (u32)OUTS + k; }
+TRH_HD u32 col_ch_pc(u32 R) { return (u32)OUTS + R; }
+TRH_HD u32 col_ch_flag(u32 R) { return (u32)OUTS + R + 1u; }
+TRH_HD u32 col_cell(u32 R, u32 cell) { return (u32)OUTS + R + 2u + cell; }
+TRH_HD bool chips_word_bits_ok(u32 W) { return word_bits_ok(W) && (W & 1u) == 0; }  // the signed check puts the sign at an odd bit
+
+enum { CHIPS_BAD_BIT = 0, CHIPS_BAD_R, CHIPS_BAD_B_FLAG, CHIPS_BAD_KNOWN, CHIPS_FAULTS };
+// the first opcode whose chips entry is refused, as opcode * CHIPS_FAULTS + fault; OPCODES * CHIPS_FAULTS for a good table
+TRH_HD u32 chips_first_bad(const u32* selection, const u32* chips) {
+    for (u32 op = 0; op < OPCODES; ++op) {
+        const u32 e = chips[op];
+        if ((e == UNKNOWN_ENTRY) != (selection[op] == UNKNOWN_ENTRY)) return op * CHIPS_FAULTS + CHIPS_BAD_KNOWN;
+        if (e == UNKNOWN_ENTRY) continue;
+        if (e >> CHIP_BITS) return op * CHIPS_FAULTS + CHIPS_BAD_BIT;
+        if ((e & (u32)TRH_CHIP_FLAG3) && (e & (u32)TRH_CHIP_SHIFT)) return op * CHIPS_FAULTS + CHIPS_BAD_R;  // they share r_word, r_even, r_odd
+        if ((e & (u32)TRH_CHIP_B_FLAG) && !(e & (u32)TRH_CHIP_FLAG4)) return op * CHIPS_FAULTS + CHIPS_BAD_B_FLAG;
+    }
+    return OPCODES * CHIPS_FAULTS;
+}
+
+TRH_HD bool is_word(u32 W, const Value& v) { return !v.negative && v.magnitude < word_limit(W); }
+TRH_HD Value negated(const Value& v) { Value r; r.magnitude = v.magnitude; r.negative = !v.negative && v.magnitude != 0; return r; }
+// x + y in sign and magnitude (zero is never negative); the caller keeps the magnitudes' sum below 2^64
+TRH_HD Value sum_of(const Value& x, const Value& y) {
+    Value r;
+    if (x.negative == y.negative) { r.magnitude = x.magnitude + y.magnitude; r.negative = x.negative; return r; }
+    const bool x_wins = x.magnitude >= y.magnitude;
+    r.magnitude = x_wins ? x.magnitude - y.magnitude : y.magnitude - x.magnitude;
+    r.negative = r.magnitude != 0 && (x_wins ? x.negative : y.negative);
+    return r;
+}
+
+// the even / odd split of `v` when `on` and v is a word, else two zeros: cells at, at + 1
+template <class Put>
+TRH_HD void put_halves(Put& put, u32 at, bool on, u32 W, const Value& v) {
+    const bool live = on && is_word(W, v);
+    put(at, positive(live ? even_part(v.magnitude) : 0u));
+    put(at + 1, positive(live ? odd_part(v.magnitude) : 0u));
+}
+// the signed word's msb, sigma = |signed(v)|, check = odd + (1 - 2 msb) 2^(W - 2) (never negative: a set msb is odd's bit W - 2) and check's
+// halves: cells at .. at + 4
+template <class Put>
+TRH_HD void put_signed(Put& put, u32 at, bool on, u32 W, const Value& v) {
+    const bool live = on && is_word(W, v);
+    const u64 w = live ? v.magnitude : 0u, msb = (w >> (W - 1)) & 1u, quarter = (u64)1 << (W - 2);
+    const u64 check = !live ? 0u : msb ? odd_part(w) - quarter : odd_part(w) + quarter;
+    put(at, positive(msb));
+    put(at + 1, positive(msb ? word_limit(W) - w : w));
+    put(at + 2, positive(check));
+    put(at + 3, positive(even_part(check)));
+    put(at + 4, positive(odd_part(check)));
+}
+
+// One row's CHIP_CELLS cells, handed to put(cell, value) in the order of the columns, each once: the row kernel stores them as they come
+// (no array of cells, which would live in scratch), chip_row() below collects them.  tv: the row's a, b, c, d as exe_row gives them;
+// flag_next: the successor's flag, false behind the last step.  The CELL_A_FLAG value is the DENOMINATOR c + flag' on a flag2 row.
+template <class Put>
+TRH_HD void chip_cells(u32 W, u32 mask, const Value& a, const Value& b, const Value& c, const Value& d, bool flag_next, Put& put) {
+    const auto has = [mask](u32 bits) { return (mask & bits) != 0; };
+    const u32 logic = TRH_CHIP_AND | TRH_CHIP_XOR | TRH_CHIP_OR, signed_ops = TRH_CHIP_SSUM | TRH_CHIP_SPROD;
+    put_halves(put, CELL_A_EVEN, has(TRH_CHIP_MOD | logic | signed_ops), W, a);
+    put_halves(put, CELL_B_EVEN, has(TRH_CHIP_MOD | TRH_CHIP_SUM | signed_ops | TRH_CHIP_FLAG4 | logic), W, b);
+    put_halves(put, CELL_C_EVEN, has(TRH_CHIP_XOR | TRH_CHIP_PROD | TRH_CHIP_SHIFT | signed_ops), W, c);
+    put_halves(put, CELL_D_EVEN, has(TRH_CHIP_PROD | TRH_CHIP_SPROD), W, d);
+    {  // the sums of two even-bits halves stay below 2^W
+        const bool live = has(logic) && is_word(W, a) && is_word(W, b);
+        const Value es = positive(live ? even_part(a.magnitude) + even_part(b.magnitude) : 0u), os = positive(live ? odd_part(a.magnitude) + odd_part(b.magnitude) : 0u);
+        put(CELL_ES_WORD, es); put_halves(put, CELL_ES_WORD + 1, true, W, es);
+        put(CELL_OS_WORD, os); put_halves(put, CELL_OS_WORD + 1, true, W, os);
+    }
+    put_signed(put, CELL_SG_A, has(signed_ops), W, a);
+    put_signed(put, CELL_SG_B, has(TRH_CHIP_SPROD | TRH_CHIP_FLAG4), W, b);
+    put_signed(put, CELL_SG_C, has(signed_ops), W, c);
+    {  // flag3 and shift are never both set: chips_first_bad
+        Value rem = positive(0);
+        if (has(TRH_CHIP_FLAG3)) { if (c.magnitude != 0) rem = sum_of(sum_of(c, negated(a)), negated(positive(1))); }
+        else if (has(TRH_CHIP_SHIFT) && (a.negative || a.magnitude <= W)) rem = sum_of(positive(W), negated(a));
+        put(CELL_R_WORD, rem);
+        put_halves(put, CELL_R_WORD + 1, true, W, rem);
+    }
+    // a_power = 2^min(a, W): saturated where the reference's 2u64.pow overflows; 0 for a negative a
+    const bool shift = has(TRH_CHIP_SHIFT), flag4 = has(TRH_CHIP_FLAG4);
+    put(CELL_A_SHIFT, positive(shift && !a.negative && a.magnitude > W ? 1u : 0u));
+    put(CELL_A_POWER, positive(!shift || a.negative ? 0u : (u64)1 << (a.magnitude < W ? (u32)a.magnitude : W)));
+    put(CELL_A_FLAG, has(TRH_CHIP_FLAG2) ? sum_of(c, positive(flag_next ? 1u : 0u)) : positive(0));
+    put(CELL_LSB_B, positive(flag4 ? b.magnitude & 1u : 0u));
+    put(CELL_B_FLAG, positive(flag4 && (mask & (u32)TRH_CHIP_B_FLAG) ? 1u : 0u));
+}
+
+struct ChipRow { Value cell[CHIP_CELLS]; };
+struct ChipRowPut {
+    ChipRow* row;
+    u32 next;  // the cells come in the order of the columns
+    TRH_HD void operator()(u32 cell, const Value& v) { if (cell == next) row->cell[next++] = v; }
+};
+// the same as an array (the host's form: tests/native/exechips_vec_test.cpp); `complete` is false if a cell came out of order or twice
+TRH_HD ChipRow chip_row(u32 W, u32 mask, const Value* tv, bool flag_next, bool* complete) {
+    ChipRow r;
+    for (u32 k = 0; k < CHIP_CELLS; ++k) r.cell[k] = positive(0);
+    ChipRowPut put{&r, 0u};
+    chip_cells(W, mask, tv[0], tv[1], tv[2], tv[3], flag_next, put);
+    *complete = put.next == CHIP_CELLS;
+    return r;
+}
+
+template <class F>
+TRH_HD Fe<F> fe_from_value(const Value& v) {
+    const Fe<F> r = fe_from_u64<F>(v.magnitude);
+    return v.negative ? fe_neg(r) : r;
+}
+
 }  // namespace exetable
 }  // namespace trh
+
+// ---- what the two entries over the steps share on the device (exetable.hip, exechips.hip) ---------------------------------------------------
+#ifdef __HIPCC__
+#include "ctx.h"
+namespace trh {
+namespace exetable {
+
+struct StepPtrs {
+    const u32 *pc, *inst, *a, *value, *regs, *flag_bits;
+    size_t m;
+    u32 word_bits, reg_count;
+};
+struct Selection { u32 e[OPCODES]; };  // a per-opcode table in a kernel's arguments: the selection, or the chips
+
+// t.e[opcode] without an indexed read of the argument block (which would move the table to scratch): opcode < 32 always
+__device__ __forceinline__ u32 entry_of(const Selection& t, u32 opcode) {
+    u32 e = UNKNOWN_ENTRY;
+#pragma unroll
+    for (u32 o = 0; o < OPCODES; ++o) e = o == opcode ? t.e[o] : e;
+    return e;
+}
+
+// the step's own scalars and what it reads of its successor (index m of no array is read); the validation has passed, so ri, rj and a
+// register operand are below reg_count and every register read stays inside the step's own block
+__device__ __forceinline__ Step load_step(const StepPtrs& g, size_t r) {
+    const u32 R = g.reg_count, inst = g.inst[r], ri = inst_ri(inst);
+    const u32* __restrict__ regs = g.regs + r * R;
+    const bool has_next = r + 1 < g.m;
+    Step st;
+    st.pc = g.pc[r]; st.inst = inst; st.a = g.a[r]; st.value = g.value[r];
+    st.reg_ri = regs[ri]; st.reg_rj = regs[inst_rj(inst)]; st.reg_a = inst_a_is_reg(inst) ? regs[st.a] : 0u;
+    st.pc_next = has_next ? g.pc[r + 1] : 0u;
+    st.reg_next_ri = has_next ? regs[R + ri] : 0u;
+    return st;
+}
+
+// what both entries take: the step arrays, the selection and the destination (`who` names the entry in the refusals' text)
+struct StepArgs {
+    u32 word_bits, reg_count;
+    const u32 *pc, *inst, *a, *value, *regs, *flag_bits;
+    size_t m;
+    const u32* selection;
+    void* dst;
+    size_t n;
+};
+int check_step_args(const char* who, int field, const StepArgs& a);
+// exe_validate_kernel over the steps into a verdict of n_sums sum words and one min word, and the host's read of it -- the one
+// synchronisation, before anything is written: TRH_EINVAL naming the first step that breaks a rule.  sums_dev (may be null): the sum words,
+// which later kernels on s may add to
+int steps_verdict(const char* who, Ctx& c, const StepPtrs& g, const Selection& t, hipStream_t s, size_t n_sums, unsigned long long** sums_dev);
+
+}  // namespace exetable
+}  // namespace trh
+#endif

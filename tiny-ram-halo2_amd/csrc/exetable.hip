@@ -20,21 +20,6 @@ namespace {
 
 using namespace exetable;
 
-struct StepPtrs {
-    const u32 *pc, *inst, *a, *value, *regs, *flag_bits;
-    size_t m;
-    u32 word_bits, reg_count;
-};
-struct Selection { u32 e[OPCODES]; };
-
-// t.e[opcode] without an indexed read of the argument block (which would move the table to scratch): opcode < 32 always
-__device__ __forceinline__ u32 entry_of(const Selection& t, u32 opcode) {
-    u32 e = UNKNOWN_ENTRY;
-#pragma unroll
-    for (u32 o = 0; o < OPCODES; ++o) e = o == opcode ? t.e[o] : e;
-    return e;
-}
-
 __global__ void __launch_bounds__(EXE_THREADS) exe_validate_kernel(StepPtrs g, Selection t, unsigned long long* __restrict__ first_bad) {
     const size_t i = (size_t)blockIdx.x * EXE_THREADS + threadIdx.x;
     if (i >= g.m) return;
@@ -42,12 +27,6 @@ __global__ void __launch_bounds__(EXE_THREADS) exe_validate_kernel(StepPtrs g, S
     const bool ok = step_ok(g.word_bits, g.reg_count, entry_of(t, inst_opcode(inst)), g.pc[i], inst, g.a[i], g.value[i], i + 1 == g.m) &&
                     step_regs_ok(g.word_bits, g.reg_count, g.regs + i * g.reg_count);
     if (!ok) atomicMin(first_bad, (unsigned long long)i);
-}
-
-template <class F>
-__device__ __forceinline__ Fe<F> fe_from_value(const Value& v) {
-    const Fe<F> r = fe_from_u64<F>(v.magnitude);
-    return v.negative ? fe_neg(r) : r;
 }
 
 // the validation has passed: ri, rj and a register operand are below reg_count, so every register read stays inside the step's own block
@@ -60,14 +39,9 @@ __global__ void __launch_bounds__(EXE_THREADS) exe_rows_kernel(StepPtrs g, Selec
             for (u32 c = 0; c < ncols; ++c) store_zero(cell(c));
             continue;
         }
-        const u32 inst = g.inst[r], ri = inst_ri(inst);
+        const Step st = load_step(g, r);
+        const u32 inst = st.inst;
         const u32* __restrict__ regs = g.regs + r * R;
-        const bool has_next = r + 1 < g.m;  // the successor of the last step is the zero row: index m of no array is read
-        Step st;
-        st.pc = g.pc[r]; st.inst = inst; st.a = g.a[r]; st.value = g.value[r];
-        st.reg_ri = regs[ri]; st.reg_rj = regs[inst_rj(inst)]; st.reg_a = inst_a_is_reg(inst) ? regs[st.a] : 0u;
-        st.pc_next = has_next ? g.pc[r + 1] : 0u;
-        st.reg_next_ri = has_next ? regs[R + ri] : 0u;
         const Row row = exe_row(g.word_bits, R, entry_of(t, inst_opcode(inst)), st);
         const Fe<F> one = fe_one<F>();
 
@@ -97,37 +71,61 @@ __global__ void __launch_bounds__(EXE_THREADS) exe_rows_kernel(StepPtrs g, Selec
     }
 }
 
-int check_args(int field, const trh_exe_table_args_t* a) {
-    if (!a) { set_error("exe_table_dev: null arguments"); return TRH_EINVAL; }
-    TRH_TRY(check_field(field));
-    if (!word_bits_ok(a->word_bits)) { set_error("exe_table_dev: word_bits %u outside 2 .. 32", a->word_bits); return TRH_EINVAL; }
-    if (!reg_count_ok(a->reg_count)) { set_error("exe_table_dev: reg_count %u outside 1 .. %u", a->reg_count, MAX_REGS); return TRH_EINVAL; }
-    const u32 bad = table_first_bad(a->selection);
-    if (bad != OPCODES * VARS) {
-        set_error("exe_table_dev: selection[%u] gives variable %c the source %u, for which it has no selector column", bad / VARS, "abcd"[bad % VARS],
-                  entry_source(a->selection[bad / VARS], bad % VARS));
-        return TRH_EINVAL;
-    }
-    if (a->m == 0 || a->m >= a->n) { set_error("exe_table_dev: %zu steps do not fit columns of %zu rows (1 <= m < n: the row behind the trace closes it)", a->m, a->n); return TRH_EINVAL; }
-    if (a->n >= ((u64)1 << 32)) { set_error("exe_table_dev: n out of range"); return TRH_EINVAL; }
-    if (!a->dst || ((uintptr_t)a->dst & 15) != 0) { set_error("exe_table_dev: dst must be a 16-byte aligned device pointer"); return TRH_EINVAL; }
-    if (!a->pc || !a->inst || !a->a || !a->value || !a->regs || !a->flag_bits) { set_error("exe_table_dev: null step array"); return TRH_EINVAL; }
-    if ((((uintptr_t)a->pc | (uintptr_t)a->inst | (uintptr_t)a->a | (uintptr_t)a->value | (uintptr_t)a->regs | (uintptr_t)a->flag_bits) & 3) != 0) {
-        set_error("exe_table_dev: the word arrays must be 4-byte aligned");
-        return TRH_EINVAL;
-    }
-    return TRH_OK;
-}
-
 }  // namespace
 }  // namespace trh
 
 using namespace trh;
 
+namespace trh {
+namespace exetable {
+
+int check_step_args(const char* who, int field, const StepArgs& a) {
+    TRH_TRY(check_field(field));
+    if (!word_bits_ok(a.word_bits)) { set_error("%s: word_bits %u outside 2 .. 32", who, a.word_bits); return TRH_EINVAL; }
+    if (!reg_count_ok(a.reg_count)) { set_error("%s: reg_count %u outside 1 .. %u", who, a.reg_count, MAX_REGS); return TRH_EINVAL; }
+    const u32 bad = table_first_bad(a.selection);
+    if (bad != OPCODES * VARS) {
+        set_error("%s: selection[%u] gives variable %c the source %u, for which it has no selector column", who, bad / VARS, "abcd"[bad % VARS],
+                  entry_source(a.selection[bad / VARS], bad % VARS));
+        return TRH_EINVAL;
+    }
+    if (a.m == 0 || a.m >= a.n) { set_error("%s: %zu steps do not fit columns of %zu rows (1 <= m < n: the row behind the trace closes it)", who, a.m, a.n); return TRH_EINVAL; }
+    if (a.n >= ((u64)1 << 32)) { set_error("%s: n out of range", who); return TRH_EINVAL; }
+    if (!a.dst || ((uintptr_t)a.dst & 15) != 0) { set_error("%s: dst must be a 16-byte aligned device pointer", who); return TRH_EINVAL; }
+    if (!a.pc || !a.inst || !a.a || !a.value || !a.regs || !a.flag_bits) { set_error("%s: null step array", who); return TRH_EINVAL; }
+    if ((((uintptr_t)a.pc | (uintptr_t)a.inst | (uintptr_t)a.a | (uintptr_t)a.value | (uintptr_t)a.regs | (uintptr_t)a.flag_bits) & 3) != 0) {
+        set_error("%s: the word arrays must be 4-byte aligned", who);
+        return TRH_EINVAL;
+    }
+    return TRH_OK;
+}
+
+int steps_verdict(const char* who, Ctx& c, const StepPtrs& g, const Selection& t, hipStream_t s, size_t n_sums, unsigned long long** sums_dev) {
+    unsigned long long* d_first_bad;  // the verdict: the smallest step index that breaks a rule
+    TRH_TRY(verdict_begin(c, n_sums, 1, s, sums_dev, &d_first_bad));
+    hipLaunchKernelGGL(exe_validate_kernel, dim3(blocks_of(g.m, EXE_THREADS)), dim3(EXE_THREADS), 0, s, g, t, d_first_bad);
+    TRH_HIP_TRY(hipGetLastError());
+    // the one synchronisation: the verdict on the steps, before the destination is touched
+    const u64* min;
+    TRH_TRY(verdict_read(c, s, nullptr, &min));
+    if (lowered(min[0])) {
+        set_error("%s: step %llu breaks the table's rules (an opcode the selection knows, ri, rj and a register operand below %u, pc, a, registers and value "
+                  "below 2^%u, Answer on the last step)", who, (unsigned long long)min[0], g.reg_count, g.word_bits);
+        return TRH_EINVAL;
+    }
+    return TRH_OK;
+}
+
+}  // namespace exetable
+}  // namespace trh
+
+using namespace trh::exetable;
+
 extern "C" {
 
 int trh_exe_table_dev(int field_id, trh_exe_table_args_t* a) {
-    TRH_TRY(check_args(field_id, a));
+    if (!a) { set_error("exe_table_dev: null arguments"); return TRH_EINVAL; }
+    TRH_TRY(check_step_args("exe_table_dev", field_id, StepArgs{a->word_bits, a->reg_count, a->pc, a->inst, a->a, a->value, a->regs, a->flag_bits, a->m, a->selection, a->dst, a->n}));
     TRH_ENTER(a->stream);
     Range range("trh_exe_table_dev");
     Ctx& c = ctx();
@@ -135,19 +133,7 @@ int trh_exe_table_dev(int field_id, trh_exe_table_args_t* a) {
     const StepPtrs g{a->pc, a->inst, a->a, a->value, a->regs, a->flag_bits, a->m, a->word_bits, a->reg_count};
     Selection t;
     for (u32 o = 0; o < OPCODES; ++o) t.e[o] = a->selection[o];
-
-    unsigned long long* d_first_bad;  // the verdict: the smallest step index that breaks a rule
-    TRH_TRY(verdict_begin(c, 0, 1, s, nullptr, &d_first_bad));
-    hipLaunchKernelGGL(exe_validate_kernel, dim3(blocks_of(a->m, EXE_THREADS)), dim3(EXE_THREADS), 0, s, g, t, d_first_bad);
-    TRH_HIP_TRY(hipGetLastError());
-    // the one synchronisation: the verdict on the steps, before the destination is touched
-    const u64* min;
-    TRH_TRY(verdict_read(c, s, nullptr, &min));
-    if (lowered(min[0])) {
-        set_error("exe_table_dev: step %llu breaks the table's rules (an opcode the selection knows, ri, rj and a register operand below %u, pc, a, registers and value "
-                  "below 2^%u, Answer on the last step)", (unsigned long long)min[0], a->reg_count, a->word_bits);
-        return TRH_EINVAL;
-    }
+    TRH_TRY(steps_verdict("exe_table_dev", c, g, t, s, 0, nullptr));
     const unsigned blocks = blocks_of(a->n, EXE_THREADS);
     with_field(field_id, [&](auto f) {
         hipLaunchKernelGGL((exe_rows_kernel<decltype(f)>), dim3(blocks < 4096u ? blocks : 4096u), dim3(EXE_THREADS), 0, s, g, t, (uint4*)a->dst, a->n);

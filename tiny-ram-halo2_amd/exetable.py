@@ -10,6 +10,9 @@ the operand, the registers and the flag before the step, the word loaded or stor
                                             operand's CONTENT as its value and CJmp's d as NONDET(PC_PLUS_ONE) (include/trh.h says why)
     build(field, word_bits, reg_count, pc, inst, a, regs, flags, value, n=...)  -> device tensor (columns, n, 4)
     witness.AdviceBuilder.exe_table(first_column, ...)                          the same into the builder's column slices
+    chip_columns(reg_count), DEFAULT_CHIPS, build_chips(...)                    the 52 + reg_count columns of the sub-chips from the same steps
+                                            (trh_exe_chips_dev; csrc/exechips.hip): Out, the changed flags, decompositions, signed words,
+                                            r, a_shift / a_power, a_flag, lsb_b / b_flag; witness.AdviceBuilder.exe_chips
 
 Which source a variable takes is data: pass selection= to build, a mapping like DEFAULT_SELECTION (opcodes it leaves out are unknown and
 refuse the steps that use them).  Steps that break a rule are refused with nothing written (api.TrhError names the first one)."""
@@ -89,12 +92,8 @@ def selection_table(selection) -> list:
     return table
 
 
-def build(field: str, word_bits: int, reg_count: int, pc, inst, a, regs, flags, value, n: int | None = None, selection=None, out=None, stream=None,
-          m: int | None = None):
-    """pc / inst / a / value: m words each, regs: m x reg_count words (step-major, the registers before the step): numpy arrays (uploaded) or
-    device tensors of 32-bit words; flags: a bool array (packed with witness.pack_bits) or a device tensor of ceil(m / 32) bitmap words.  m
-    defaults to pc's length.  n: rows per column (default: out's); out: a (columns, n, 4) int64 device tensor to write into.  Asynchronous
-    on `stream` once the steps have passed validation."""
+def _steps(word_bits, reg_count, pc, inst, a, regs, flags, value, n, out, m, ncols):
+    """the step arrays on out's device (or the current one) and the destination: what build and build_chips share"""
     import torch
     dev = _device() if out is None else out.device
     pc, inst, a, value = _words(pc, dev, "pc"), _words(inst, dev, "inst"), _words(a, dev, "a"), _words(value, dev, "value")
@@ -111,11 +110,75 @@ def build(field: str, word_bits: int, reg_count: int, pc, inst, a, regs, flags, 
     if n is None:
         assert out is not None, "n= or out="
         n = out.shape[1]
-    ncols = 28 + 9 * reg_count
     out = _out(out, (ncols, n, 4), dev)
     ptr = lambda t: t.data_ptr() if t.numel() else None  # noqa: E731
-    args = api.ExeTableArgs(word_bits=word_bits, reg_count=reg_count, pc=ptr(pc), inst=ptr(inst), a=ptr(a), value=ptr(value), regs=ptr(regs),
-                            flag_bits=ptr(flag_bits), m=m, selection=(ctypes.c_uint32 * 32)(*selection_table(DEFAULT_SELECTION if selection is None else selection)),
-                            dst=out.data_ptr(), n=n, stream=_stream(stream, dev))
+    keep = (pc, inst, a, value, regs, flag_bits)
+    return dict(word_bits=word_bits, reg_count=reg_count, pc=ptr(pc), inst=ptr(inst), a=ptr(a), value=ptr(value), regs=ptr(regs), flag_bits=ptr(flag_bits), m=m,
+                dst=out.data_ptr(), n=n), out, dev, keep
+
+
+def build(field: str, word_bits: int, reg_count: int, pc, inst, a, regs, flags, value, n: int | None = None, selection=None, out=None, stream=None,
+          m: int | None = None):
+    """pc / inst / a / value: m words each, regs: m x reg_count words (step-major, the registers before the step): numpy arrays (uploaded) or
+    device tensors of 32-bit words; flags: a bool array (packed with witness.pack_bits) or a device tensor of ceil(m / 32) bitmap words.  m
+    defaults to pc's length.  n: rows per column (default: out's); out: a (columns, n, 4) int64 device tensor to write into.  Asynchronous
+    on `stream` once the steps have passed validation."""
+    fields, out, dev, keep = _steps(word_bits, reg_count, pc, inst, a, regs, flags, value, n, out, m, 28 + 9 * reg_count)
+    args = api.ExeTableArgs(selection=(ctypes.c_uint32 * 32)(*selection_table(DEFAULT_SELECTION if selection is None else selection)), stream=_stream(stream, dev), **fields)
     api._check(api.lib().trh_exe_table_dev(api.FIELD_ID[field], ctypes.byref(args)))
+    del keep
+    return out
+
+
+# ---- the chips: Out, the changed flags and the sub-chips' advice (trh_exe_chips_dev) ---------------------------------------------------------
+# TRH_CHIP_*: bits 0 - 12 are the reference's Out in Out::new order
+AND, XOR_, OR, SUM, PROD, SSUM, SPROD, MOD, SHIFT, FLAG1, FLAG2, FLAG3, FLAG4, B_FLAG, CH_PC, CH_FLAG, CH_REG = (1 << i for i in range(17))
+OUT_NAMES = ("and", "xor", "or", "sum", "prod", "ssum", "sprod", "mod", "shift", "flag1", "flag2", "flag3", "flag4")
+INVERSE_STRIP = 8  # csrc/exechips_inv.h EXE_CHIPS_STRIP: rows per lane of the inversion kernel
+
+# out.rs:148-349 and the `ch:` fields of aux.rs:109-396
+DEFAULT_CHIPS = {
+    "and": AND | FLAG1 | FLAG2 | CH_REG | CH_FLAG, "or": OR | FLAG1 | FLAG2 | CH_REG | CH_FLAG, "xor": XOR_ | FLAG1 | FLAG2 | CH_REG | CH_FLAG,
+    "not": XOR_ | FLAG1 | FLAG2 | CH_REG | CH_FLAG,
+    "add": SUM | CH_REG | CH_FLAG, "sub": SUM | CH_REG | CH_FLAG,
+    "mull": PROD | FLAG1 | FLAG2 | CH_REG | CH_FLAG, "umulh": PROD | FLAG1 | FLAG2 | CH_REG | CH_FLAG, "smulh": SPROD | FLAG1 | FLAG2 | CH_REG | CH_FLAG,
+    "udiv": MOD | FLAG1 | FLAG2 | FLAG3 | CH_REG | CH_FLAG, "umod": MOD | FLAG1 | FLAG2 | FLAG3 | CH_REG | CH_FLAG,
+    "shl": SHIFT | FLAG4 | B_FLAG | CH_REG | CH_FLAG, "shr": SHIFT | FLAG4 | CH_REG | CH_FLAG,
+    "cmpe": XOR_ | FLAG1 | FLAG2 | CH_FLAG,
+    "cmpa": SUM | CH_FLAG, "cmpae": SUM | CH_FLAG, "cmpg": SSUM | CH_FLAG, "cmpge": SSUM | CH_FLAG,
+    "mov": XOR_ | CH_REG, "cmov": MOD | CH_REG,
+    "jmp": XOR_ | CH_PC, "cjmp": MOD | CH_PC, "cnjmp": MOD | CH_PC,
+    "load.w": CH_REG, "store.w": XOR_, "answer": 0,
+}
+
+
+def chip_columns(reg_count: int) -> tuple:
+    """the 52 + reg_count column names of build_chips, in the order of the result"""
+    names = [f"out_{x}" for x in OUT_NAMES] + [f"ch_reg{i}" for i in range(reg_count)] + ["ch_pc", "ch_flag"]
+    names += [f"{v}_{half}" for v in "abcd" for half in ("even", "odd")]
+    names += [f"{s}_{x}" for s in ("es", "os") for x in ("word", "even", "odd")]
+    names += [f"sg_{v}_{x}" for v in "abc" for x in ("msb", "sigma", "check", "check_even", "check_odd")]
+    names += ["r_word", "r_even", "r_odd", "a_shift", "a_power", "a_flag", "lsb_b", "b_flag"]
+    return tuple(names)
+
+
+def chips_table(chips) -> list:
+    """a mapping opcode (name or number) -> TRH_CHIP_* bits into the 32 words of trh_exe_chips_args_t.chips"""
+    table = [UNKNOWN] * 32
+    for op, bits in chips.items():
+        assert 0 <= bits < 1 << 32
+        table[OPCODES[op] if isinstance(op, str) else op] = bits
+    return table
+
+
+def build_chips(field: str, word_bits: int, reg_count: int, pc, inst, a, regs, flags, value, n: int | None = None, selection=None, chips=None, out=None,
+                stream=None, m: int | None = None):
+    """the 52 + reg_count columns of chip_columns from the same steps as build (include/trh.h says what each cell is): -> device tensor
+    (columns, n, 4).  chips: a mapping like DEFAULT_CHIPS, which must know exactly the opcodes `selection` knows.  word_bits must be even.
+    Asynchronous on `stream` once the steps have passed validation; it reads no column of build's, and the two can run in either order."""
+    fields, out, dev, keep = _steps(word_bits, reg_count, pc, inst, a, regs, flags, value, n, out, m, 52 + reg_count)
+    args = api.ExeChipsArgs(selection=(ctypes.c_uint32 * 32)(*selection_table(DEFAULT_SELECTION if selection is None else selection)),
+                            chips=(ctypes.c_uint32 * 32)(*chips_table(DEFAULT_CHIPS if chips is None else chips)), stream=_stream(stream, dev), **fields)
+    api._check(api.lib().trh_exe_chips_dev(api.FIELD_ID[field], ctypes.byref(args)))
+    del keep
     return out

@@ -14,7 +14,8 @@ the (columns, n, 4) Montgomery tensors that plonk.create_proof and mock.MockProv
 
 The one table that is no per-row function of the trace, the memory-consistency table, is made from the access log by memtable.build
 (AdviceBuilder.mem_table): sorted, scanned and checked on the device.  The Exe table's temporary variables and selectors are derived from
-the steps themselves by exetable.build (AdviceBuilder.exe_table).
+the steps themselves by exetable.build (AdviceBuilder.exe_table), and the Out, changed and sub-chip columns of the same steps by
+exetable.build_chips (AdviceBuilder.exe_chips).
 """
 from __future__ import annotations
 
@@ -212,6 +213,14 @@ class AdviceBuilder:
         from . import exetable
         return exetable.build(self.field, word_bits, reg_count, pc, inst, a, regs, flags, value, selection=selection,
                               out=self._slice(first_column, 28 + 9 * reg_count), stream=stream, m=m)
+
+    def exe_chips(self, first_column: int, word_bits: int, reg_count: int, pc, inst, a, regs, flags, value, selection=None, chips=None, stream=None,
+                  m: int | None = None):
+        """the sub-chips' columns of the same steps into the 52 + reg_count columns first_column .. (exetable.chip_columns,
+        exetable.build_chips): -> the builder's own slice"""
+        from . import exetable
+        return exetable.build_chips(self.field, word_bits, reg_count, pc, inst, a, regs, flags, value, selection=selection, chips=chips,
+                                    out=self._slice(first_column, 52 + reg_count), stream=stream, m=m)
 
     def tensor(self):
         return self._t
